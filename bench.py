@@ -17,10 +17,13 @@ the next step computes, two score buffers) and all of them have completed when t
 `python bench.py --gpus N` started plainly launches its own N ranks (one child process per GPU); under
 torch.distributed.run it is one of the ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-"roofline" (dominant kernel, algorithmic work / HIP-event time measured in this run) and
-"cpu_baseline" (the CPU oracle timed on this box's host cores on a bounded sample; 1 core, with the
-all-core vectorised variant beside it under "all_cores").
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and prints the headline
+(metric, value, unit, higher_is_better, dtype, ms_per_step, the configuration).  --full adds what takes time of its own:
+"parity" (a seeded sample of the last step's counts and scores against the CPU oracle), "roofline" and "kernels"
+(dominant kernel, algorithmic work / HIP-event time measured in this run), the collective's self-check under "gather"
+and "cpu_baseline" (the CPU oracle timed on this box's host cores on a bounded sample; 1 core, with the all-core
+vectorised variant beside it under "all_cores").
+--dump-outputs DIR writes what the last timed step computed (rank 0's shard) as .npy files; see dump_outputs().
 """
 import argparse
 import glob
@@ -175,6 +178,42 @@ def latest_traffic(kernel, config=1):
     return None, None, None
 
 
+DUMP_SCORES_WHOLE = 1 << 22      # score vectors up to this length are written whole (32 MB of float64) ...
+DUMP_SCORES_SAMPLE = 1 << 20     # ... longer ones as a seeded sample of this many rows (values + row numbers: 16 MB)
+DUMP_COUNTS_BYTES = 24 << 20     # count rows as float32 (exact: a count never exceeds 2^24), a seeded sample of this size
+DUMP_SEED = 20261016
+
+
+def _dump_rows(n, m):
+    """The same sorted row numbers for the same (n, m), run after run."""
+    if m >= n:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+
+
+def dump_outputs(dirname, counts, scores, status):
+    """What a caller of the timed path receives from its last step, as DIR/<name>.npy (float32 / float64, < 64 MB):
+    scores.npy (float64 per contig), counts.npy (float32 k-mer count rows), status.npy (float64 [rows with a NaN score]).
+    Vectors too long to write whole are a seeded sample of rows whose row numbers go to score_rows.npy / count_rows.npy."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n, D = counts.shape
+    srows = _dump_rows(n, DUMP_SCORES_SAMPLE) if n > DUMP_SCORES_WHOLE else None
+    crows = _dump_rows(n, max(1, DUMP_COUNTS_BYTES // (4 * D)))
+    out = {"status": np.array([status.item()], dtype=np.float64)}
+    if srows is None:
+        out["scores"] = scores.cpu().numpy().astype(np.float64)
+    else:
+        out["scores"] = scores[torch.from_numpy(srows).to(scores.device)].cpu().numpy().astype(np.float64)
+        out["score_rows"] = srows.astype(np.float64)
+    sel = counts if crows is None else counts[torch.from_numpy(crows).to(counts.device)]
+    out["counts"] = sel.cpu().numpy().view(np.uint32).astype(np.float32)
+    if crows is not None:
+        out["count_rows"] = crows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -186,20 +225,27 @@ def main():
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--refs", type=int, default=None, help="synthetic reference genomes (configs 2, 4)")
     ap.add_argument("--method", default="combo")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--parity-contigs", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity check against the CPU oracle, the per-kernel and "
+                         "roofline figures, the collective's self-check and the CPU baseline (a plain run only times)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--parity-contigs", type=int, default=None, help="contigs of --full's parity check")
     ap.add_argument("--workload", default="uniform", choices=["uniform", "ragged"],
                     help="uniform: the BASELINE configuration (fixed-length, uniform i.i.d. contigs; the headline). "
                          "ragged: heavy-tailed lengths 5-500 kb in arbitrary order, per-contig GC 0.3-0.7, 0.1 %% N -- "
                          "a second, separately labelled workload; --contigs defaults to 200000 there")
-    ap.add_argument("--min-seconds", type=float, default=8.0,
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="time at least this long: the timed region is max(--steps, enough steps to fill it), so that a "
                          "millisecond-scale step is measured at the sustained clock (and is visible to an outside "
-                         "GPU-activity sampler); 0 = exactly --steps")
+                         "GPU-activity sampler); 0 (default) = exactly --steps")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, form the process group, all-gather the rank ids and print the line's "
                          "n_gpus / ranks_seen; no GPU work (what the CPU test of the launcher runs, over gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` started plainly (no RANK in the environment): this process becomes the launcher.  It
     # starts the N ranks as CHILD processes before anything here touches the GPU (the devices are counted in sysfs, not through the runtime), hands
@@ -233,7 +279,7 @@ def main():
 
     # worker processes of the all-core CPU baseline: forked now, before anything initialises the GPU in this process
     pool = None
-    if world_env == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and world_env == 1 and args.gpus == 1 and not args.no_cpu_baseline:
         import multiprocessing as mp
         # the job's CPU share (a 1-GPU box allots 16 of the host's cores), not the host's core count
         try:
@@ -397,16 +443,14 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     prof = ctx.profile()
-    n_fallback, n_exact = ctx.score_stats()
-    stats_ex = ctx.score_stats_ex()
-    # the collective, checked after the timed region: this rank's slice of the last step's gathered vector is its score
-    # vector bit for bit, and every rank's slice arrived (a score is never NaN for these synthetic contigs; the gather
-    # buffers start out as NaN)
+    # the collective, checked after the timed region (--full): this rank's slice of the last step's gathered vector is its
+    # score vector bit for bit, and every rank's slice arrived (a score is never NaN for these synthetic contigs; the
+    # gather buffers start out as NaN)
     gather_info = None
     if dist:
         gather_info = {"backend": dist.get_backend(), "async": dist.get_backend() == "nccl",
                        "bytes_per_rank_per_step": n * 8}
-        if gathered_buf is not None and dist.get_backend() == "nccl":
+        if args.full and gathered_buf is not None and dist.get_backend() == "nccl":
             b = (nstep[0] - 1) & 1
             mine = gathered_buf[b][rank * n:(rank + 1) * n]
             gather_info["gathered_equals_scores"] = bool(torch.equal(mine, scores_buf[b]))
@@ -419,9 +463,45 @@ def main():
             dist.destroy_process_group()
         return
 
+    out = {
+        "metric": ("Gbases/s k-mer-count+score, k=%d, ragged 5-500 kb contigs" % k) if ragged else
+                  "Gbases/s k-mer-count+score, k=%d, %d kb contigs" % (k, L // 1000),
+        "value": world * T * steps / elapsed / 1e9,
+        "unit": "Gbases/s", "n_gpus": world, "ranks_seen": seen, "steps": steps, "steps_requested": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": ("u32 counts + int8 MFMA proposal (exact integer counts x 24-bit fixed-point reference columns in three int8 "
+                  "parts, exact int32 accumulate; the upper two parts in the sweep, the third added as an exact integer product "
+                  "to the window's candidates) + f64 decision") if "phk_knn_i8_general_kernel" in prof else
+                 "u32 counts + f16 MFMA proposal (exact integer counts x fp16 reference parts, f32 accumulate; k=4: high parts in the sweep, low parts added in f64 to the window's candidates) + f64 decision",
+        "data": ("synthetic (seeded, device-generated: heavy-tailed lengths 5-500 kb in arbitrary order, per-contig GC "
+                 "0.3-0.7, 0.1 % invalid bases); reference matrix: " if ragged else
+                 "synthetic (seeded uniform ATGC contigs, device-generated); reference matrix: ") + ref_name,
+        "config": {"workload": ("RAGGED (not the BASELINE configuration): k=%d, %d contigs per GPU, %.2f Gbases, mean %d / max %d "
+                                "bases, validity mask, count+normalise+%s score, %d reference rows + %d centroids"
+                                % (k, n, T / 1e9, T // n, int(lengths.max()), args.method, M, C)) if ragged else
+                               "BASELINE configs[%d]: k=%d, %d x %d-base contigs per GPU, count+normalise+%s score, "
+                               "%d reference rows + %d centroids" % (args.config, k, n, L, args.method, M, C),
+                   "contigs_per_gpu": n, "contig_length": L, "k": k, "method": args.method,
+                   "parallelism": "contig shards, %d rank(s), replicated reference, final all-gather of scores" % world},
+        "timed_region_s": elapsed,
+    }
+    if gather_info:
+        out["gather"] = gather_info
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, counts, scores, status)
+    if not args.full:
+        print(json.dumps(out))
+        if dist:
+            dist.destroy_process_group()
+        return
+
     # ---- parity spot check against the oracle (outside the timed region) ----
     from oracle import oracle
     from phamers_amd import synth
+    n_fallback, n_exact = ctx.score_stats()
+    stats_ex = ctx.score_stats_ex()
     npar = args.parity_contigs if args.parity_contigs is not None else (256 if D * M <= 256 * 5000 else 24)
     npar = min(npar, n)
     if ragged:
@@ -520,28 +600,7 @@ def main():
     if issue:
         roofline["mfma_issue_frac"] = issue * kernels[dom]["frac"]
 
-    out = {
-        "metric": ("Gbases/s k-mer-count+score, k=%d, ragged 5-500 kb contigs" % k) if ragged else
-                  "Gbases/s k-mer-count+score, k=%d, %d kb contigs" % (k, L // 1000),
-        "value": world * T * steps / elapsed / 1e9,
-        "unit": "Gbases/s", "n_gpus": world, "ranks_seen": seen, "steps": steps, "steps_requested": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": ("u32 counts + int8 MFMA proposal (exact integer counts x 24-bit fixed-point reference columns in three int8 "
-                  "parts, exact int32 accumulate; the upper two parts in the sweep, the third added as an exact integer product "
-                  "to the window's candidates) + f64 decision") if "phk_knn_i8_general_kernel" in prof else
-                 "u32 counts + f16 MFMA proposal (exact integer counts x fp16 reference parts, f32 accumulate; k=4: high parts in the sweep, low parts added in f64 to the window's candidates) + f64 decision",
-        "data": ("synthetic (seeded, device-generated: heavy-tailed lengths 5-500 kb in arbitrary order, per-contig GC "
-                 "0.3-0.7, 0.1 % invalid bases); reference matrix: " if ragged else
-                 "synthetic (seeded uniform ATGC contigs, device-generated); reference matrix: ") + ref_name,
-        "config": {"workload": ("RAGGED (not the BASELINE configuration): k=%d, %d contigs per GPU, %.2f Gbases, mean %d / max %d "
-                                "bases, validity mask, count+normalise+%s score, %d reference rows + %d centroids"
-                                % (k, n, T / 1e9, T // n, int(lengths.max()), args.method, M, C)) if ragged else
-                               "BASELINE configs[%d]: k=%d, %d x %d-base contigs per GPU, count+normalise+%s score, "
-                               "%d reference rows + %d centroids" % (args.config, k, n, L, args.method, M, C),
-                   "contigs_per_gpu": n, "contig_length": L, "k": k, "method": args.method,
-                   "parallelism": "contig shards, %d rank(s), replicated reference, final all-gather of scores" % world},
+    out.update({
         "roofline": roofline,
         "kernels": kernels,
         # per-kernel times are HIP events around each launch on the stream it runs on: in a call of several scoring batches
@@ -549,10 +608,7 @@ def main():
         # kernels' times overlap the sweep's and the column does not add up to the step
         "kernel_times_overlap": bool(k == 4 and n > (1 << 20)),
         "parity": parity,
-        "timed_region_s": elapsed,
-    }
-    if gather_info:
-        out["gather"] = gather_info
+    })
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(k, L if not ragged else int(T // n), pos, neg, cpos, cneg, pool=pool)
     if pool is not None:

@@ -134,7 +134,7 @@ def test_bench_runs_the_rccl_gather_as_a_one_rank_group():
     init_process_group("nccl", device_id=...), the rank-id all-gather, the per-step asynchronous
     all_gather_into_tensor on two buffers beside the library's stream, the closing barrier, destroy_process_group.
     The line must report one rank seen, green parity, and a gathered vector equal to the score vector."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "1", "--contigs", "65536",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "1", "--contigs", "65536", "--full",
                         "--no-cpu-baseline", "--min-seconds", "0", "--steps", "3", "--warmup", "1"],
                        env=_rccl_env(PHK_BENCH_FORCE_DIST="1", PHK_BENCH_BACKEND="nccl"),
                        capture_output=True, text=True, timeout=900)

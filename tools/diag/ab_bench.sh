@@ -10,7 +10,7 @@ for r in $(seq 1 $rounds); do
   for spec in "$@"; do
     label=${spec%%=*}; lib=${spec#*=}
     if [ -n "$lib" ]; then export PHK_ALLOW_DIAGNOSTIC_BUILD=1 PHAMERS_AB_LIB=$lib; else unset PHK_ALLOW_DIAGNOSTIC_BUILD PHAMERS_AB_LIB; fi
-    python bench.py "${bargs[@]}" --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full "${bargs[@]}" --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split(chr(10))[-1])
 ks=d['kernels']; tot=sum(v['ms_per_step'] for v in ks.values()); nl=sum(v['launches_per_step'] for v in ks.values())

@@ -7,7 +7,7 @@
 # usage: tools/diag/f16h_ablate.sh <out file> ; afterwards the product build is restored
 out=${1:-gpurun_out/f16h_ablate.txt}
 run() {
-    python bench.py --min-seconds 3 --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --min-seconds 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split(chr(10))[-1])
 print('$1', 'step %.4f ms' % d['ms_per_step'], {k: round(v['ms_per_step'], 4) for k, v in d['kernels'].items() if v['ms_per_step'] > 0.05})" >> $out

@@ -22,18 +22,18 @@ done
 unset PHK_ALLOW_DIAGNOSTIC_BUILD PHAMERS_AB_LIB
 for ppm in 0 1000; do
 for lanes in "" d; do
-PHK_BENCH_RAGGED_PPM=$ppm PHK_COUNT_LANES=$lanes python bench.py --workload ragged --min-seconds 2 --no-cpu-baseline 2>/dev/null | python -c "
+PHK_BENCH_RAGGED_PPM=$ppm PHK_COUNT_LANES=$lanes python bench.py --full --workload ragged --min-seconds 2 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split(chr(10))[-1])
 print('ragged k=4 ppm $ppm lanes [$lanes]  step %.3f ms' % d['ms_per_step'], {k.replace('phk_','').replace('_kernel',''): round(v['ms_per_step'],4) for k,v in d['kernels'].items() if v['ms_per_step'] > 0.02 and 'count' in k}, d['parity']['counts_bit_exact'])" >> $out
 done
 done
 exit 0
-python bench.py --workload ragged --min-seconds 2 --no-cpu-baseline 2>/dev/null | python -c "
+python bench.py --full --workload ragged --min-seconds 2 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split(chr(10))[-1])
 print('ragged k=4 (in-tree)  step %.3f ms' % d['ms_per_step'], {k.replace('phk_','').replace('_kernel',''): round(v['ms_per_step'],4) for k,v in d['kernels'].items() if v['ms_per_step'] > 0.01}, d['parity']['counts_bit_exact'])" >> $out
-PHK_COUNT_LANES=d python bench.py --workload ragged --min-seconds 2 --no-cpu-baseline 2>/dev/null | python -c "
+PHK_COUNT_LANES=d python bench.py --full --workload ragged --min-seconds 2 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split(chr(10))[-1])
 print('ragged k=4 (slot kernel d)  step %.3f ms' % d['ms_per_step'], {k.replace('phk_','').replace('_kernel',''): round(v['ms_per_step'],4) for k,v in d['kernels'].items() if v['ms_per_step'] > 0.01}, d['parity']['counts_bit_exact'])" >> $out

@@ -6,7 +6,7 @@ out=gpurun_out/sweep_i8.txt
 mkdir -p gpurun_out
 label=${1:-default}; shift || true
 for cfg in 4 2; do
-    env "$@" timeout -k 10 240 python bench.py --config $cfg --steps 3 --warmup 1 --min-seconds 0 --no-cpu-baseline --parity-contigs 8 \
+    env "$@" timeout -k 10 240 python bench.py --full --config $cfg --steps 3 --warmup 1 --min-seconds 0 --no-cpu-baseline --parity-contigs 8 \
         > gpurun_out/sweep_tmp.json 2> gpurun_out/sweep_tmp.err
     python - "$label" "$cfg" >> $out <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/trace_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --no-cpu-baseline --min-seconds $SEC > "$OUT/bench_under_trace.json" 2> "$OUT/trace.err" || echo "trace run failed"
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $ROOT/bench.py --full --no-cpu-baseline --min-seconds $SEC > "$OUT/bench_under_trace.json" 2> "$OUT/trace.err" || echo "trace run failed"
 f=$(ls -t "$OUT"/trace/*/*_kernel_stats.csv | head -1)
 cp "$f" "$OUT/kernel_stats.csv"
 head -8 "$OUT/kernel_stats.csv" | cut -c1-60,200-330

@@ -10,7 +10,7 @@ N=${3:-}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-ARGS="--config $CFG --no-cpu-baseline --min-seconds 0"
+ARGS="--full --config $CFG --no-cpu-baseline"
 [ -n "$N" ] && ARGS="$ARGS --contigs $N"
 cd /tmp && export TMPDIR=/tmp
 echo "== kernel trace + stats"
