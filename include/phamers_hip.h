@@ -62,6 +62,7 @@ extern "C" {
 #define PHK_METHOD_KNN 1         /* scripts/phamer.py:268-273 */
 #define PHK_METHOD_KMEANS 2      /* scripts/phamer.py:240-256 (centroids supplied) */
 #define PHK_METHOD_COMBO 3       /* scripts/phamer.py:303-313 */
+#define PHK_METHOD_DENSITY 4     /* scripts/phamer.py:275-287; exclusive: not to be OR-ed with the others */
 
 typedef struct phk_ctx phk_ctx;
 typedef struct phk_model phk_model;
@@ -263,6 +264,10 @@ int phk_model_destroy(phk_ctx *ctx, phk_model *model);
 int phk_model_set_centroids(phk_ctx *ctx, phk_model *model, const double *cpos, uint64_t n_cpos, const double *cneg,
                             uint64_t n_cneg);
 int phk_model_set_column_mask(phk_ctx *ctx, phk_model *model, const uint8_t *mask);
+/* Bandwidths of the density method (phamer_scorer.positive_bandwidth / negative_bandwidth, scripts/phamer.py:82-83): the
+ * Gaussian kernel widths of the positive and the negative class.  A model starts with the reference's 0.005 / 0.01.  Each must
+ * be finite and > 0, else PHK_ERR_ARG (model unchanged). */
+int phk_model_set_bandwidths(phk_ctx *ctx, phk_model *model, double h_pos, double h_neg);
 
 /* Deterministic device k-means (opt-in alternative to the scikit-learn fit of scripts/learning.py:131-146,
  * whose centroids depend on the scikit-learn version): k-means++ seeding driven by splitmix64(seed + j),
@@ -289,15 +294,25 @@ int phk_kmeans_lloyd(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, uint
 
 /* ---- host API: scoring ------------------------------------------------------------- */
 /* phamer.score_points / phamer_scorer.score_points (scripts/phamer.py:451-468, 177-195) for
- * method in {knn, kmeans, combo}: Q[N][D] float64 host rows -> scores[N] float64.
+ * method in {knn, kmeans, combo, density}: Q[N][D] float64 host rows -> scores[N] float64.
  *   knn    : 2*(majority label of the kn nearest train rows) - 1   (scripts/learning.py:118-128)
  *   kmeans : tanh((e- - e+)/(e+ + e-)), e+/- = distance to the nearest positive / negative
  *            centroid (scripts/phamer.py:198-210, 250-256; scripts/learning.py:47-66)
  *   combo  : knn + kmeans (scripts/phamer.py:303-313)
+ *   density: L+ - L-, L = the Gaussian kernel density log-likelihood of the query under one class's unmasked train rows,
+ *            bandwidth h+ / h- (phk_model_set_bandwidths): phamer_scorer.density_score_points (scripts/phamer.py:275-287),
+ *            learning.get_density (scripts/learning.py:107-115).  float64 throughout; the result of a query does not depend
+ *            on N, on the batch it came in or on the entry point.  PHK_ERR_ARG when a class has no unmasked row.
  * Returns PHK_ERR_NAN (scores untouched) if any query element is NaN -- the reference's
  * scikit-learn call raises on such input. */
 int phk_score(phk_ctx *ctx, const phk_model *model, const double *Q, uint64_t N, int method,
               double *scores);
+
+/* KernelDensity(kernel='gaussian', bandwidth=h).fit(X).score_samples(Q) (learning.get_density, scripts/learning.py:107-115):
+ * out[q] = logsumexp_j(-|Q[q] - X[j]|^2 / (2 h^2)) - log(M) - (D/2) log(2 pi) - D log(h), float64, the density method's
+ * kernel over one data set.  Host pointers.  h must be finite and > 0 (else PHK_ERR_ARG); a NaN query row gives PHK_ERR_NAN. */
+int phk_kde_log_density(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, double h,
+                        double *out);
 
 /* learning.distances (scripts/learning.py:47-56; with np.argmin on its result: learning.closest_to :59-66): the
  * Euclidean distances of every row of Q[N][D] to every row of X[M][D], out[N][M], float64, in the reference's

@@ -15,8 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libphamers_hip.so")
 
 PHK_OK = 0
 PHK_ERR_ARG, PHK_ERR_HIP, PHK_ERR_NOMEM, PHK_ERR_UNSUPPORTED, PHK_ERR_NAN, PHK_ERR_IO = -1, -2, -3, -4, -5, -6
-METHOD_KNN, METHOD_KMEANS, METHOD_COMBO = 1, 2, 3
-METHODS = {"knn": METHOD_KNN, "kmeans": METHOD_KMEANS, "combo": METHOD_COMBO}
+METHOD_KNN, METHOD_KMEANS, METHOD_COMBO, METHOD_DENSITY = 1, 2, 3, 4
+METHODS = {"knn": METHOD_KNN, "kmeans": METHOD_KMEANS, "combo": METHOD_COMBO, "density": METHOD_DENSITY}
 MAX_K = 7
 ABI_VERSION = 2
 
@@ -83,6 +83,8 @@ SIGNATURES = {
     "phk_model_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_model_set_centroids": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64]),
     "phk_model_set_column_mask": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "phk_model_set_bandwidths": (c_int, [c_void_p, c_void_p, c_double, c_double]),
+    "phk_kde_log_density": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_double, c_void_p]),
     "phk_score": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p]),
     "phk_distances": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_pack_ascii_dev": (c_int, [c_void_p, c_void_p, c_u64, c_char_p, c_void_p, c_void_p, c_void_p]),
@@ -307,6 +309,14 @@ class Model(object):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         check(self.ctx.lib.phk_model_set_column_mask(self.ctx.handle, self.handle, ptr(m)))
 
+    def set_bandwidths(self, h_pos, h_neg):
+        """Gaussian kernel widths of the density method per class (phamer_scorer.positive_bandwidth / negative_bandwidth;
+        a model starts with the reference's 0.005 / 0.01).  ValueError unless both are finite and > 0."""
+        h_pos, h_neg = float(h_pos), float(h_neg)
+        if not (np.isfinite(h_pos) and np.isfinite(h_neg) and h_pos > 0 and h_neg > 0):
+            raise ValueError("bandwidths must be finite and > 0, got %r, %r" % (h_pos, h_neg))
+        check(self.ctx.lib.phk_model_set_bandwidths(self.ctx.handle, self.handle, h_pos, h_neg))
+
     def score(self, Q, method="combo"):
         Q = np.ascontiguousarray(Q, dtype=np.float64)
         if Q.ndim != 2 or Q.shape[1] != self.D:
@@ -314,6 +324,25 @@ class Model(object):
         out = np.empty(Q.shape[0], dtype=np.float64)
         check(self.ctx.lib.phk_score(self.ctx.handle, self.handle, ptr(Q), Q.shape[0], METHODS[method], ptr(out)))
         return out
+
+
+def kde_log_density(ctx, Q, X, h):
+    """KernelDensity(kernel='gaussian', bandwidth=h).fit(X).score_samples(Q) on the device (phk_kde_log_density): (N,) float64.
+    ValueError for NaN input or a bandwidth that is not finite and > 0, as scikit-learn raises."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if Q.ndim != 2 or X.ndim != 2 or Q.shape[1] != X.shape[1]:
+        raise ValueError("query rows and data must be 2-D with the same number of columns")
+    if X.shape[0] == 0:
+        raise ValueError("Found array with 0 sample(s) (shape=%s) while a minimum of 1 is required." % (X.shape,))
+    h = float(h)
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError("bandwidth must be finite and > 0, got %r" % (h,))
+    if np.isnan(Q).any() or np.isnan(X).any():
+        raise ValueError("Input contains NaN.")
+    out = np.empty(Q.shape[0], dtype=np.float64)
+    check(ctx.lib.phk_kde_log_density(ctx.handle, ptr(Q), Q.shape[0], ptr(X), X.shape[0], X.shape[1], h, ptr(out)))
+    return out
 
 
 class Batch(object):

@@ -6,9 +6,11 @@ The reference rebuilds everything per fold: it slices the train rows out of the 
 k-NN classifier and scores the held-out rows -- N times, although the N train sets share (N-1)/N of their rows.
 Here the full reference matrix is uploaded and prepared ONCE (`_lib.Model` over every positive and negative row); a
 fold is then
-    * a column mask over that model's train rows (the held-out rows are excluded from the k-NN search),
+    * a column mask over that model's train rows (the held-out rows are excluded from the k-NN search and, for the
+      density method, from both kernel density sums and their row counts),
     * the fold's centroids, written into the model's centroid segments (k-means on the fold's train rows: scikit-learn
-      by default, as the reference; ``kmeans='gpu'`` selects the deterministic device k-means per fold),
+      by default, as the reference; ``kmeans='gpu'`` selects the deterministic device k-means per fold; kmeans and
+      combo only),
     * one scoring call for the held-out rows.
 Scores are those of a model built from the fold's train rows alone (the k-NN search is translation invariant: only
 the error bounds depend on the centring vector, and they are evaluated for the one in use);
@@ -62,6 +64,8 @@ class cross_validator(object):
         self.kmeans = 'sklearn'                      # or 'gpu': deterministic device k-means per fold
         self.k_clusters = 86                         # scripts/phamer.py:78
         self.k_neighbors = 3                         # scripts/phamer.py:79
+        self.positive_bandwidth = 0.005              # scripts/phamer.py:82-83 (method 'density')
+        self.negative_bandwidth = 0.01
 
     # ---- the reference's entry point ----------------------------------------------------------------------
     def cross_validate(self):
@@ -71,7 +75,7 @@ class cross_validator(object):
         self.num_positive, self.num_negative = self.positive_data.shape[0], self.negative_data.shape[0]
         plan = FoldPlan(self.num_positive, self.num_negative, self.N, self.seed)
         self.positive_assignment, self.negative_assignment = plan.positive, plan.negative
-        resident = self.scoring_function is phamer.score_points and (self.method or 'combo') in ('knn', 'kmeans', 'combo')
+        resident = self.scoring_function is phamer.score_points and (self.method or 'combo') in ('knn', 'kmeans', 'combo', 'density')
         runner = self._folds_on_resident_model if resident else self._folds_through_scoring_function
         self.positive_scores, self.negative_scores = runner(plan)
         logger.info("%d-fold cross validation complete." % self.N)
@@ -99,7 +103,7 @@ class cross_validator(object):
         if np.isnan(P).any() or np.isnan(Nm).any():
             raise ValueError("Input contains NaN.")
         pos_scores, neg_scores = np.zeros(len(P)), np.zeros(len(Nm))
-        with_centroids = method != 'knn'
+        with_centroids = method in ('kmeans', 'combo')
         model = None
         ctx = _lib.get_context()
         self.model_uploads = 0
@@ -119,6 +123,8 @@ class cross_validator(object):
                                        k_neighbors=self.k_neighbors)
                     self._model_centroids = (len(cents[0]), len(cents[1])) if cents else (0, 0)
                     self.model_uploads += 1
+                    if method == 'density':
+                        model.set_bandwidths(self.positive_bandwidth, self.negative_bandwidth)
                 elif with_centroids:
                     model.set_centroids(*cents)
                 model.set_column_mask(np.concatenate((out_p, out_n)))

@@ -78,6 +78,7 @@ enum PhkSlot {
     WS_SCTL,        // scoring (MFMA path): the call's statistics totals, the two sets of counters / query lists / striped words
     WS_CTL,         // small control words the kernels keep zeroed themselves (no memset per call): the count planner's two
                     // alternating blocks (PhkCountCtl), see phk_launch_count
+    WS_KDE,         // density scoring: per-chunk (max, sum) partials + query norms (density.hip)
     WS_SLOTS
 };
 

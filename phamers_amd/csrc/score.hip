@@ -204,6 +204,8 @@ extern "C" int phk_model_create(phk_ctx *ctx, const double *pos, uint64_t n_pos,
                 rc = PHK_ERR_HIP; break;
             }
         }
+        rc = phk_model_build_density(ctx, m);
+        if (rc != PHK_OK) break;
         rc = phk_model_build_fast(ctx, m, pos, neg, cpos, cneg);
     } while (0);
     if (rc != PHK_OK) {
@@ -224,6 +226,7 @@ extern "C" int phk_model_destroy(phk_ctx *ctx, phk_model *m) {
     if (m->d_R64) (void)hipFree(m->d_R64);
     if (m->d_labels) (void)hipFree(m->d_labels);
     if (m->d_C64) (void)hipFree(m->d_C64);
+    if (m->d_rn) (void)hipFree(m->d_rn);
     phk_model_free_fast(m);
     delete m;
     return PHK_OK;
@@ -300,7 +303,8 @@ extern "C" int phk_distances(phk_ctx *ctx, const double *Q, uint64_t N, const do
 }
 
 static int check_method(const phk_model *m, int method) {
-    PHK_REQUIRE(method == PHK_METHOD_KNN || method == PHK_METHOD_KMEANS || method == PHK_METHOD_COMBO,
+    PHK_REQUIRE(method == PHK_METHOD_KNN || method == PHK_METHOD_KMEANS || method == PHK_METHOD_COMBO ||
+                    method == PHK_METHOD_DENSITY,
                 "phk_score: unknown method %d", method);
     PHK_REQUIRE(!(method & PHK_METHOD_KMEANS) || m->n_cpos > 0,
                 "phk_score: method needs centroids but the model was created without them");
@@ -322,6 +326,13 @@ int phk_score_rows(phk_ctx *ctx, const phk_model *m, const double *d_Q, const ui
         return PHK_OK;
     }
     const uint64_t D = m->D;
+
+    // density (density.hip): one dense float64 path; the MFMA proposal / force_exact knobs do not apply
+    if (method == PHK_METHOD_DENSITY) {
+        ctx->last_score_fast = false;
+        ctx->score_totals_zeroed = false;
+        return phk_score_density(ctx, m, d_Q, d_counts, N, d_scores, d_status);
+    }
 
     // PHK_FORCE_EXACT=1 routes every model through the float64 path (used by the parity tests to
     // cross-check the two GPU paths against each other)

@@ -624,6 +624,12 @@ extern "C" int phk_model_set_column_mask(phk_ctx *ctx, phk_model *m, const uint8
         PHK_HIP(hipMemcpy(m->d_col_mask, mask, m->M, hipMemcpyHostToDevice));
     }
     m->has_mask = mask != nullptr;
+    m->eff_pos = m->n_pos;   // (unmasked rows per class: the density method's n_c_eff)
+    m->eff_neg = m->n_neg;
+    if (mask) {
+        for (uint64_t c = 0; c < m->n_pos; ++c) m->eff_pos -= mask[c] ? 1 : 0;
+        for (uint64_t c = m->n_pos; c < m->M; ++c) m->eff_neg -= mask[c] ? 1 : 0;
+    }
     if (m->fast) {
         // (the fp32 / int8 operands are never masked -- those sweeps stand down while a mask is set -- so clearing the mask
         // makes them valid again unless the centroids were replaced meanwhile)

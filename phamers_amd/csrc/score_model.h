@@ -10,6 +10,10 @@ struct phk_model {
     double *d_R64 = nullptr;      // [M][D] train = vstack(pos, neg)  (scripts/phamer.py:186)
     uint8_t *d_labels = nullptr;  // [M] 1 = positive row           (scripts/phamer.py:187)
     double *d_C64 = nullptr;      // [n_cpos + n_cneg][D] centroids
+    // density method (density.hip): |r_j|^2 per train row, the two bandwidths, and the unmasked rows of each class
+    double *d_rn = nullptr;
+    double h_pos = 0.005, h_neg = 0.01;   // scripts/phamer.py:82-83
+    uint64_t eff_pos = 0, eff_neg = 0;
     // MFMA path (score_mfma.hip); null when the shape is outside it
     bool fast = false;
     double *d_colnorm = nullptr;  // |r'| per real column (train rows, pos centroids, neg centroids)
@@ -72,6 +76,11 @@ struct phk_model {
 // exact float64 batch scorer (score.hip)
 int phk_score_exact_batch(phk_ctx *ctx, const phk_model *m, const double *d_Q, uint64_t nq, int method,
                           double *d_knn, double *d_cen, uint32_t *d_status);
+
+// density method (density.hip)
+int phk_model_build_density(phk_ctx *ctx, phk_model *m);
+int phk_score_density(phk_ctx *ctx, const phk_model *m, const double *d_Q, const uint32_t *d_counts, uint64_t N,
+                      double *d_scores, uint32_t *d_status);
 
 // MFMA path hooks (score_mfma.hip)
 int phk_model_build_fast(phk_ctx *ctx, phk_model *m, const double *pos, const double *neg,

@@ -211,8 +211,8 @@ def default_scorer(device_index=None):
             return np.zeros(0)
         ctx = _lib.get_context(device_index)
         batch = _lib.Batch.from_sequences(ctx, list(sequences), kmer_length)
-        model = _lib.Model(ctx, positive, negative, cpos if method != "knn" else None,
-                           cneg if method != "knn" else None, k_neighbors)
+        cen = method in ("kmeans", "combo")     # (density and knn need no centroids)
+        model = _lib.Model(ctx, positive, negative, cpos if cen else None, cneg if cen else None, k_neighbors)
         try:
             return batch.score(model, method)
         finally:
@@ -270,8 +270,9 @@ def score_fasta_distributed(path, positive, negative, positive_centroids=None, n
         fasta.close()
     local = np.zeros(0)
     if batch is not None:
-        model = _lib.Model(ctx, positive, negative, positive_centroids if method != "knn" else None,
-                           negative_centroids if method != "knn" else None, k_neighbors)
+        cen = method in ("kmeans", "combo")     # (density and knn need no centroids)
+        model = _lib.Model(ctx, positive, negative, positive_centroids if cen else None,
+                           negative_centroids if cen else None, k_neighbors)
         try:
             if length_requirement:
                 keep = np.flatnonzero(lengths >= int(length_requirement))

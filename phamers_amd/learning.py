@@ -6,6 +6,7 @@ learning.py -- drop-in for the hot-path helpers of PhaMers' scripts/learning.py.
     closest_to(point, picks)                      scripts/learning.py:59-66     -> GPU distances + first-index argmin
     kmeans(data, k, ...)                          scripts/learning.py:131-146   -> scikit-learn's seeding on the host + its Lloyd sweeps on the GPU
     get_centroids(data, assignment)               scripts/learning.py:69-81     -> NumPy (86 means)
+    get_density(point, data, bandwidth=0.1)       scripts/learning.py:107-115   -> GPU (float64 Gaussian KDE, log_density batched)
 
 k-means reproduces the reference's scikit-learn fit (a per-run fit that does not depend on the number of
 query contigs; the golden scores are pinned to its centroids): the k-means++
@@ -210,3 +211,19 @@ def get_centroids(data, assignment):
     if len(labels) == 0:
         logger.warning("No clusters assigned to data.")
     return np.array([np.mean(data[assignment == c], axis=0) for c in labels])
+
+
+def log_density(queries, data, bandwidth=0.1):
+    """Gaussian kernel density log-likelihood of each row of ``queries`` (N, D) under ``data`` (M, D): what
+    KernelDensity(kernel='gaussian', bandwidth=bandwidth).fit(data).score_samples(queries) returns, (N,) float64,
+    computed densely in float64 on the device (phk_kde_log_density)."""
+    queries = np.asarray(queries, dtype=np.float64)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    return _lib.kde_log_density(_lib.get_context(), queries, np.asarray(data, dtype=np.float64), bandwidth)
+
+
+def get_density(point, data, bandwidth=0.1):
+    """Density of ``data`` at one point (scripts/learning.py:107-115): the scalar log-likelihood that
+    KernelDensity(kernel='gaussian', bandwidth=bandwidth).fit(data).score_samples([point])[0] returns."""
+    return float(log_density(np.asarray(point, dtype=np.float64).reshape(1, -1), data, bandwidth)[0])

@@ -2,7 +2,8 @@
 phamer.py -- drop-in for the scoring entry points of PhaMers' scripts/phamer.py, device resident.
 
     phamer_scorer            attribute surface + load_data / screen_by_length / equalize_reference_data /
-                             score_points / knn_ / kmeans_ / combo_score_points      scripts/phamer.py:42-313
+                             score_points / knn_ / kmeans_ / density_ / combo_score_points
+                                                                                    scripts/phamer.py:42-313
     score_points(scoring_data, positive_training_data, negative_training_data, method=None)
                                                                                     scripts/phamer.py:451-468
     main()                   `python -m phamers_amd.phamer -in <dir> -data <dir> [-e]`  scripts/phamer.py:512-598
@@ -15,9 +16,10 @@ reference meaning (the normalised float64 matrix) but is materialised from the d
 assigning it (as phamer.score_points and the cross-validation do) switches the object to host rows, which are
 scored through the float64-row entry point.
 
-The k-means fit that yields the centroids is scikit-learn's, as in the reference (learning.kmeans).  Methods
-outside {knn, kmeans, combo} raise NotImplementedError: dbscan / svm / density / silhouette are outside the
-accelerated path.
+The k-means fit that yields the centroids is scikit-learn's, as in the reference (learning.kmeans); the density
+method needs none (a dense float64 Gaussian kernel density per class, density.hip).  Methods outside
+{knn, kmeans, combo, density} raise NotImplementedError: dbscan / svm / silhouette are outside the accelerated path
+(SURVEY.md section 8).
 """
 import argparse
 import logging
@@ -33,8 +35,9 @@ logging.basicConfig(format='[%(asctime)s][%(levelname)s][%(funcName)s] - %(messa
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.WARNING)
 
-_GPU_METHODS = ('knn', 'kmeans', 'combo')
-_OTHER_METHODS = ('dbscan', 'svm', 'density', 'silhouette')
+_GPU_METHODS = ('knn', 'kmeans', 'combo', 'density')
+_OTHER_METHODS = ('dbscan', 'svm', 'silhouette')
+_CENTROID_METHODS = ('kmeans', 'combo')
 
 
 def _lone(directory, suffixes, avoid_stem_suffix=None):
@@ -72,6 +75,8 @@ class phamer_scorer(object):
         self.kmer_length = 4
         self.k_clusters = 86
         self.k_neighbors = 3
+        self.positive_bandwidth = 0.005     # scripts/phamer.py:82-83 (density method)
+        self.negative_bandwidth = 0.01
         # centroids of the last kmeans / combo call (inspection, tests)
         self.positive_centroids = self.negative_centroids = None
         self.scores = None
@@ -271,7 +276,7 @@ class phamer_scorer(object):
         return self.scores
 
     def _outside_path(self):
-        raise NotImplementedError("scoring method %r is outside the accelerated path; knn / kmeans / combo are "
+        raise NotImplementedError("scoring method %r is outside the accelerated path; knn / kmeans / combo / density are "
                                   "available" % (self.scoring_method,))
 
     def _centroids_of(self, pos, neg, k_clusters, deliver=None):
@@ -341,13 +346,15 @@ class phamer_scorer(object):
                                                                               self.k_clusters)
 
     def _gpu_score(self, method):
-        with_centroids = method != 'knn'
+        with_centroids = method in _CENTROID_METHODS
         if with_centroids:
             self._fit_centroids()
         model = _lib.Model(_lib.get_context(), self.positive_data, self.negative_data,
                            self.positive_centroids if with_centroids else None,
                            self.negative_centroids if with_centroids else None, k_neighbors=self.k_neighbors)
         try:
+            if method == 'density':
+                model.set_bandwidths(self.positive_bandwidth, self.negative_bandwidth)
             if self._batch is not None:
                 return self._batch.score(model, method)          # resident counts; NaN rows raise ValueError
             q = np.asarray(self._rows, dtype=np.float64)
@@ -364,6 +371,11 @@ class phamer_scorer(object):
     def kmeans_score_points(self):
         """scripts/phamer.py:240-256: tanh proximity metric to the nearest centroid of each class."""
         return self._gpu_score('kmeans')
+
+    def density_score_points(self):
+        """scripts/phamer.py:275-287: log-density under the positive class minus that under the negative class (Gaussian
+        kernels of width positive_bandwidth / negative_bandwidth; learning.get_density per class)."""
+        return self._gpu_score('density')
 
     def combo_score_points(self):
         """scripts/phamer.py:303-313: knn score + kmeans score (one fused GPU pass)."""
@@ -547,8 +559,8 @@ def _rank_count_and_score(fasta_file, part, kmer_length, method, positive, negat
         scores = np.zeros(0)
         if keep.any():
             sub = batch if keep.all() else batch.select(np.flatnonzero(keep))
-            model = _lib.Model(ctx, positive, negative, cpos if method != 'knn' else None, cneg if method != 'knn' else None,
-                               k_neighbors=k_neighbors)
+            cen = method in _CENTROID_METHODS
+            model = _lib.Model(ctx, positive, negative, cpos if cen else None, cneg if cen else None, k_neighbors=k_neighbors)
             try:
                 scores = sub.score(model, method)
             finally:
