@@ -314,6 +314,22 @@ int phk_score(phk_ctx *ctx, const phk_model *model, const double *Q, uint64_t N,
 int phk_kde_log_density(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, double h,
                         double *out);
 
+/* learning.silhouettes (scripts/learning.py:84-92, scikit-learn silhouette_samples): X[n][D] float64, labels[n] already
+ * encoded 0..n_labels-1 -> out[n].  a = mean distance to the rest of the own cluster, b = smallest mean distance to another
+ * cluster, s = (b - a) / max(a, b), 0 for a singleton.  Distances are float64 direct differences; every sum is taken in an
+ * order fixed by the labels alone, so the result is bit-identical from run to run.  Host pointers.  PHK_ERR_ARG for a
+ * label >= n_labels or n_labels outside 2..n-1; PHK_ERR_NAN for NaN rows. */
+int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const uint32_t *labels, uint32_t n_labels,
+                    double *out);
+
+/* learning.dbscan (scripts/learning.py:149-163, scikit-learn DBSCAN(eps, min_samples).fit(X)): labels[n] (-1 = noise),
+ * core[n] (1 = core sample; may be NULL), *n_clusters (may be NULL).  j is a neighbour of i iff the float64
+ * direct-difference distance is <= eps (i itself included); core iff at least min_samples neighbours; clusters = the
+ * connected components of the core points, numbered by their smallest row; a border point takes the smallest label among
+ * its core neighbours.  Host pointers.  PHK_ERR_ARG for eps not finite and > 0 or min_samples < 1; PHK_ERR_NAN for NaN rows. */
+int phk_dbscan(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, double eps, uint64_t min_samples, int64_t *labels,
+               uint8_t *core, uint64_t *n_clusters);
+
 /* learning.distances (scripts/learning.py:47-56; with np.argmin on its result: learning.closest_to :59-66): the
  * Euclidean distances of every row of Q[N][D] to every row of X[M][D], out[N][M], float64, in the reference's
  * direct-difference form sqrt(sum_d (q_d - x_d)^2).  Host pointers. */

@@ -87,6 +87,8 @@ SIGNATURES = {
     "phk_kde_log_density": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_double, c_void_p]),
     "phk_score": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p]),
     "phk_distances": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p]),
+    "phk_silhouettes": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_void_p]),
+    "phk_dbscan": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_double, c_u64, c_void_p, c_void_p, P(c_u64)]),
     "phk_pack_ascii_dev": (c_int, [c_void_p, c_void_p, c_u64, c_char_p, c_void_p, c_void_p, c_void_p]),
     "phk_count_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_int,
                               c_void_p, c_void_p]),
@@ -343,6 +345,31 @@ def kde_log_density(ctx, Q, X, h):
     out = np.empty(Q.shape[0], dtype=np.float64)
     check(ctx.lib.phk_kde_log_density(ctx.handle, ptr(Q), Q.shape[0], ptr(X), X.shape[0], X.shape[1], h, ptr(out)))
     return out
+
+
+def silhouettes(ctx, X, labels, n_labels):
+    """scikit-learn silhouette_samples(X, labels) on the device (phk_silhouettes): ``labels`` already encoded
+    0..n_labels-1; (n,) float64."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    lab = np.ascontiguousarray(labels, dtype=np.uint32)
+    if X.ndim != 2 or lab.shape != (X.shape[0],):
+        raise ValueError("X must be 2-D with one label per row")
+    out = np.empty(X.shape[0], dtype=np.float64)
+    check(ctx.lib.phk_silhouettes(ctx.handle, ptr(X), X.shape[0], X.shape[1], ptr(lab), int(n_labels), ptr(out)))
+    return out
+
+
+def dbscan(ctx, X, eps, min_samples):
+    """DBSCAN(eps, min_samples).fit(X) on the device (phk_dbscan): (labels int64 (-1 = noise), core mask bool, n_clusters)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be 2-D")
+    labels = np.empty(X.shape[0], dtype=np.int64)
+    core = np.empty(X.shape[0], dtype=np.uint8)
+    k = c_u64()
+    check(ctx.lib.phk_dbscan(ctx.handle, ptr(X), X.shape[0], X.shape[1], float(eps), int(min_samples), ptr(labels), ptr(core),
+                             ctypes.byref(k)))
+    return labels, core.astype(bool), int(k.value)
 
 
 class Batch(object):

@@ -7,6 +7,12 @@ learning.py -- drop-in for the hot-path helpers of PhaMers' scripts/learning.py.
     kmeans(data, k, ...)                          scripts/learning.py:131-146   -> scikit-learn's seeding on the host + its Lloyd sweeps on the GPU
     get_centroids(data, assignment)               scripts/learning.py:69-81     -> NumPy (86 means)
     get_density(point, data, bandwidth=0.1)       scripts/learning.py:107-115   -> GPU (float64 Gaussian KDE, log_density batched)
+    dbscan(data, eps, min_samples, ...)           scripts/learning.py:149-163   -> GPU (neighbour counts + lock-free union-find)
+    silhouettes(data, assignment)                 scripts/learning.py:84-92     -> GPU (float64 cluster distance sums)
+    cluster_silhouettes(data, assignment, c)      scripts/learning.py:95-104    -> GPU silhouettes of one cluster's members
+    silhouette_score(data, labels)                (sklearn.metrics name)        -> mean of the GPU silhouettes
+    cluster_deviations(data, assignment)          scripts/learning.py:31-44     -> NumPy (O(n D))
+    sort_assignment_by_size(assignment, ...)      scripts/learning.py:166-182   -> NumPy
 
 k-means reproduces the reference's scikit-learn fit (a per-run fit that does not depend on the number of
 query contigs; the golden scores are pinned to its centroids): the k-means++
@@ -187,20 +193,20 @@ def kmeans(data, k, verbose=False, sort_by_size=False, _ctx=None):
     the version-independent device k-means (kmeans_gpu: other seeds, other centroids)."""
     import os
     mode = os.environ.get("PHAMERS_KMEANS", "device")
-    if sort_by_size:
-        raise NotImplementedError("sort_by_size is outside the accelerated path")
+    assignment = None
     if mode == "gpu":
-        return kmeans_gpu(data, k)[0]
-    if mode != "sklearn":
+        assignment = kmeans_gpu(data, k)[0]
+    elif mode != "sklearn":
         got = kmeans_reference_on_device(data, k, ctx=_ctx)   # (_ctx: a context of the caller's own -- a helper thread's)
         if got is not None:
-            return got[0]
-    from sklearn.cluster import KMeans
-    assignment = KMeans(n_clusters=k, random_state=kmeans_seed).fit(data).labels_
-    if type(assignment) != np.ndarray:
-        assignment = np.array(assignment)
+            assignment = got[0]
+    if assignment is None:
+        from sklearn.cluster import KMeans
+        assignment = KMeans(n_clusters=k, random_state=kmeans_seed).fit(data).labels_
+        if type(assignment) != np.ndarray:
+            assignment = np.array(assignment)
     if sort_by_size:
-        raise NotImplementedError("sort_by_size is outside the accelerated path")
+        assignment = sort_assignment_by_size(assignment, ascending=False)   # scripts/learning.py:144-145
     return assignment
 
 
@@ -227,3 +233,100 @@ def get_density(point, data, bandwidth=0.1):
     """Density of ``data`` at one point (scripts/learning.py:107-115): the scalar log-likelihood that
     KernelDensity(kernel='gaussian', bandwidth=bandwidth).fit(data).score_samples([point])[0] returns."""
     return float(log_density(np.asarray(point, dtype=np.float64).reshape(1, -1), data, bandwidth)[0])
+
+
+def _check_rows(data):
+    """float64 C-contiguous 2-D rows; the ValueError scikit-learn raises for NaN / infinite input."""
+    X = np.ascontiguousarray(data, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("Expected 2D array, got %dD array instead" % X.ndim)
+    if np.isnan(X).any():
+        raise ValueError("Input contains NaN.")
+    if not np.isfinite(X).all():
+        raise ValueError("Input contains infinity or a value too large for dtype('float64').")
+    return X
+
+
+def dbscan(data, eps, min_samples, sort_by_size=False):
+    """DBSCAN labels (scripts/learning.py:149-163): what ``DBSCAN(eps=eps, min_samples=min_samples).fit(data).labels_``
+    returns, -1 = noise, computed on the device (phk_dbscan: neighbours by float64 direct differences, d <= eps).  With
+    ``sort_by_size`` the clusters are relabelled largest first, as the reference does."""
+    labels = dbscan_fit(data, eps, min_samples)[0]
+    num_clusters = len(set(labels.tolist()) - set([-1]))
+    pct_unassigned = 100.0 * np.sum(labels == -1) / float(len(labels)) if len(labels) else 0.0
+    logger.debug('%d clusters, %.1f%% unassigned' % (num_clusters, pct_unassigned))
+    if sort_by_size:
+        labels = sort_assignment_by_size(labels, ascending=False)
+    return labels
+
+
+def dbscan_fit(data, eps, min_samples):
+    """(labels_, core_sample_indices_) of ``DBSCAN(eps=eps, min_samples=min_samples).fit(data)``."""
+    eps = float(eps)
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise ValueError("The 'eps' parameter of DBSCAN must be a float in the range (0.0, inf). Got %r instead." % (eps,))
+    if isinstance(min_samples, (bool, np.bool_)) or not isinstance(min_samples, (int, np.integer)) or min_samples < 1:
+        raise ValueError("The 'min_samples' parameter of DBSCAN must be an int in the range [1, inf). Got %r instead."
+                         % (min_samples,))
+    X = _check_rows(data)
+    if X.shape[0] == 0:
+        raise ValueError("Found array with 0 sample(s) (shape=%s) while a minimum of 1 is required." % (X.shape,))
+    labels, core, _ = _lib.dbscan(_lib.get_context(), X, eps, int(min_samples))
+    return labels, np.flatnonzero(core)
+
+
+def silhouettes(data, assignment):
+    """Silhouette value of every row (scripts/learning.py:84-92): what ``silhouette_samples(data, assignment)`` returns.
+    Labels of any type are encoded in np.unique order (scikit-learn's LabelEncoder); -1 is an ordinary cluster here.
+    Computed on the device (phk_silhouettes), float64, bit-identical from run to run."""
+    X = _check_rows(data)
+    assignment = np.asarray(assignment)
+    if assignment.shape != (X.shape[0],):
+        raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]"
+                         % (X.shape[0], assignment.shape[0] if assignment.ndim else 1))
+    _, codes = np.unique(assignment, return_inverse=True)
+    codes = codes.ravel()
+    n_labels = int(codes.max()) + 1 if codes.size else 0
+    if not 2 <= n_labels <= X.shape[0] - 1:
+        raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % n_labels)
+    return _lib.silhouettes(_lib.get_context(), X, codes, n_labels)
+
+
+def cluster_silhouettes(data, assignment, cluster):
+    """Silhouettes of the members of one cluster, in row order (scripts/learning.py:95-104)."""
+    ss = silhouettes(data, assignment)
+    return np.array([ss[i] for i in range(len(assignment)) if assignment[i] == cluster])
+
+
+def silhouette_score(data, labels):
+    """Mean silhouette (sklearn.metrics.silhouette_score with its defaults, as scripts/cluster.py:43 calls it)."""
+    return float(np.mean(silhouettes(data, labels)))
+
+
+def cluster_deviations(data, assignment):
+    """Mean distance of each cluster's members to its centroid (scripts/learning.py:31-44), replicated as written: the
+    clusters are taken to be labelled 0..K-1 (K = the number of labels other than -1)."""
+    data = np.asarray(data)
+    num_clusters = len(set(assignment) - set([-1]))
+    centroids = get_centroids(data, assignment)
+    deviations = np.zeros(num_clusters)
+    for cluster in range(num_clusters):
+        which = [i for i in range(data.shape[0]) if assignment[i] == cluster]
+        vector = centroids[cluster]
+        if len(vector.shape) == 1:
+            vector = np.array([vector])
+        deviations[cluster] = np.mean(np.linalg.norm(np.repeat(vector, data[which].shape[0], axis=0) - data[which], axis=1))
+    return deviations
+
+
+def sort_assignment_by_size(assignment, ascending=True):
+    """Clusters relabelled by size (scripts/learning.py:166-182): 0 = the smallest when ``ascending``, the largest
+    otherwise; ties in the order of ``sorted(zip(sizes, clusters))`` (reversed when not ascending); -1 stays -1."""
+    assignment = np.asarray(assignment)
+    cluster_set = list(set(assignment.tolist()) - set([-1]))
+    cluster_sizes = [np.sum(assignment == cluster) for cluster in cluster_set]
+    sorted_assignment = [cluster for (size, cluster) in sorted(zip(cluster_sizes, cluster_set))[::[-1, 1][ascending]]]
+    new_assignment = np.ones(len(assignment), dtype=int) * -1
+    for new, cluster in enumerate(sorted_assignment):
+        new_assignment[assignment == cluster] = new
+    return new_assignment
