@@ -63,6 +63,7 @@ extern "C" {
 #define PHK_METHOD_KMEANS 2      /* scripts/phamer.py:240-256 (centroids supplied) */
 #define PHK_METHOD_COMBO 3       /* scripts/phamer.py:303-313 */
 #define PHK_METHOD_DENSITY 4     /* scripts/phamer.py:275-287; exclusive: not to be OR-ed with the others */
+#define PHK_METHOD_SVM 5         /* scripts/phamer.py:258-266; exclusive, needs phk_model_fit_svm first */
 
 typedef struct phk_ctx phk_ctx;
 typedef struct phk_model phk_model;
@@ -268,6 +269,12 @@ int phk_model_set_column_mask(phk_ctx *ctx, phk_model *model, const uint8_t *mas
  * Gaussian kernel widths of the positive and the negative class.  A model starts with the reference's 0.005 / 0.01.  Each must
  * be finite and > 0, else PHK_ERR_ARG (model unchanged). */
 int phk_model_set_bandwidths(phk_ctx *ctx, phk_model *model, double h_pos, double h_neg);
+/* Fits the svm method (phamer_scorer.svm_score_points, scripts/phamer.py:258-266: NuSVC().fit(train, labels)) on the
+ * model's train rows that the column mask leaves in: Nu-SVC with an RBF kernel of width gamma (> 0; scikit-learn's 'scale'
+ * is 1 / (D var(X)) over those rows, computed by the caller), nu in (0, 1], stopping tolerance tol -- see phk_nusvc_fit.
+ * The support vectors are copied into the model; a later mask does not change them.  PHK_ERR_ARG for an infeasible nu, a
+ * class without rows or a bad argument (the previous fit is then kept). */
+int phk_model_fit_svm(phk_ctx *ctx, phk_model *model, double nu, double gamma, double tol);
 
 /* Deterministic device k-means (opt-in alternative to the scikit-learn fit of scripts/learning.py:131-146,
  * whose centroids depend on the scikit-learn version): k-means++ seeding driven by splitmix64(seed + j),
@@ -294,7 +301,7 @@ int phk_kmeans_lloyd(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, uint
 
 /* ---- host API: scoring ------------------------------------------------------------- */
 /* phamer.score_points / phamer_scorer.score_points (scripts/phamer.py:451-468, 177-195) for
- * method in {knn, kmeans, combo, density}: Q[N][D] float64 host rows -> scores[N] float64.
+ * method in {knn, kmeans, combo, density, svm}: Q[N][D] float64 host rows -> scores[N] float64.
  *   knn    : 2*(majority label of the kn nearest train rows) - 1   (scripts/learning.py:118-128)
  *   kmeans : tanh((e- - e+)/(e+ + e-)), e+/- = distance to the nearest positive / negative
  *            centroid (scripts/phamer.py:198-210, 250-256; scripts/learning.py:47-66)
@@ -303,10 +310,32 @@ int phk_kmeans_lloyd(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, uint
  *            bandwidth h+ / h- (phk_model_set_bandwidths): phamer_scorer.density_score_points (scripts/phamer.py:275-287),
  *            learning.get_density (scripts/learning.py:107-115).  float64 throughout; the result of a query does not depend
  *            on N, on the batch it came in or on the entry point.  PHK_ERR_ARG when a class has no unmasked row.
+ *   svm    : 1.0 where libsvm's decision value sum_sv coef_sv exp(-gamma |q - x_sv|^2) - rho is <= 0, else 0.0: the
+ *            predict of the NuSVC fitted by phk_model_fit_svm (scripts/phamer.py:258-266).  float64; the result of a query
+ *            does not depend on N, the batch or the entry point.  PHK_ERR_ARG before a fit.
  * Returns PHK_ERR_NAN (scores untouched) if any query element is NaN -- the reference's
  * scikit-learn call raises on such input. */
 int phk_score(phk_ctx *ctx, const phk_model *model, const double *Q, uint64_t N, int method,
               double *scores);
+
+/* scikit-learn NuSVC(nu, kernel='rbf', gamma, tol, shrinking=False, max_iter).fit(X, labels) for labels in {0, 1}
+ * (phamer_scorer.svm_score_points, scripts/phamer.py:258-266), as scikit-learn's libsvm fork solves it (svm.cpp
+ * solve_nu_svc, Solver_NU; shrinking does not change the solution): the kernel matrix on the device, rounded to float32 as
+ * libsvm's Qfloat, the solver in one workgroup.  X[n][D], labels[n] host arrays; gamma > 0 (scikit-learn's 'scale' /
+ * 'auto' are computed by the caller); max_iter -1 = unlimited.  Out (host, capacity n): support[n_sv] = the rows of X that
+ * are support vectors, in libsvm's order (label-0 rows first); dual_coef[n_sv] = libsvm's coefficients alpha_i y_i / r
+ * with y = +1 for label 0 (scikit-learn's binary dual_coef_ is their negation); *rho = libsvm's rho (scikit-learn's binary
+ * intercept_); *n_iter = solver iterations.  PHK_ERR_ARG for labels outside {0, 1}, a single class, an infeasible nu
+ * (svm_check_parameter, svm.cpp:3129: nu (n0 + n1) / 2 > min(n0, n1)), nu outside (0, 1], or more than 65536 rows. */
+int phk_nusvc_fit(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const double *labels, double nu, double gamma,
+                  double tol, int32_t max_iter, int32_t *support, double *dual_coef, double *rho, int32_t *n_sv,
+                  int32_t *n_iter);
+/* libsvm's decision values (svm_predict_values, k_function of svm.cpp:452) of Q[N][D] under support vectors SV[n_sv][D]
+ * with libsvm's coefficients and rho: dec[q] = sum_sv dual_coef_sv exp(-gamma |Q[q] - SV_sv|^2) - rho, float64, on the
+ * MFMA Gram tile; the value of a query does not depend on N.  Host pointers.  scikit-learn's binary decision_function is
+ * -dec; its predict is 1 (classes_[1]) where dec <= 0. */
+int phk_nusvc_decision(phk_ctx *ctx, const double *SV, uint64_t n_sv, uint64_t D, const double *dual_coef, double rho,
+                       double gamma, const double *Q, uint64_t N, double *dec);
 
 /* KernelDensity(kernel='gaussian', bandwidth=h).fit(X).score_samples(Q) (learning.get_density, scripts/learning.py:107-115):
  * out[q] = logsumexp_j(-|Q[q] - X[j]|^2 / (2 h^2)) - log(M) - (D/2) log(2 pi) - D log(h), float64, the density method's

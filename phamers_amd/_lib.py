@@ -15,8 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libphamers_hip.so")
 
 PHK_OK = 0
 PHK_ERR_ARG, PHK_ERR_HIP, PHK_ERR_NOMEM, PHK_ERR_UNSUPPORTED, PHK_ERR_NAN, PHK_ERR_IO = -1, -2, -3, -4, -5, -6
-METHOD_KNN, METHOD_KMEANS, METHOD_COMBO, METHOD_DENSITY = 1, 2, 3, 4
-METHODS = {"knn": METHOD_KNN, "kmeans": METHOD_KMEANS, "combo": METHOD_COMBO, "density": METHOD_DENSITY}
+METHOD_KNN, METHOD_KMEANS, METHOD_COMBO, METHOD_DENSITY, METHOD_SVM = 1, 2, 3, 4, 5
+METHODS = {"knn": METHOD_KNN, "kmeans": METHOD_KMEANS, "combo": METHOD_COMBO, "density": METHOD_DENSITY, "svm": METHOD_SVM}
 MAX_K = 7
 ABI_VERSION = 2
 
@@ -85,6 +85,11 @@ SIGNATURES = {
     "phk_model_set_column_mask": (c_int, [c_void_p, c_void_p, c_void_p]),
     "phk_model_set_bandwidths": (c_int, [c_void_p, c_void_p, c_double, c_double]),
     "phk_kde_log_density": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_double, c_void_p]),
+    "phk_model_fit_svm": (c_int, [c_void_p, c_void_p, c_double, c_double, c_double]),
+    "phk_nusvc_fit": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_double, c_double, c_double, ctypes.c_int32,
+                              c_void_p, c_void_p, P(c_double), P(ctypes.c_int32), P(ctypes.c_int32)]),
+    "phk_nusvc_decision": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_double, c_double, c_void_p, c_u64,
+                                   c_void_p]),
     "phk_score": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p]),
     "phk_distances": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_silhouettes": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_void_p]),
@@ -162,6 +167,12 @@ def load():
 def check(rc):
     if rc != PHK_OK:
         raise PhkError(rc, load().phk_last_error().decode("utf-8", "replace"))
+
+
+def last_error():
+    """The message of the last failed call without its "phk_...: " prefix."""
+    msg = load().phk_last_error().decode("utf-8", "replace")
+    return msg.split(": ", 1)[1] if msg.startswith("phk_") and ": " in msg else msg
 
 
 def default_device():
@@ -280,6 +291,7 @@ class Model(object):
             if a is not None and np.isnan(a).any():
                 raise ValueError("Input contains NaN.")
         self.D = pos.shape[1]
+        self._pos, self._neg, self._mask = pos, neg, None     # (the svm method's gamma='scale' reads the unmasked rows)
         h = ctypes.c_void_p()
         check(ctx.lib.phk_model_create(ctx.handle, ptr(pos), pos.shape[0], ptr(neg), neg.shape[0],
                                        ptr(cp), 0 if cp is None else cp.shape[0],
@@ -310,6 +322,21 @@ class Model(object):
         """Exclude train rows from the k-NN search (``mask``: bool over vstack(positive, negative); None lifts it)."""
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         check(self.ctx.lib.phk_model_set_column_mask(self.ctx.handle, self.handle, ptr(m)))
+        self._mask = None if m is None else m.astype(bool)
+
+    def fit_svm(self, nu=0.5, gamma='scale', tol=1e-3):
+        """Fits the svm method (phamer_scorer.svm_score_points: NuSVC().fit(train, labels), scripts/phamer.py:258-266) on
+        the train rows the column mask leaves in; 'scale' / 'auto' are scikit-learn's, over those rows in vstack order.
+        Returns gamma.  ValueError for an infeasible nu or a class without rows, as scikit-learn raises."""
+        X = np.vstack((self._pos, self._neg))
+        if self._mask is not None:
+            X = X[~self._mask]
+        g = svm_gamma(X, gamma)
+        rc = self.ctx.lib.phk_model_fit_svm(self.ctx.handle, self.handle, float(nu), g, float(tol))
+        if rc == PHK_ERR_ARG:
+            raise ValueError(last_error())
+        check(rc)
+        return g
 
     def set_bandwidths(self, h_pos, h_neg):
         """Gaussian kernel widths of the density method per class (phamer_scorer.positive_bandwidth / negative_bandwidth;
@@ -370,6 +397,51 @@ def dbscan(ctx, X, eps, min_samples):
     check(ctx.lib.phk_dbscan(ctx.handle, ptr(X), X.shape[0], X.shape[1], float(eps), int(min_samples), ptr(labels), ptr(core),
                              ctypes.byref(k)))
     return labels, core.astype(bool), int(k.value)
+
+
+def svm_gamma(X, gamma):
+    """scikit-learn's _gamma (sklearn/svm/_base.py): 'scale' = 1 / (D * X.var()) (1.0 when the variance is 0), 'auto' =
+    1 / D, else the number itself."""
+    if isinstance(gamma, str):
+        if gamma == 'scale':
+            X_var = X.var()
+            return 1.0 / (X.shape[1] * X_var) if X_var != 0 else 1.0
+        if gamma == 'auto':
+            return 1.0 / X.shape[1]
+        raise ValueError("gamma must be 'scale', 'auto' or a float, got %r" % (gamma,))
+    g = float(gamma)
+    if not (np.isfinite(g) and g > 0):
+        raise ValueError("gamma must be finite and > 0, got %r" % (gamma,))
+    return g
+
+
+def nusvc_fit(ctx, X, labels, nu, gamma, tol, max_iter=-1):
+    """phk_nusvc_fit: (support, libsvm dual coefficients, libsvm rho, n_iter) for labels in {0, 1} and gamma > 0.
+    ValueError (libsvm's message) for an infeasible nu, a single class or other bad arguments."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    y = np.ascontiguousarray(labels, dtype=np.float64)
+    n = X.shape[0]
+    support = np.empty(n, dtype=np.int32)
+    coef = np.empty(n, dtype=np.float64)
+    rho, n_sv, n_iter = c_double(), ctypes.c_int32(), ctypes.c_int32()
+    rc = ctx.lib.phk_nusvc_fit(ctx.handle, ptr(X), n, X.shape[1], ptr(y), float(nu), float(gamma), float(tol), int(max_iter),
+                               ptr(support), ptr(coef), ctypes.byref(rho), ctypes.byref(n_sv), ctypes.byref(n_iter))
+    if rc == PHK_ERR_ARG:
+        raise ValueError(last_error())
+    check(rc)
+    k = n_sv.value
+    return support[:k].copy(), coef[:k].copy(), rho.value, n_iter.value
+
+
+def nusvc_decision(ctx, SV, coef, rho, gamma, Q):
+    """phk_nusvc_decision: libsvm's decision values (N,) float64 of the rows Q."""
+    SV = np.ascontiguousarray(SV, dtype=np.float64)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    out = np.empty(Q.shape[0], dtype=np.float64)
+    check(ctx.lib.phk_nusvc_decision(ctx.handle, ptr(SV), SV.shape[0], SV.shape[1], ptr(coef), float(rho), float(gamma),
+                                     ptr(Q), Q.shape[0], ptr(out)))
+    return out
 
 
 class Batch(object):

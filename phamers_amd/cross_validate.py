@@ -11,7 +11,9 @@ fold is then
     * the fold's centroids, written into the model's centroid segments (k-means on the fold's train rows: scikit-learn
       by default, as the reference; ``kmeans='gpu'`` selects the deterministic device k-means per fold; kmeans and
       combo only),
+    * for the svm method, a NuSVC fit on the rows the mask leaves in (phk_model_fit_svm),
     * one scoring call for the held-out rows.
+The dbscan method runs through the reference's per-fold calls of phamer.score_points.
 Scores are those of a model built from the fold's train rows alone (the k-NN search is translation invariant: only
 the error bounds depend on the centring vector, and they are evaluated for the one in use);
 tests/golden/cross_validation.npz holds what the reference's own cross_validate produced.
@@ -75,7 +77,7 @@ class cross_validator(object):
         self.num_positive, self.num_negative = self.positive_data.shape[0], self.negative_data.shape[0]
         plan = FoldPlan(self.num_positive, self.num_negative, self.N, self.seed)
         self.positive_assignment, self.negative_assignment = plan.positive, plan.negative
-        resident = self.scoring_function is phamer.score_points and (self.method or 'combo') in ('knn', 'kmeans', 'combo', 'density')
+        resident = self.scoring_function is phamer.score_points and (self.method or 'combo') in ('knn', 'kmeans', 'combo', 'density', 'svm')
         runner = self._folds_on_resident_model if resident else self._folds_through_scoring_function
         self.positive_scores, self.negative_scores = runner(plan)
         logger.info("%d-fold cross validation complete." % self.N)
@@ -128,6 +130,8 @@ class cross_validator(object):
                 elif with_centroids:
                     model.set_centroids(*cents)
                 model.set_column_mask(np.concatenate((out_p, out_n)))
+                if method == 'svm':
+                    model.fit_svm()    # on the fold's train rows (the mask's complement), gamma over those rows
                 scores = model.score(np.vstack((P[out_p], Nm[out_n])), method)
                 n_p = int(out_p.sum())
                 pos_scores[out_p], neg_scores[out_n] = scores[:n_p], scores[n_p:]
@@ -138,11 +142,17 @@ class cross_validator(object):
 
     # ---- generic: any scoring function, the reference's per-fold calls ---------------------------------------
     def _folds_through_scoring_function(self, plan):
+        # (phamer.score_points serves knn / kmeans / combo / density only; the reference's call of it for the other methods
+        # is score_with_scorer -- the same scorer, the same matrices)
+        fn = phamer.score_with_scorer if self.scoring_function is phamer.score_points else self.scoring_function
         pos_scores, neg_scores = np.zeros(self.num_positive), np.zeros(self.num_negative)
         for fold in range(plan.folds):
             out_p, out_n = plan.held_out(fold)
-            scores = self.scoring_function(np.vstack((self.positive_data[out_p], self.negative_data[out_n])),
+            scores = fn(np.vstack((self.positive_data[out_p], self.negative_data[out_n])),
                                            self.positive_data[~out_p], self.negative_data[~out_n], method=self.method)
+            scores = np.asarray(scores)
+            if scores.ndim == 2 and scores.shape[1] == 1:
+                scores = scores[:, 0]    # the dbscan method's (n, 1) scores (the NumPy of the reference's era took them)
             n_p = int(out_p.sum())
             pos_scores[out_p], neg_scores[out_n] = scores[:n_p], scores[n_p:]
         return pos_scores, neg_scores

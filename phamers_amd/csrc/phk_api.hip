@@ -554,7 +554,7 @@ extern "C" int phk_count_score_dev(phk_ctx *ctx, const phk_model *model, const u
     // next batch's sweep inside phk_score_fast.)
     // k = 5: the count kernel's flush also writes the int8 operand of the scorer's sweep (PhkPrep8, phk_common.h)
     ctx->prep8.armed = false;
-    if (k == 5 && method != PHK_METHOD_DENSITY && !d_mask && n > 0 && phk_model_has_fast(model) && model->d_A8 && !model->bf_stale && !ctx->knobs.force_exact &&
+    if (k == 5 && method != PHK_METHOD_DENSITY && method != PHK_METHOD_SVM && !d_mask && n > 0 && phk_model_has_fast(model) && model->d_A8 && !model->bf_stale && !ctx->knobs.force_exact &&
         !ctx->knobs.proposal[0] && !ctx->knobs.count_lanes) {
         const uint64_t D = model->D;
         void *frag, *big;

@@ -227,6 +227,7 @@ extern "C" int phk_model_destroy(phk_ctx *ctx, phk_model *m) {
     if (m->d_labels) (void)hipFree(m->d_labels);
     if (m->d_C64) (void)hipFree(m->d_C64);
     if (m->d_rn) (void)hipFree(m->d_rn);
+    phk_model_free_svm(m);
     phk_model_free_fast(m);
     delete m;
     return PHK_OK;
@@ -304,9 +305,9 @@ extern "C" int phk_distances(phk_ctx *ctx, const double *Q, uint64_t N, const do
 
 static int check_method(const phk_model *m, int method) {
     PHK_REQUIRE(method == PHK_METHOD_KNN || method == PHK_METHOD_KMEANS || method == PHK_METHOD_COMBO ||
-                    method == PHK_METHOD_DENSITY,
+                    method == PHK_METHOD_DENSITY || method == PHK_METHOD_SVM,
                 "phk_score: unknown method %d", method);
-    PHK_REQUIRE(!(method & PHK_METHOD_KMEANS) || m->n_cpos > 0,
+    PHK_REQUIRE(method == PHK_METHOD_SVM || !(method & PHK_METHOD_KMEANS) || m->n_cpos > 0,
                 "phk_score: method needs centroids but the model was created without them");
     return PHK_OK;
 }
@@ -332,6 +333,12 @@ int phk_score_rows(phk_ctx *ctx, const phk_model *m, const double *d_Q, const ui
         ctx->last_score_fast = false;
         ctx->score_totals_zeroed = false;
         return phk_score_density(ctx, m, d_Q, d_counts, N, d_scores, d_status);
+    }
+    // svm (svm.hip): the fitted model's dense float64 decision, likewise
+    if (method == PHK_METHOD_SVM) {
+        ctx->last_score_fast = false;
+        ctx->score_totals_zeroed = false;
+        return phk_score_svm(ctx, m, d_Q, d_counts, N, d_scores, d_status);
     }
 
     // PHK_FORCE_EXACT=1 routes every model through the float64 path (used by the parity tests to

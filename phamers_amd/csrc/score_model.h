@@ -14,6 +14,13 @@ struct phk_model {
     double *d_rn = nullptr;
     double h_pos = 0.005, h_neg = 0.01;   // scripts/phamer.py:82-83
     uint64_t eff_pos = 0, eff_neg = 0;
+    // svm method (svm.hip): the support vectors of the last phk_model_fit_svm in libsvm's order, their |x|^2 and libsvm's
+    // coefficients (one allocation: [n_sv][D] rows, then n_sv norms, then n_sv coefficients), rho, gamma
+    double *d_sv = nullptr, *d_svn = nullptr, *d_svcoef = nullptr;
+    uint64_t n_sv = 0;
+    double svm_rho = 0.0, svm_gamma = 0.0;
+    int32_t svm_iter = 0;
+    bool svm_fitted = false;
     // MFMA path (score_mfma.hip); null when the shape is outside it
     bool fast = false;
     double *d_colnorm = nullptr;  // |r'| per real column (train rows, pos centroids, neg centroids)
@@ -81,6 +88,11 @@ int phk_score_exact_batch(phk_ctx *ctx, const phk_model *m, const double *d_Q, u
 int phk_model_build_density(phk_ctx *ctx, phk_model *m);
 int phk_score_density(phk_ctx *ctx, const phk_model *m, const double *d_Q, const uint32_t *d_counts, uint64_t N,
                       double *d_scores, uint32_t *d_status);
+
+// svm method (svm.hip)
+void phk_model_free_svm(phk_model *m);
+int phk_score_svm(phk_ctx *ctx, const phk_model *m, const double *d_Q, const uint32_t *d_counts, uint64_t N, double *d_scores,
+                  uint32_t *d_status);
 
 // MFMA path hooks (score_mfma.hip)
 int phk_model_build_fast(phk_ctx *ctx, phk_model *m, const double *pos, const double *neg,

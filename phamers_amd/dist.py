@@ -211,9 +211,11 @@ def default_scorer(device_index=None):
             return np.zeros(0)
         ctx = _lib.get_context(device_index)
         batch = _lib.Batch.from_sequences(ctx, list(sequences), kmer_length)
-        cen = method in ("kmeans", "combo")     # (density and knn need no centroids)
+        cen = method in ("kmeans", "combo")     # (density, svm and knn need no centroids)
         model = _lib.Model(ctx, positive, negative, cpos if cen else None, cneg if cen else None, k_neighbors)
         try:
+            if method == "svm":
+                model.fit_svm()      # (deterministic: every rank fits the same model)
             return batch.score(model, method)
         finally:
             model.close()
@@ -270,10 +272,12 @@ def score_fasta_distributed(path, positive, negative, positive_centroids=None, n
         fasta.close()
     local = np.zeros(0)
     if batch is not None:
-        cen = method in ("kmeans", "combo")     # (density and knn need no centroids)
+        cen = method in ("kmeans", "combo")     # (density, svm and knn need no centroids)
         model = _lib.Model(ctx, positive, negative, positive_centroids if cen else None,
                            negative_centroids if cen else None, k_neighbors)
         try:
+            if method == "svm":
+                model.fit_svm()      # (deterministic: every rank fits the same model)
             if length_requirement:
                 keep = np.flatnonzero(lengths >= int(length_requirement))
                 ids = ids[keep]

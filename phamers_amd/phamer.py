@@ -2,7 +2,7 @@
 phamer.py -- drop-in for the scoring entry points of PhaMers' scripts/phamer.py, device resident.
 
     phamer_scorer            attribute surface + load_data / screen_by_length / equalize_reference_data /
-                             score_points / knn_ / kmeans_ / density_ / combo_score_points
+                             score_points / dbscan_ / knn_ / kmeans_ / svm_ / density_ / combo_score_points
                                                                                     scripts/phamer.py:42-313
     score_points(scoring_data, positive_training_data, negative_training_data, method=None)
                                                                                     scripts/phamer.py:451-468
@@ -17,9 +17,13 @@ assigning it (as phamer.score_points and the cross-validation do) switches the o
 scored through the float64-row entry point.
 
 The k-means fit that yields the centroids is scikit-learn's, as in the reference (learning.kmeans); the density
-method needs none (a dense float64 Gaussian kernel density per class, density.hip).  Methods outside
-{knn, kmeans, combo, density} raise NotImplementedError: dbscan / svm / silhouette are outside the accelerated path
-(SURVEY.md section 8).
+method needs none (a dense float64 Gaussian kernel density per class, density.hip).  The svm method fits scikit-learn's
+NuSVC() on the device (svm.hip) and scores 1.0 / 0.0 by its predict; dbscan clusters each class with learning.dbscan
+(k-means when that finds fewer than three clusters) and scores with the kmeans method's nearest-centroid kernels.
+The silhouette method raises NotImplementedError: the reference builds its negative side from the positive data
+(scripts/phamer.py:295), so a faithful port scores 0 for every contig after an O((N + n)^2) silhouette pass
+(SURVEY.md section 8).  The functional score_points keeps its method set (knn / kmeans / combo / density) and raises
+for the others; score_with_scorer is the same call for every method of phamer_scorer.
 """
 import argparse
 import logging
@@ -35,9 +39,10 @@ logging.basicConfig(format='[%(asctime)s][%(levelname)s][%(funcName)s] - %(messa
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.WARNING)
 
-_GPU_METHODS = ('knn', 'kmeans', 'combo', 'density')
-_OTHER_METHODS = ('dbscan', 'svm', 'silhouette')
+_GPU_METHODS = ('dbscan', 'knn', 'kmeans', 'combo', 'density', 'svm')
+_OTHER_METHODS = ('silhouette',)
 _CENTROID_METHODS = ('kmeans', 'combo')
+_FUNCTIONAL_METHODS = ('knn', 'kmeans', 'combo', 'density')   # what the functional score_points serves
 
 
 def _lone(directory, suffixes, avoid_stem_suffix=None):
@@ -77,6 +82,10 @@ class phamer_scorer(object):
         self.k_neighbors = 3
         self.positive_bandwidth = 0.005     # scripts/phamer.py:82-83 (density method)
         self.negative_bandwidth = 0.01
+        self.k_clusters_positive = 86       # scripts/phamer.py:80-89 (dbscan method: its k-means fallback, eps, min_samples)
+        self.k_clusters_negative = 20
+        self.eps = [1, 1]
+        self.min_samples = [2, 2]
         # centroids of the last kmeans / combo call (inspection, tests)
         self.positive_centroids = self.negative_centroids = None
         self.scores = None
@@ -276,8 +285,10 @@ class phamer_scorer(object):
         return self.scores
 
     def _outside_path(self):
-        raise NotImplementedError("scoring method %r is outside the accelerated path; knn / kmeans / combo / density are "
-                                  "available" % (self.scoring_method,))
+        raise NotImplementedError("scoring method %r is not available: the reference's silhouette method scores its "
+                                  "contigs against the positive data twice (scripts/phamer.py:295), i.e. 0 for every "
+                                  "contig; dbscan / kmeans / knn / svm / density / combo are available"
+                                  % (self.scoring_method,))
 
     def _centroids_of(self, pos, neg, k_clusters, deliver=None):
         """k-means labels -> the reference's per-label means, for both classes.  deliver: called from a helper thread,
@@ -345,16 +356,19 @@ class phamer_scorer(object):
         self.positive_centroids, self.negative_centroids = self._centroids_of(self.positive_data, self.negative_data,
                                                                               self.k_clusters)
 
-    def _gpu_score(self, method):
+    def _gpu_score(self, method, centroids=None):
         with_centroids = method in _CENTROID_METHODS
-        if with_centroids:
+        if with_centroids and centroids is None:
             self._fit_centroids()
+            centroids = self.positive_centroids, self.negative_centroids
         model = _lib.Model(_lib.get_context(), self.positive_data, self.negative_data,
-                           self.positive_centroids if with_centroids else None,
-                           self.negative_centroids if with_centroids else None, k_neighbors=self.k_neighbors)
+                           centroids[0] if with_centroids else None,
+                           centroids[1] if with_centroids else None, k_neighbors=self.k_neighbors)
         try:
             if method == 'density':
                 model.set_bandwidths(self.positive_bandwidth, self.negative_bandwidth)
+            elif method == 'svm':
+                model.fit_svm()                                   # NuSVC() defaults: nu 0.5, gamma 'scale', tol 1e-3
             if self._batch is not None:
                 return self._batch.score(model, method)          # resident counts; NaN rows raise ValueError
             q = np.asarray(self._rows, dtype=np.float64)
@@ -371,6 +385,29 @@ class phamer_scorer(object):
     def kmeans_score_points(self):
         """scripts/phamer.py:240-256: tanh proximity metric to the nearest centroid of each class."""
         return self._gpu_score('kmeans')
+
+    def dbscan_score_points(self):
+        """scripts/phamer.py:212-238: DBSCAN per class (eps / min_samples), k-means with k_clusters_positive /
+        k_clusters_negative for a class where DBSCAN's largest label is below 2, the clusters' means (noise excluded), then
+        the kmeans method's proximity metric to the nearest centroid of each class.  A list of one-element lists, as the
+        reference returns (score_points makes it an (n, 1) array)."""
+        pos, neg = self.positive_data, self.negative_data
+        positive_assignment = learning.dbscan(pos, self.eps[0], self.min_samples[0])
+        negative_assignment = learning.dbscan(neg, self.eps[1], self.min_samples[1])
+        if max(positive_assignment) < 2:
+            logger.warning("Clustering positive with k-means instead...")
+            positive_assignment = learning.kmeans(pos, self.k_clusters_positive)
+        if max(negative_assignment) < 2:
+            logger.warning("Clustering negative with k-means instead...")
+            negative_assignment = learning.kmeans(neg, self.k_clusters_negative)
+        centroids = (learning.get_centroids(pos, positive_assignment), learning.get_centroids(neg, negative_assignment))
+        self.positive_centroids, self.negative_centroids = centroids
+        return [[s] for s in self._gpu_score('kmeans', centroids)]
+
+    def svm_score_points(self):
+        """scripts/phamer.py:258-266: NuSVC().fit(vstack(positive, negative), labels 1 / 0).predict(points) -- the fit and
+        the prediction on the device (svm.hip), 1.0 / 0.0 per contig."""
+        return self._gpu_score('svm')
 
     def density_score_points(self):
         """scripts/phamer.py:275-287: log-density under the positive class minus that under the negative class (Gaussian
@@ -408,7 +445,19 @@ def _length_screen(data_ids, fasta_ids, lengths, length_requirement):
 
 def score_points(scoring_data, positive_training_data, negative_training_data, method=None):
     """Functional form of phamer_scorer.score_points (scripts/phamer.py:451-468), the scoring function of the
-    reference's cross-validation (scripts/cross_validate.py:95)."""
+    reference's cross-validation (scripts/cross_validate.py:95), for the methods it has always served: knn / kmeans /
+    combo / density.  The others raise NotImplementedError before any device work, as before; svm and dbscan are
+    served by phamer_scorer.score_points, by cross_validator (which routes them itself) and by score_with_scorer."""
+    method = method or phamer_scorer().scoring_method
+    if method not in _FUNCTIONAL_METHODS:
+        raise NotImplementedError("score_points(method=%r): the functional form scores %s; use phamer_scorer.score_points "
+                                  "or score_with_scorer for dbscan / svm" % (method, " / ".join(_FUNCTIONAL_METHODS)))
+    return score_with_scorer(scoring_data, positive_training_data, negative_training_data, method)
+
+
+def score_with_scorer(scoring_data, positive_training_data, negative_training_data, method=None):
+    """The body of the reference's functional score_points (scripts/phamer.py:451-468) for every method phamer_scorer
+    has: a scorer over the given matrices, then its score_points()."""
     scorer = phamer_scorer()
     scorer.scoring_method = method or scorer.scoring_method
     scorer.data_points = scoring_data
@@ -562,6 +611,8 @@ def _rank_count_and_score(fasta_file, part, kmer_length, method, positive, negat
             cen = method in _CENTROID_METHODS
             model = _lib.Model(ctx, positive, negative, cpos if cen else None, cneg if cen else None, k_neighbors=k_neighbors)
             try:
+                if method == 'svm':
+                    model.fit_svm()
                 scores = sub.score(model, method)
             finally:
                 model.close()
