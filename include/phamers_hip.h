@@ -261,7 +261,12 @@ int phk_model_destroy(phk_ctx *ctx, phk_model *model);
  * (mask[n_pos + n_neg] host bytes in vstack(pos, neg) order, non-zero = held out, excluded from the k-NN search;
  * NULL lifts the mask) plus that fold's centroids (same counts as at creation).  Scores then equal those of a model
  * built from the unmasked rows alone: the search is translation invariant, so keeping the full matrix's centring
- * vector changes nothing but the error bounds, which are evaluated for it. */
+ * vector changes nothing but the error bounds, which are evaluated for it.
+ * phk_model_set_centroids, phk_model_set_column_mask and phk_model_set_bandwidths may come in any order and any number
+ * of times (a mask replaces the previous one): every method then scores as a model built from the current unmasked rows
+ * with the current centroids and bandwidths.  A mask that leaves a class without rows is accepted (it must leave at least
+ * kn rows); the density method then returns PHK_ERR_ARG.  The svm fit is a snapshot: phk_model_fit_svm fits the rows
+ * unmasked at the time of the call, and a later mask or centroid change leaves it as it is until the next fit. */
 int phk_model_set_centroids(phk_ctx *ctx, phk_model *model, const double *cpos, uint64_t n_cpos, const double *cneg,
                             uint64_t n_cneg);
 int phk_model_set_column_mask(phk_ctx *ctx, phk_model *model, const uint8_t *mask);

@@ -319,8 +319,8 @@ int phk_model_update_centroids_f16(phk_model *m, const double *cpos, const doubl
     if (hi_only) {
         if (m->d_Af16h) {
             // the centroid blocks of the host copy, then the bias pieces: of the centroid blocks alone while the model's
-            // exponent still fits the new biases, else of every block (NOTE: the train blocks then carry the biases as
-            // built -- a column mask is re-applied by the caller's next phk_model_set_column_mask / apply_mask)
+            // exponent still fits the new biases, else of every block (the train blocks then carry the biases as built:
+            // phk_model_set_centroids masks them again)
             std::vector<uint8_t> &rech = m->h_rech;
             for (uint64_t b = 0; b < nbc; ++b)
                 for (int st = 0; st < 16; ++st)

@@ -30,6 +30,29 @@ __global__ void phk_rowsum_kernel(const uint32_t *__restrict__ counts, uint64_t 
 
 bool phk_fast_supports_dim(uint64_t D);
 
+// Column mask -> the train segment's candidate lists.  A masked column carries padding terms, so its value (~ -1e30) loses
+// to every unmasked one -- but it keeps its real index, and where fewer unmasked columns than list slots reach a half-list
+// it fills the slot.  The decision stages compute exact distances for every slot whose index is < M: such a column would
+// be a candidate again (a held-out row, its own nearest neighbour).  It is turned into an empty slot, as the proposal
+// kernels write them.  (Segment 0 is the first 2 CAND N entries of a list set.)
+__global__ __launch_bounds__(256) void phk_mask_lists_kernel(float *__restrict__ cv, uint32_t *__restrict__ ci, uint64_t n,
+                                                             uint64_t M, const uint8_t *__restrict__ mask) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t c = ci[t];
+    if (c < M && mask[c]) {
+        ci[t] = 0xFFFFFFFFu;
+        cv[t] = -3.0e38f;
+    }
+}
+static int phk_mask_lists(phk_ctx *ctx, const phk_model *m, float *cv, uint32_t *ci, uint64_t N) {
+    const uint64_t n = 2ull * CAND * N;
+    if (!m->has_mask || n == 0) return PHK_OK;
+    PHK_LAUNCH(ctx, "phk_mask_lists_kernel",
+               phk_mask_lists_kernel<<<dim3((unsigned)phk_div_up(n, 256)), dim3(256), 0, ctx->stream>>>(cv, ci, n, m->M, m->d_col_mask));
+    return PHK_OK;
+}
+
 // ------------------------------------------------------------------------------------
 // model build (host): centre, round to fp32, fragment-order, upload
 // ------------------------------------------------------------------------------------
@@ -418,6 +441,7 @@ int phk_score_fast(phk_ctx *ctx, const phk_model *m, const double *d_Q, const ui
             PHK_TRY(phk_launch_proposal_f16(ctx, m, src, d_counts != nullptr, rsum, nb, nref, npos, nneg, (float *)cv,
                                             ci, cu));
         }
+        if (nref) PHK_TRY(phk_mask_lists(ctx, m, (float *)cv, ci, nb));
         const unsigned rblocks = (unsigned)phk_div_up(nb, 4);
         if (hi_only) {
             HiParams hp;
@@ -535,6 +559,7 @@ int phk_score_fast(phk_ctx *ctx, const phk_model *m, const double *d_Q, const ui
             const uint64_t cap = nb < cap2 ? nb : cap2;
             PHK_TRY(phk_launch_proposal_f16(ctx, m, src, true, rsum, cap, nref, npos, nneg, cv2, ci2, cu2, fb_list, fbc,
                                             PHK_SECOND_SPLITS, set2_bytes));
+            if (nref) PHK_TRY(phk_mask_lists(ctx, m, cv2, ci2, cap));
             RerankParams p2 = p;
             split_f16_bound(p2);
             p2.N = cap;
@@ -607,7 +632,14 @@ extern "C" int phk_model_set_centroids(phk_ctx *ctx, phk_model *m, const double 
     m->max_colnorm = mx;
     m->cen_replaced = true;
     m->bf_stale = true;
-    return phk_model_update_centroids_f16(m, cpos, cneg, cnorm.data());
+    PHK_TRY(phk_model_update_centroids_f16(m, cpos, cneg, cnorm.data()));
+    if (m->has_mask) {
+        // new centroids that move the bias exponent rewrite the bias pieces of every block, the train blocks' from the
+        // unmasked host copy: mask them again, so the order of set_centroids and set_column_mask does not matter
+        PHK_TRY(phk_model_apply_mask_f16(ctx, m));
+        PHK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return PHK_OK;
 }
 
 extern "C" int phk_model_set_column_mask(phk_ctx *ctx, phk_model *m, const uint8_t *mask) {
