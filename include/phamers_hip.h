@@ -278,7 +278,7 @@ int phk_model_set_bandwidths(phk_ctx *ctx, phk_model *model, double h_pos, doubl
  * model's train rows that the column mask leaves in: Nu-SVC with an RBF kernel of width gamma (> 0; scikit-learn's 'scale'
  * is 1 / (D var(X)) over those rows, computed by the caller), nu in (0, 1], stopping tolerance tol -- see phk_nusvc_fit.
  * The support vectors are copied into the model; a later mask does not change them.  PHK_ERR_ARG for an infeasible nu, a
- * class without rows or a bad argument (the previous fit is then kept). */
+ * class without rows, a bad argument or a fit whose coefficients are not finite (the previous fit is then kept). */
 int phk_model_fit_svm(phk_ctx *ctx, phk_model *model, double nu, double gamma, double tol);
 
 /* Deterministic device k-means (opt-in alternative to the scikit-learn fit of scripts/learning.py:131-146,
@@ -331,7 +331,8 @@ int phk_score(phk_ctx *ctx, const phk_model *model, const double *Q, uint64_t N,
  * are support vectors, in libsvm's order (label-0 rows first); dual_coef[n_sv] = libsvm's coefficients alpha_i y_i / r
  * with y = +1 for label 0 (scikit-learn's binary dual_coef_ is their negation); *rho = libsvm's rho (scikit-learn's binary
  * intercept_); *n_iter = solver iterations.  PHK_ERR_ARG for labels outside {0, 1}, a single class, an infeasible nu
- * (svm_check_parameter, svm.cpp:3129: nu (n0 + n1) / 2 > min(n0, n1)), nu outside (0, 1], or more than 65536 rows. */
+ * (svm_check_parameter, svm.cpp:3129: nu (n0 + n1) / 2 > min(n0, n1)), nu outside (0, 1], more than 65536 rows, or
+ * support-vector coefficients or rho that are not finite (r = 0; scikit-learn's fit raises there too). */
 int phk_nusvc_fit(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const double *labels, double nu, double gamma,
                   double tol, int32_t max_iter, int32_t *support, double *dual_coef, double *rho, int32_t *n_sv,
                   int32_t *n_iter);

@@ -521,6 +521,12 @@ static int svm_fit_grouped(phk_ctx *ctx, const double *d_Xg, uint64_t n0, uint64
     coef.assign(n, 0.0);
     for (uint64_t i = 0; i < n; ++i) coef[i] = a[i] * ((double)y[i] / c.r);
     *rho = c.rho / c.r;
+    // scikit-learn refuses a fit whose support-vector coefficients or intercept are not finite (sklearn/svm/_base.py, fit):
+    // r = 0, e.g. two identical rows with opposite labels and nothing else
+    bool finite = std::isfinite(*rho);
+    for (uint64_t i = 0; i < n; ++i) finite = finite && (a[i] == 0.0 || std::isfinite(coef[i]));
+    PHK_REQUIRE(finite, "phk_nusvc_fit: The dual coefficients or intercepts are not finite. The input data may contain large "
+                        "values and need to be preprocessed.");
     *n_iter = c.iter;
     return PHK_OK;
 }
@@ -663,7 +669,6 @@ extern "C" int phk_model_fit_svm(phk_ctx *ctx, phk_model *m, double nu, double g
         if (!mask[r]) idx.push_back((uint32_t)r);
     const uint64_t n = idx.size(), D = m->D;
     PHK_TRY(svm_check(n0, n - n0, nu, gamma, tol));
-    phk_model_free_svm(m);
     void *d_xg, *d_idx;
     PHK_TRY(phk_ws(ctx, WS_SUB, n * D * sizeof(double), &d_xg));
     PHK_TRY(phk_ws(ctx, WS_OFFSETS, n * sizeof(uint32_t), &d_idx));
@@ -685,6 +690,7 @@ extern "C" int phk_model_fit_svm(phk_ctx *ctx, phk_model *m, double nu, double g
         }
     const uint64_t ns = sv.size();
     PHK_REQUIRE(ns > 0, "phk_model_fit_svm: no support vectors");
+    phk_model_free_svm(m);   // (a refused fit keeps the previous one)
     PHK_HIP(hipMalloc((void **)&m->d_sv, ns * D * sizeof(double) + 2 * ns * sizeof(double)));
     m->d_svn = m->d_sv + ns * D;
     m->d_svcoef = m->d_svn + ns;

@@ -1,7 +1,9 @@
 """
 svm.py -- drop-in for the part of scikit-learn's ``svm`` module that PhaMers uses (scripts/phamer.py:258-266,
 ``from sklearn import svm``; ``svm.NuSVC()``): a binary Nu-SVC with an RBF kernel, fitted and evaluated on the GPU
-(svm.cpp of scikit-learn's libsvm fork restated in svm.hip, without shrinking).
+(svm.cpp of scikit-learn's libsvm fork restated in svm.hip, without shrinking: it equals NuSVC(shrinking=False).
+scikit-learn's default NuSVC() shrinks; that gives the same fit on the reference's data, but not on every input --
+DESIGN.md section 4.7).
 
     NuSVC(nu=0.5, gamma='scale', tol=1e-3)      fit / predict / decision_function,
                                                 support_, support_vectors_, dual_coef_, intercept_, n_iter_, classes_
@@ -25,7 +27,7 @@ class NuSVC(object):
         if probability:
             raise NotImplementedError("NuSVC: probability=True is not supported")
         self.nu, self.kernel, self.gamma, self.tol = nu, kernel, gamma, tol
-        self.shrinking = shrinking      # (accepted; the solution does not depend on it)
+        self.shrinking = shrinking      # (accepted and ignored: the device solver never shrinks; see the module docstring)
         self.probability, self.max_iter = probability, max_iter
 
     def fit(self, X, y, sample_weight=None):

@@ -69,6 +69,66 @@ def dbscan(X, eps, min_samples):
     return labels, core
 
 
+def dbscan_cells(X, eps, min_samples):
+    """dbscan() for D <= 3 at any size: rows hashed into cells of side eps, neighbours searched in the 3^D cells around a
+    row's own; the same float64 direct-difference test d(i, j) <= eps and the same labelling rules.  (labels, core)."""
+    X = np.asarray(X, dtype=np.float64)
+    n, D = X.shape
+    assert D <= 3
+    cell = np.floor(X / eps).astype(np.int64)
+    cell -= cell.min(axis=0) - 1
+    span = cell.max(axis=0) + 2
+    key = np.zeros(n, dtype=np.int64)
+    for k in range(D):
+        key = key * span[k] + cell[:, k]
+    order = np.argsort(key, kind="stable")
+    skey = key[order]
+    offsets = [0]
+    for k in range(D):
+        offsets = [o * span[k] + d for o in offsets for d in (-1, 0, 1)]
+    # candidate pairs (i, j) of neighbouring cells, all at once per offset
+    ii, jj = [], []
+    for o in offsets:
+        lo = np.searchsorted(skey, key + o, side="left")
+        hi = np.searchsorted(skey, key + o, side="right")
+        cnt = hi - lo
+        i = np.repeat(np.arange(n), cnt)
+        start = np.repeat(lo - np.cumsum(cnt) + cnt, cnt)
+        j = order[start + np.arange(cnt.sum())]
+        ii.append(i)
+        jj.append(j)
+    i, j = np.concatenate(ii), np.concatenate(jj)
+    d = np.sqrt(((X[i] - X[j]) ** 2).sum(axis=1))
+    nb = d <= eps
+    i, j = i[nb], j[nb]
+    core = np.bincount(i, minlength=n) >= min_samples
+    # components of the core graph: union-find with the smaller root kept
+    parent = np.arange(n)
+    cc = core[i] & core[j]
+    a, b = i[cc], j[cc]
+    while True:
+        ra, rb = parent[a], parent[b]
+        lo_, hi_ = np.minimum(ra, rb), np.maximum(ra, rb)
+        if (lo_ == hi_).all():
+            break
+        np.minimum.at(parent, hi_, lo_)
+        while True:                                   # pointer jumping to the roots
+            pp = parent[parent]
+            if np.array_equal(pp, parent):
+                break
+            parent = pp
+    labels = np.full(n, -1, dtype=np.int64)
+    roots = parent[core]
+    uniq = np.unique(roots)                           # a root is its component's smallest core row: row order = label order
+    labels[core] = np.searchsorted(uniq, roots)
+    bd = ~core[i] & core[j]                           # border points: the smallest label of their core neighbours
+    lab = np.full(n, np.iinfo(np.int64).max)
+    np.minimum.at(lab, i[bd], labels[j[bd]])
+    has = ~core & (lab != np.iinfo(np.int64).max)
+    labels[has] = lab[has]
+    return labels, core
+
+
 def silhouettes(X, labels):
     n = np.asarray(X).shape[0]
     return np.concatenate([silhouettes_sample(X, labels, np.arange(s, min(s + 256, n))) for s in range(0, n, 256)])

@@ -1,7 +1,8 @@
 """NumPy restatement of scikit-learn's NuSVC (RBF kernel, binary labels) for the svm scoring method (test-only).
 
-It follows scikit-learn's libsvm fork (sklearn/svm/src/libsvm/svm.cpp, scikit-learn 1.7.2) without shrinking, which
-changes neither the iterations nor the solution on the fixture cases:
+It follows scikit-learn's libsvm fork (sklearn/svm/src/libsvm/svm.cpp, scikit-learn 1.7.2) without shrinking, i.e.
+NuSVC(shrinking=False).  On the reference's data the default NuSVC() (shrinking on) takes the same iterations to the
+same solution, but not in general (tests/golden/scoring_svm_synth.npz, case "shrink"):
     svm_group_classes (:2243)      rows grouped by sorted label: label-0 rows first (y = +1), then label-1 rows (y = -1)
     solve_nu_svc (:1646)           alpha filled class by class up to nu * l / 2; final scaling by 1 / r
     SVC_Q::get_Q (:1436)           Q_ij = (float)(y_i y_j K_ij)  (typedef float Qfloat, :79); QD_ii = 1
@@ -50,8 +51,16 @@ def kernel_matrix(Xg, y, gamma):
     return Q
 
 
-def solve_nu(Q, y, nu, eps=1e-3, max_iter=-1):
-    """Solver_NU on the grouped problem with C = 1: (alpha, G, rho, r, n_iter) before the 1/r scaling."""
+def solve_nu(Q, y, nu, eps=1e-3, max_iter=-1, counters=None):
+    """Solver_NU on the grouped problem with C = 1: (alpha, G, rho, r, n_iter) before the 1/r scaling.
+
+    ``counters`` (a dict, optional) counts the TAU branches (quad_coef <= 0 replaced by TAU): "tau_j", candidates j of the
+    working-set choice that were scored with TAU; "tau_same" / "tau_opposite", updates of a pair with the same / opposite
+    y that used TAU.  (Solver_NU's pair always shares y -- i is the i candidate of j's class -- so "tau_opposite" stays
+    0; the branch is libsvm's, kept as it is.)"""
+    if counters is not None:
+        for k in ("tau_j", "tau_same", "tau_opposite"):
+            counters.setdefault(k, 0)
     l = len(y)
     pos = y == 1
     alpha = np.zeros(l)
@@ -95,11 +104,15 @@ def solve_nu(Q, y, nu, eps=1e-3, max_iter=-1):
             qc = 1.0 + 1.0 - 2.0 * Q[ip, jp]
             od = -(gd * gd) / np.where(qc > 0, qc, TAU)
             obj[jp] = np.where(gd > 0, od, np.inf)
+            if counters is not None:
+                counters["tau_j"] += int(((gd > 0) & ~(qc > 0)).sum())
         if inn != -1 and len(jn):
             gd = Gmaxn - G[jn]
             qc = 1.0 + 1.0 - 2.0 * Q[inn, jn]
             od = -(gd * gd) / np.where(qc > 0, qc, TAU)
             obj[jn] = np.where(gd > 0, od, np.inf)
+            if counters is not None:
+                counters["tau_j"] += int(((gd > 0) & ~(qc > 0)).sum())
         ok = np.isfinite(obj)
         if max(Gmaxp + Gmaxp2, Gmaxn + Gmaxn2) < eps or not ok.any():
             break
@@ -111,7 +124,10 @@ def solve_nu(Q, y, nu, eps=1e-3, max_iter=-1):
         Qij = Q[i, j]
         if y[i] != y[j]:
             qc = 1.0 + 1.0 + 2.0 * Qij
-            qc = TAU if qc <= 0 else qc
+            if qc <= 0:
+                qc = TAU
+                if counters is not None:
+                    counters["tau_opposite"] += 1
             delta = (-G[i] - G[j]) / qc
             diff = alpha[i] - alpha[j]
             alpha[i] += delta
@@ -128,7 +144,10 @@ def solve_nu(Q, y, nu, eps=1e-3, max_iter=-1):
                 alpha[j], alpha[i] = 1.0, 1.0 + diff
         else:
             qc = 1.0 + 1.0 - 2.0 * Qij
-            qc = TAU if qc <= 0 else qc
+            if qc <= 0:
+                qc = TAU
+                if counters is not None:
+                    counters["tau_same"] += 1
             delta = (G[i] - G[j]) / qc
             s = alpha[i] + alpha[j]
             alpha[i] -= delta
@@ -172,9 +191,9 @@ def calculate_rho(alpha, G, y):
 
 class Fit(object):
     """A fitted binary NuSVC in scikit-learn's terms: support_, dual_coef_ (1, n_SV), intercept_ (1,), n_iter_,
-    _gamma, plus support_vectors_."""
+    _gamma, plus support_vectors_.  ``max_iter`` as NuSVC's (-1: no limit); ``counters`` as solve_nu's."""
 
-    def __init__(self, X, labels, nu=0.5, gamma='scale', tol=1e-3):
+    def __init__(self, X, labels, nu=0.5, gamma='scale', tol=1e-3, max_iter=-1, counters=None):
         X = np.asarray(X, dtype=np.float64)
         labels = np.asarray(labels)
         n1 = int((labels == 1).sum())
@@ -187,10 +206,14 @@ class Fit(object):
         self._gamma = gamma_scale(X) if gamma == 'scale' else (1.0 / X.shape[1] if gamma == 'auto' else float(gamma))
         perm, y = grouped_order(labels)
         Q = kernel_matrix(X[perm], y, self._gamma)
-        alpha, _, rho, r, it = solve_nu(Q, y, nu, tol)
-        coef = alpha * (y / r)                # solve_nu_svc: alpha[i] *= y[i] / r
-        rho = rho / r
+        alpha, _, rho, r, it = solve_nu(Q, y, nu, tol, max_iter, counters)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            coef = alpha * (y / r)            # solve_nu_svc: alpha[i] *= y[i] / r
+            rho = rho / r
         sv = np.flatnonzero(alpha != 0)
+        if not (np.isfinite(coef[sv]).all() and np.isfinite(rho)):     # sklearn/svm/_base.py, fit (r = 0)
+            raise ValueError("The dual coefficients or intercepts are not finite. The input data may contain large values "
+                             "and need to be preprocessed.")
         self.support_ = perm[sv].astype(np.int32)
         self.support_vectors_ = X[self.support_]
         self.dual_coef_ = -coef[sv][None, :]  # binary: scikit-learn negates libsvm's coefficients and rho

@@ -145,3 +145,19 @@ def test_kmeans_sort_by_size_relabels_largest_first(monkeypatch):
     got = learning.kmeans(np.zeros((8, 2)), 3, sort_by_size=True)
     assert np.array_equal(got, cluster_ref.sort_assignment_by_size(fit, ascending=False))
     assert np.array_equal(got, [1, 2, 2, 0, 0, 0, 1, 0])
+
+
+@pytest.mark.parametrize("D", [1, 2, 3])
+def test_cell_list_dbscan_equals_the_all_pairs_restatement(D):
+    """cluster_ref.dbscan_cells (the scalable restatement the GPU scale test is held to) against cluster_ref.dbscan on random
+    and dyadic sets with exact duplicates, eps on and off the dyadic grid."""
+    rng = np.random.default_rng(D)
+    for trial in range(8):
+        n = int(rng.integers(1, 400))
+        X = rng.integers(0, 16, (n, D)) / 8.0 if trial % 2 else rng.random((n, D)) * 2.0 - 0.5
+        X[n // 2:n // 2 + n // 4] = X[:n // 4]
+        for eps in (0.125, 0.25, 0.3, 0.5, 1.0):
+            for ms in (1, 2, 4, 7):
+                a, ca = cluster_ref.dbscan(X, eps, ms)
+                b, cb = cluster_ref.dbscan_cells(X, eps, ms)
+                assert np.array_equal(a, b) and np.array_equal(ca, cb), (trial, eps, ms)

@@ -162,3 +162,121 @@ def test_silhouettes_scale_2_16_rows_sampled():
     got = learning.silhouettes(X, lab)
     rows = rng.choice(n, 512, replace=False)
     assert np.abs(got[rows] - cluster_ref.silhouettes_sample(X, lab, rows)).max() <= SKL
+
+
+# ---- several launches and odd shapes --------------------------------------------------------------------------------------
+
+def _profiled(ctx, fn):
+    """fn() with the profiler on: (its result, {kernel: launches})."""
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    try:
+        out = fn()
+        return out, {k: v[1] for k, v in ctx.profile().items()}
+    finally:
+        ctx.profile_enable(False)
+
+
+def _chains(n_pairs=24, length=3500):
+    """Dyadic 2-D rows for eps = 1, min_samples = 4 (every distance exact, d = eps included): pairs of parallel chains
+    spaced 0.5 (chain A at y = 4k, chain B at y = 4k + 2); every other pair joined at its far end by three rows; border
+    rows at y = 4k + 1, exactly eps from one core row of each chain of an unjoined pair (three neighbours: not core); noise
+    rows 3 apart below everything."""
+    x = np.arange(length) * 0.5
+    rows = []
+    for k in range(n_pairs):
+        y0 = 4.0 * k
+        for yy in (y0, y0 + 2.0):
+            rows.append(np.column_stack((x, np.full(length, yy))))
+        if k % 2:
+            rows.append(np.column_stack((np.full(3, x[-1]), y0 + np.array([0.5, 1.0, 1.5]))))
+        else:
+            bx = x[np.arange(3, length - 3, 701)]
+            rows.append(np.column_stack((bx, np.full(len(bx), y0 + 1.0))))
+    rows.append(np.column_stack((np.arange(1000) * 3.0, np.full(1000, -10.0))))
+    return np.vstack(rows)
+
+
+def test_dbscan_union_in_several_launches():
+    """More than 2^17 + 2^15 core rows: the union pass runs in at least two launches (the row blocks I of a later launch
+    start at ib0 > 0).  Components spread over every slice (permuted rows), chains joined at one far end, border rows between
+    two clusters (the smaller label wins) and noise: labels and core mask equal the cell-list restatement."""
+    from phamers_amd import _lib
+    X = _chains()
+    X = X[np.random.default_rng(7).permutation(len(X))]
+    want, want_core = cluster_ref.dbscan_cells(X, 1.0, 4)
+    assert want_core.sum() >= (1 << 17) + (1 << 15)
+    assert (want == -1).sum() == 1000 and want.max() + 1 == 36
+    ctx = _lib.get_context()
+    (labels, core, k), launches = _profiled(ctx, lambda: _lib.dbscan(ctx, X, 1.0, 4))
+    assert launches["phk_cl_union_kernel"] >= 2, launches
+    assert k == want.max() + 1
+    assert np.array_equal(core, want_core)
+    assert np.array_equal(labels, want)
+
+
+def test_dbscan_cell_restatement_sees_two_labelled_borders():
+    """(the scale case above is only as good as its borders: some border rows do touch two clusters)"""
+    X = _chains(n_pairs=2, length=40)
+    labels, core = cluster_ref.dbscan_cells(X, 1.0, 4)
+    d = cluster_ref.pair_distances(X, X)
+    border = np.flatnonzero(~core & (labels >= 0))
+    two = [i for i in border if len(set(labels[(d[i] <= 1.0) & core].tolist())) == 2]
+    assert two and all(labels[i] == min(labels[(d[i] <= 1.0) & core]) for i in two)
+
+
+@pytest.mark.parametrize("D", [1, 15, 16, 17])
+def test_dbscan_small_shapes(D):
+    """n around the 64-row tile, D around the 16-column LDS step, min_samples in {1, 2, 5, n, n + 1}, exact duplicates:
+    labels and core rows equal cluster_ref.dbscan."""
+    from phamers_amd import learning
+    rng = np.random.default_rng(100 + D)
+    eps = 0.25 * np.sqrt(D) + 0.125
+    for n in (1, 2, 63, 64, 65, 129):
+        X = rng.integers(0, 4, (n, D)) / 4.0
+        X[n // 2:n // 2 + n // 4] = X[:n // 4]
+        for ms in sorted({1, 2, 5, n, n + 1}):
+            want, want_core = cluster_ref.dbscan(X, eps, ms)
+            labels, core = learning.dbscan_fit(X, eps, ms)
+            assert np.array_equal(labels, want), (n, ms)
+            assert np.array_equal(core, np.flatnonzero(want_core)), (n, ms)
+
+
+def test_silhouettes_in_several_query_batches():
+    """K = 4 096 labels cap a query batch at 8 192 rows: 40 000 rows run in five batches, the last one partial (the finish
+    kernel's and the sums kernel's q0 > 0).  Singletons score 0; clusters larger than 64 rows span several chunks.  Sampled
+    rows (B - 1, B, B + 1 and the last row among them) within 1e-8 of the restatement; a second call is bit-identical."""
+    from phamers_amd import _lib, learning
+    rng = np.random.default_rng(40)
+    n, K = 40000, 4096
+    lab = np.concatenate((np.repeat(np.arange(20), 300), np.arange(20, 120), 120 + np.arange(n - 6100) % (K - 120)))
+    lab = lab[rng.permutation(n)]
+    assert len(np.unique(lab)) == K
+    X = rng.random((n, 2)) + (lab % 16)[:, None] * 0.25
+    ctx = _lib.get_context()
+    got, launches = _profiled(ctx, lambda: learning.silhouettes(X, lab))
+    assert launches["phk_cl_silhouette_finish_kernel"] >= 2, launches
+    single = np.flatnonzero(np.bincount(lab, minlength=K)[lab] == 1)
+    assert len(single) >= 100 and np.all(got[single] == 0.0)
+    B = 8192
+    rows = np.unique(np.concatenate(([0, B - 1, B, B + 1, 2 * B, n - 1], rng.choice(n, 200, replace=False))))
+    assert np.abs(got[rows] - cluster_ref.silhouettes_sample(X, lab, rows)).max() <= SKL
+    assert np.array_equal(learning.silhouettes(X, lab), got)
+
+
+@pytest.mark.parametrize("D", [1, 16, 17])
+def test_silhouettes_with_unused_label_ids(D):
+    """phk_silhouettes with label ids that have no members (sizes[c] = 0): empty clusters take no part in b; the result
+    equals that of the same clusters numbered without gaps."""
+    from phamers_amd import _lib
+    rng = np.random.default_rng(D)
+    n = 300
+    X = rng.random((n, D))
+    used = np.array([1, 4, 5, 9])
+    lab = used[rng.integers(0, 4, n)]
+    X += (lab == 4)[:, None] * 0.5
+    ctx = _lib.get_context()
+    got = _lib.silhouettes(ctx, X, lab, 12)
+    dense = np.searchsorted(used, lab)
+    assert np.array_equal(got, _lib.silhouettes(ctx, X, dense, 4))
+    assert np.abs(got - cluster_ref.silhouettes(X, lab)).max() <= SKL

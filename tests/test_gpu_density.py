@@ -266,3 +266,50 @@ def test_two_pow_20_synthetic_contigs():
             device.score_counts(ctx, model, d_counts.ptr + int(a) * 256 * 4, int(b - a), "density", d_part.ptr + int(a) * 8)
         assert np.array_equal(d_part.to_host(), full), parts
     model.close()
+
+
+def _profiled(ctx, fn):
+    """fn() with the profiler on: (its result, {kernel: launches})."""
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    try:
+        out = fn()
+        return out, {k: v[1] for k, v in ctx.profile().items()}
+    finally:
+        ctx.profile_enable(False)
+
+
+@pytest.mark.parametrize("D", [1, 31, 33, 65])
+def test_odd_widths_across_chunks_and_query_blocks(D):
+    """The fp64 Gram tile with D % 32 != 0 (phk_kde_partial_kernel<false>) for M around the 256-row chunk and N around the
+    128-query block: within F64 of the restatement, and bit-identical whatever the split of the queries across calls."""
+    from phamers_amd import learning
+    rng = np.random.default_rng(D)
+    h = 0.25 * np.sqrt(D)
+    for M in (1, 255, 256, 257, 513):
+        X = rng.random((M, D))
+        Q = np.vstack((X[rng.integers(0, M, 2048)] + rng.normal(size=(2048, D)) * 0.1, rng.random((2049, D)) * 1.5))
+        want = density_ref.log_density(Q, X, h)
+        full = learning.log_density(Q, X, h)
+        assert density_ref.close(full, want, F64), M
+        for N in (1, 127, 128, 129, 4097):
+            got = learning.log_density(Q[:N], X, h)
+            assert np.array_equal(got, full[:N]), (M, N)
+        parts = [learning.log_density(Q[a:b], X, h) for a, b in ((0, 129), (129, 2049), (2049, 4097))]
+        assert np.array_equal(np.concatenate(parts), full), M
+
+
+def test_query_batches_at_4096_columns():
+    """D = 4096 caps a launch at 8 192 queries (256 MiB of queries): 8 300 queries run in two batches, within F64 of the
+    restatement and bit-identical to the queries scored in one call each side of the cut."""
+    from phamers_amd import _lib, learning
+    rng = np.random.default_rng(4096)
+    D, M, N = 4096, 300, 8300
+    X = rng.random((M, D))
+    Q = np.vstack((X[rng.integers(0, M, N // 2)] + rng.normal(size=(N // 2, D)) * 0.01, rng.random((N - N // 2, D))))
+    h = 4.0
+    got, launches = _profiled(_lib.get_context(), lambda: learning.log_density(Q, X, h))
+    assert launches.get("phk_kde_merge_kernel", 0) >= 2, launches
+    assert density_ref.close(got, density_ref.log_density(Q, X, h), F64)
+    for a, b in ((0, 8191), (8191, 8193), (8193, N)):
+        assert np.array_equal(learning.log_density(Q[a:b], X, h), got[a:b]), (a, b)

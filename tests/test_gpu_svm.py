@@ -204,3 +204,174 @@ def test_entry_points_and_splits_on_two_pow_20_contigs():
     assert clear.mean() > 0.999
     assert np.array_equal(full[sample][clear], np.where(dec[clear] <= 0, 1.0, 0.0)[:])
     model.close()
+
+
+# ---- synthetic dyadic cases: long fits, max_iter, TAU, odd shapes --------------------------------------------------------
+# Every entry is a multiple of 2^-12 (or 1/8), so Q is the same on the device as in NumPy and the fit is held to scikit-learn's
+# NuSVC(shrinking=False) and to the restatement within 1e-12 (tests/golden/scoring_svm_synth.npz).
+from tests.test_svm_host import EXACT, synth_case, synth_ref_fit  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def synth():
+    return helpers.load_npz("scoring_svm_synth.npz")
+
+
+def _solve_launches(ctx, fn):
+    """fn() with the profiler on: (its result, launches of phk_svm_solve_kernel)."""
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    try:
+        out = fn()
+        return out, ctx.profile().get("phk_svm_solve_kernel", (0.0, 0))[1]
+    finally:
+        ctx.profile_enable(False)
+
+
+@pytest.mark.parametrize("case", ["long", "maxiter"])
+def test_nusvc_long_fit_matches_the_unshrunk_scikit_learn_fit(synth, case):
+    """~10 000 iterations (three solver launches, alpha / G / iteration carried between them; near-duplicate rows take the TAU
+    branches) and max_iter = 4 097: the same iterations and support vectors as NuSVC(shrinking=False) and the restatement,
+    coefficients and intercept within 1e-12, decisions within 1e-9, predictions exact."""
+    from phamers_amd import _lib, svm
+    s, t = synth, case + "_noshrink"
+    X, y, q, nu, max_iter = synth_case(s, case)
+    m, launches = _solve_launches(_lib.get_context(), lambda: svm.NuSVC(nu=nu, max_iter=max_iter).fit(X, y))
+    ref = synth_ref_fit(s, case)[0]
+    if case == "long":
+        assert launches >= 3 and int(m.n_iter_[0]) > 2 * 4096
+    assert m._gamma == float(s["gamma_" + t])
+    for want_iter, want_sv, want_coef, want_b in ((int(s["n_iter_" + t][0]), s["support_" + t], s["dual_coef_" + t],
+                                                   s["intercept_" + t][0]),
+                                                  (int(ref.n_iter_[0]), ref.support_, ref.dual_coef_[0], ref.intercept_[0])):
+        assert int(m.n_iter_[0]) == want_iter
+        assert np.array_equal(m.support_, want_sv)
+        assert np.max(np.abs(m.dual_coef_[0] - want_coef)) <= EXACT
+        assert abs(m.intercept_[0] - want_b) <= EXACT
+    assert np.max(np.abs(m.decision_function(q) - s["dec_" + t])) <= dec_tol(s, t, 1e-9)
+    assert np.array_equal(m.predict(q), s["pred_" + t].astype(np.float64))
+
+
+def test_nusvc_agrees_with_the_default_fit_where_scikit_learns_fits_agree(synth):
+    """On a case where shrinking changes scikit-learn's solution, the device (which does not shrink) is exact against
+    NuSVC(shrinking=False), and predicts as NuSVC() does wherever NuSVC() and NuSVC(shrinking=False) agree."""
+    from phamers_amd import svm
+    s = synth
+    X, y, q, nu, _ = synth_case(s, "shrink")
+    m = svm.NuSVC(nu=nu).fit(X, y)
+    t = "shrink_noshrink"
+    assert int(m.n_iter_[0]) == int(s["n_iter_" + t][0])
+    assert np.array_equal(m.support_, s["support_" + t])
+    assert np.max(np.abs(m.dual_coef_[0] - s["dual_coef_" + t])) <= EXACT
+    assert abs(m.intercept_[0] - s["intercept_" + t][0]) <= EXACT
+    pred = m.predict(q)
+    assert np.array_equal(pred, s["pred_" + t].astype(np.float64))
+    same = s["pred_shrink_default"] == s["pred_shrink_noshrink"]
+    assert not same.all()
+    assert np.array_equal(pred[same], s["pred_shrink_default"][same].astype(np.float64))
+
+
+@pytest.mark.parametrize("max_iter", [1, 4095, 4096, 4097, 8193])
+def test_max_iter_at_the_solver_launch_boundaries(synth, max_iter):
+    """max_iter around the 4 096 iterations of one solver launch: 4 096 ends the first launch exactly at the limit, and the
+    second must stop without a step.  Against the restatement with the same max_iter: n_iter_ = max_iter, the same support
+    set, coefficients and rho within 1e-12."""
+    from phamers_amd import _lib
+    X, y, _, nu, _ = synth_case(synth, "long")
+    ctx = _lib.get_context()
+    (sv, coef, rho, it), launches = _solve_launches(
+        ctx, lambda: _lib.nusvc_fit(ctx, X, y, nu, _lib.svm_gamma(X, "scale"), 1e-3, max_iter))
+    ref = svm_ref.Fit(X, y, nu=nu, max_iter=max_iter)
+    assert it == max_iter == int(ref.n_iter_[0])
+    assert launches == max_iter // 4096 + 1
+    assert np.array_equal(sv, ref.support_)
+    assert np.max(np.abs(coef - ref.libsvm_coef)) <= EXACT
+    assert abs(rho - ref.libsvm_rho) <= EXACT
+
+
+# (n, D, positive rows or None for random labels, nu): every n around the 128-row Gram block and the 256-row chunk, D around
+# the 32-column K step (D % 32 != 0: the tile kernel's FULL = false branch), imbalanced classes just inside the nu
+# feasibility bound (at the bound itself the fit is refused: test_degenerate_fits_are_refused)
+SVM_SHAPES = [(2, 32, None, 0.5), (3, 31, None, 0.5), (127, 33, None, 0.5), (128, 32, None, 0.5), (129, 1, None, 0.5),
+              (255, 31, None, 0.5), (256, 33, 64, 0.49), (257, 32, None, 0.5), (1023, 1, None, 0.3),
+              (1024, 31, 256, 0.45), (1025, 33, None, 0.5), (2049, 33, None, 0.5)]
+
+
+def _shape_case(n, D, n_pos, nu):
+    rng = np.random.default_rng(n * 64 + D)
+    X = rng.integers(0, 8, (n, D)) / 8.0
+    if n_pos is None:
+        y = (X[:, 0] + rng.random(n) > 0.9).astype(np.float64)
+        y[:2] = (0.0, 1.0)
+    else:
+        y = np.zeros(n)
+        y[rng.permutation(n)[:n_pos]] = 1.0
+        assert nu * n / 2 <= min(n_pos, n - n_pos)
+    return X, y, rng.integers(0, 8, (300, D)) / 8.0
+
+
+def test_fit_and_decision_across_shapes():
+    """Fit and decision at every shape of SVM_SHAPES against the restatement: the same iterations and support set,
+    coefficients and rho within 1e-12, decisions within 1e-9 (plus the cancellation term) and bit-identical whatever the
+    split of the queries across calls.  The support-vector counts fall on both sides of 256 and 512 (the decision's
+    256-row chunk cut)."""
+    from phamers_amd import _lib
+    ctx = _lib.get_context()
+    counts = []
+    for n, D, n_pos, nu in SVM_SHAPES:
+        X, y, q = _shape_case(n, D, n_pos, nu)
+        tag = (n, D, n_pos, nu)
+        ref = svm_ref.Fit(X, y, nu=nu)
+        sv, coef, rho, it = _lib.nusvc_fit(ctx, X, y, nu, ref._gamma, 1e-3, -1)
+        assert it == int(ref.n_iter_[0]), tag
+        assert np.array_equal(sv, ref.support_), tag
+        assert np.max(np.abs(coef - ref.libsvm_coef)) <= EXACT, tag
+        assert abs(rho - ref.libsvm_rho) <= EXACT, tag
+        counts.append(len(sv))
+        dec = _lib.nusvc_decision(ctx, X[sv], coef, rho, ref._gamma, q)
+        want = svm_ref.decision(q, X[sv], coef, rho, ref._gamma)
+        assert np.max(np.abs(dec - want)) <= 1e-9 + 1e-14 * np.abs(coef).sum(), tag
+        for cut in (1, 127, 128, 129, 299):
+            parts = [_lib.nusvc_decision(ctx, X[sv], coef, rho, ref._gamma, p) for p in (q[:cut], q[cut:])]
+            assert np.array_equal(np.concatenate(parts), dec), (tag, cut)
+    counts = np.array(counts)
+    assert (counts < 256).any() and ((counts > 256) & (counts < 512)).any() and (counts > 512).any(), counts
+
+
+@pytest.mark.parametrize("case", ["pair", "pair+1", "bound256", "bound1024"])
+def test_degenerate_fits_are_refused(case):
+    """Fits where libsvm's r is 0 or infinite, so that its coefficients or rho are not finite, and scikit-learn's fit raises:
+    one row twice with labels 0 and 1 (n = 2, and n = 3 with one more row), and imbalanced classes at the exact nu
+    feasibility bound nu n / 2 = min(n0, n1) (the minority at the upper bound: no free row).  The device fit raises the same
+    error (it returned non-finite or no coefficients before); the restatement agrees.  A model keeps its previous svm fit."""
+    from phamers_amd import _lib, svm
+    X = np.array([[0.25, 0.5, 0.125], [0.25, 0.5, 0.125]])
+    y = np.array([0.0, 1.0])
+    nu = 0.5
+    if case == "pair+1":
+        X, y = np.vstack((X, [[0.5, 0.5, 0.5]])), np.array([0.0, 1.0, 1.0])
+    elif case.startswith("bound"):
+        n = int(case[5:])
+        X, y, _ = _shape_case(n, 33 if n == 256 else 31, n // 4, 0.5)
+        assert nu * n / 2 == min(y.sum(), n - y.sum())
+    msg = "dual coefficients or intercepts are not finite"
+    with pytest.raises(ValueError, match=msg):
+        svm_ref.Fit(X, y, nu=nu)
+    with pytest.raises(ValueError, match=msg):
+        svm.NuSVC(nu=nu).fit(X, y)
+    if case != "pair":
+        return
+    ctx = _lib.get_context()
+    pos, neg = _ref_matrices()
+    P, N = pos[:40], np.vstack((pos[:1], neg[:40]))       # negative row 0 = positive row 0
+    model = _lib.Model(ctx, P, N, k_neighbors=3)
+    model.fit_svm()
+    q = helpers.load_npz("scoring_k4.npz")["q"][:50]
+    before = model.score(q, "svm")
+    mask = np.ones(len(P) + len(N), np.uint8)
+    mask[[0, len(P), len(P) + 1]] = 0                     # a row twice with opposite labels, one more negative row
+    model.set_column_mask(mask)
+    with pytest.raises(ValueError, match=msg):
+        model.fit_svm()
+    assert np.array_equal(model.score(q, "svm"), before)
+    model.close()

@@ -74,6 +74,110 @@ def test_full_matrix_figures(golden):
         assert np.abs(golden["dec_" + tag]).min() >= 1e-5
 
 
+# ---- synthetic dyadic cases (tests/golden/scoring_svm_synth.npz, tools/gen_golden_svm_synth.py) --------------------------
+SYNTH_CASES = ("long", "maxiter", "shrink")
+SYNTH_DATA = {"long": "long", "maxiter": "long", "shrink": "shrink"}
+EXACT = 1e-12
+
+
+def synth_case(s, case):
+    """(train rows, labels, queries, nu, max_iter) of a synthetic case; every entry a multiple of 2^-12."""
+    ds = SYNTH_DATA[case]
+    u = float(s["unit"])
+    return (s["X_" + ds] / u, s["y_" + ds].astype(np.float64), s["q_" + ds] / u, float(s["nu_" + case]),
+            int(s["max_iter_" + case]))
+
+
+@pytest.fixture(scope="module")
+def synth():
+    return helpers.load_npz("scoring_svm_synth.npz")
+
+
+_REF_FITS = {}
+
+
+def synth_ref_fit(s, case):
+    """svm_ref.Fit of a synthetic case with its TAU counters (cached: the long case takes a few seconds)."""
+    if case not in _REF_FITS:
+        X, y, _, nu, max_iter = synth_case(s, case)
+        cnt = {}
+        f = svm_ref.Fit(X, y, nu=nu, max_iter=max_iter, counters=cnt)
+        _REF_FITS[case] = (f, cnt)
+    return _REF_FITS[case]
+
+
+@pytest.mark.parametrize("case", SYNTH_CASES)
+def test_restatement_reproduces_the_unshrunk_synthetic_fits(synth, case):
+    """svm_ref.Fit against NuSVC(shrinking=False) on dyadic data: the same iterations and support vectors, coefficients and
+    intercept within 1e-12, decisions within 1e-9 (plus the cancellation term), predictions exact."""
+    s, t = synth, case + "_noshrink"
+    X, y, q, _, _ = synth_case(s, case)
+    f = synth_ref_fit(s, case)[0]
+    assert f._gamma == float(s["gamma_" + t])
+    assert int(f.n_iter_[0]) == int(s["n_iter_" + t][0])
+    assert np.array_equal(f.support_, s["support_" + t])
+    assert np.max(np.abs(f.dual_coef_[0] - s["dual_coef_" + t])) <= EXACT
+    assert abs(f.intercept_[0] - s["intercept_" + t][0]) <= EXACT
+    assert np.max(np.abs(f.decision_function(q) - s["dec_" + t])) <= dec_tol(s, t, 1e-9)
+    assert np.array_equal(f.predict(q), s["pred_" + t].astype(np.float64))
+
+
+def test_synthetic_fixture_shapes(synth):
+    """The long case needs three launches of the GPU solver (4 096 iterations each) and leaves room for max_iter = 8 193;
+    max_iter = 4 097 stops there; the generator refused near-zero decisions."""
+    s = synth
+    assert int(s["n_iter_long_noshrink"][0]) > 2 * 4096 + 1
+    assert int(s["n_iter_maxiter_noshrink"][0]) == int(s["max_iter_maxiter"]) == 4097
+    for t in [c + "_" + m for c in SYNTH_CASES for m in ("noshrink", "default")]:
+        assert np.abs(s["dec_" + t]).min() >= 1e-5, t
+    X = s["X_long"]
+    y = s["y_long"]
+    assert np.array_equal(X[0], X[1]) and y[0] == y[1]
+    assert np.array_equal(X[2], X[3]) and y[2] != y[3]
+
+
+def test_shrinking_changes_the_solution_in_general(synth):
+    """What DESIGN.md and phamers_amd/svm.py state: scikit-learn's NuSVC() (shrinking on) and NuSVC(shrinking=False) can
+    end at different solutions.  On the 'shrink' case they differ in iterations, intercept and some predictions; on the
+    long case they agree."""
+    s = synth
+    a, b = "shrink_noshrink", "shrink_default"
+    assert int(s["n_iter_" + a][0]) != int(s["n_iter_" + b][0])
+    assert abs(s["intercept_" + a][0] - s["intercept_" + b][0]) > 1e-5
+    assert (s["pred_" + a] != s["pred_" + b]).any()
+    a, b = "long_noshrink", "long_default"
+    assert int(s["n_iter_" + a][0]) == int(s["n_iter_" + b][0])
+    assert np.array_equal(s["support_" + a], s["support_" + b])
+    assert np.array_equal(s["pred_" + a], s["pred_" + b])
+
+
+def test_long_case_takes_the_tau_branches(synth):
+    """libsvm's quad_coef <= 0 -> TAU branches on the long case: in the choice of j and in the update of a same-label pair
+    (near duplicates: Q_ij rounds to 1.0f while the gradients differ).  Exact duplicates never reach them (their gradients
+    stay equal, so grad_diff = 0), and Solver_NU never updates a pair of opposite labels."""
+    s = synth
+    cnt = synth_ref_fit(s, "long")[1]
+    assert cnt["tau_j"] >= 1
+    assert cnt["tau_same"] >= 1
+    assert cnt["tau_opposite"] == 0
+    # the near-duplicate rows are what makes quad_coef vanish: Q_ij = 1.0f with x_i != x_j
+    X, y, _, _, _ = synth_case(s, "long")
+    perm, yg = svm_ref.grouped_order(y)
+    Q = svm_ref.kernel_matrix(X[perm[:64]], yg[:64], svm_ref.gamma_scale(X))
+    pos = {p: k for k, p in enumerate(perm[:64])}
+    pairs = [(i, j) for i in pos for j in pos
+             if i < j and y[i] == y[j] and not np.array_equal(X[i], X[j]) and Q[pos[i], pos[j]] == 1.0]
+    assert pairs
+
+
+def test_max_iter_stops_the_restatement(synth):
+    X, y, _, nu, _ = synth_case(synth, "long")
+    perm, yg = svm_ref.grouped_order(y)
+    Q = svm_ref.kernel_matrix(X[perm], yg, svm_ref.gamma_scale(X))
+    for m in (1, 2, 5000):
+        assert svm_ref.solve_nu(Q, yg, nu, 1e-3, m)[4] == m
+
+
 @pytest.mark.parametrize("tag", ("full", "eq", "fold0", "k5"))
 def test_gamma_scale_has_scikit_learns_bits(golden, tag):
     from phamers_amd import _lib
