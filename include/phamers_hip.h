@@ -365,6 +365,50 @@ int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const
 int phk_dbscan(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, double eps, uint64_t min_samples, int64_t *labels,
                uint8_t *core, uint64_t *n_clusters);
 
+/* ---- PCA and t-SNE (phamer_scorer.do_tsne, scripts/phamer.py:337-366).  Host pointers, float64 throughout;
+ * every sum is taken in an order fixed by the shapes alone (no floating-point atomics): results are bit-identical from run
+ * to run.  The callers (phamers_amd/manifold.py) reject NaN / infinite input first. ---- */
+
+/* Column means mean[D] and the centred covariance cov[D][D] = Xc^T Xc / (n - 1) of X[n][D] (fp64 matrix pipe, rows cut
+ * into chunks whose partial sums meet in chunk order).  2 <= n, 1 <= D <= 8192. */
+int phk_pca_covariance(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, double *mean, double *cov);
+
+/* out[n][n_components] = (X - mean) V^T for the component rows V[n_components][D], each sum in column order. */
+int phk_pca_project(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const double *mean, const double *V,
+                    uint64_t n_components, double *out);
+
+/* For every row of Z[n][d] its k nearest OTHER rows: idx[n][k] and the squared distances d2[n][k], ordered by
+ * (distance, index).  Squared distances are float64 direct differences accumulated by fma in column order (the same bits
+ * for (i, j) and (j, i)).  1 <= k <= min(n - 1, 4096); n < 2^24. */
+int phk_tsne_neighbors(phk_ctx *ctx, const double *Z, uint64_t n, uint64_t d, uint64_t k, int32_t *idx, double *d2);
+
+/* scikit-learn's _binary_search_perplexity on d2[n][k]: the conditional affinities P[n][k] and the precision beta[n] of
+ * every row (beta from 1, at most 100 steps, entropy tolerance 1e-5). */
+int phk_tsne_affinities(phk_ctx *ctx, const double *d2, uint64_t n, uint64_t k, double perplexity, double *P, double *beta);
+
+/* The symmetric affinities (P + P^T) / sum(P + P^T) over the union of the directed edges idx[n][k] as CSR: indptr[n + 1],
+ * and indices / values with room for 2 n k entries (columns ascending within a row); *nnz = entries written.  Host only. */
+int phk_tsne_symmetrize(const int32_t *idx, const double *P, uint64_t n, uint64_t k, int64_t *indptr, int32_t *indices,
+                        double *values, uint64_t *nnz);
+
+/* The t-SNE objective at Y[n][2] for the CSR affinities times `exaggeration`: *kl = sum p log(max(p, eps) / max(q, eps))
+ * over the entries, q_ij = w_ij / Z, w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} w_ij, and
+ * grad[n][2] = 4 (sum_j p_ij w_ij (y_i - y_j) - (1 / Z) sum_j w_ij^2 (y_i - y_j)), the second sum over ALL j. */
+int phk_tsne_gradient(phk_ctx *ctx, const double *Y, uint64_t n, const int64_t *indptr, const int32_t *indices,
+                      const double *values, double exaggeration, double *kl, double *grad);
+
+/* Exactly n_steps updates of scikit-learn's _gradient_descent on Y[n][2] (in place), from update = 0 and gains = 1;
+ * *kl (may be NULL) = the objective at the last gradient evaluation. */
+int phk_tsne_descend(phk_ctx *ctx, double *Y, uint64_t n, const int64_t *indptr, const int32_t *indices, const double *values,
+                     double exaggeration, double momentum, double learning_rate, double min_gain, uint64_t n_steps, double *kl);
+
+/* TSNE._tsne: 250 iterations at momentum 0.5 with the affinities times early_exaggeration, then up to max_iter (>= 250) at
+ * momentum 0.8 without; every 50th iteration the objective and the gradient norm decide n_iter_without_progress and
+ * min_grad_norm as scikit-learn does.  Y[n][2] in place; *kl, *n_iter as TSNE.kl_divergence_, TSNE.n_iter_. */
+int phk_tsne_fit(phk_ctx *ctx, double *Y, uint64_t n, const int64_t *indptr, const int32_t *indices, const double *values,
+                 double early_exaggeration, double learning_rate, uint64_t max_iter, uint64_t n_iter_without_progress,
+                 double min_grad_norm, double *kl, uint64_t *n_iter);
+
 /* learning.distances (scripts/learning.py:47-56; with np.argmin on its result: learning.closest_to :59-66): the
  * Euclidean distances of every row of Q[N][D] to every row of X[M][D], out[N][M], float64, in the reference's
  * direct-difference form sqrt(sum_d (q_d - x_d)^2).  Host pointers. */

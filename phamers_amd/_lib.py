@@ -94,6 +94,16 @@ SIGNATURES = {
     "phk_distances": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_silhouettes": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_void_p]),
     "phk_dbscan": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_double, c_u64, c_void_p, c_void_p, P(c_u64)]),
+    "phk_pca_covariance": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p]),
+    "phk_pca_project": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u64, c_void_p]),
+    "phk_tsne_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
+    "phk_tsne_affinities": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_double, c_void_p, c_void_p]),
+    "phk_tsne_symmetrize": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_void_p, P(c_u64)]),
+    "phk_tsne_gradient": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_double, P(c_double), c_void_p]),
+    "phk_tsne_descend": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double,
+                                 c_u64, P(c_double)]),
+    "phk_tsne_fit": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_u64, c_u64, c_double,
+                             P(c_double), P(c_u64)]),
     "phk_pack_ascii_dev": (c_int, [c_void_p, c_void_p, c_u64, c_char_p, c_void_p, c_void_p, c_void_p]),
     "phk_count_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_int,
                               c_void_p, c_void_p]),

@@ -6,6 +6,8 @@ scripts/fileIO.py (host I/O):
     save_counts(counts, ids, file_name, args=None, header=...)      scripts/fileIO.py:169-181
     save_phamer_scores(ids, scores, file_name, args=None)           scripts/fileIO.py:241-253
     read_phamer_output(filename)                                    scripts/fileIO.py:256-272
+    save_tsne_data(filename, tsne_data, ids, args=None, chops=None) scripts/fileIO.py:199-214
+    read_tsne_file(tsne_file)                                       scripts/fileIO.py:217-237
     generate_summary(args, line_start='', header='')                scripts/basic.py:22-37
 
 The writers are native (csrc/csvio.cpp: rows formatted on all cores -- the features cache of a 1 M-contig FASTA is
@@ -19,6 +21,8 @@ reproduces (a 300 000-value fuzz agrees).  The reference itself is a Python 2.7 
 calls print 12 significant digits.  No file the reference ships covers this, so byte compatibility with the ORIGINAL
 runtime's score text is unpinned; `read_phamer_output` parses either form, and the values agree to those 12 digits.
 """
+import warnings
+
 import numpy as np
 
 from . import _lib
@@ -159,3 +163,35 @@ def read_phamer_output(filename):
     with open(filename, 'r') as f:
         pairs = (line.split(',', 1) for line in f if '#' not in line and ',' in line)
         return {cid: float(val.split()[0]) for cid, val in pairs}
+
+
+# t-SNE files
+def save_tsne_data(filename, tsne_data, ids, args=None, chops=None):
+    """The t-SNE coordinates file (scripts/fileIO.py:199-214): a comment header -- 'chops: <queries>, <positive>,
+    <negative>' on its second line, the argument summary below when ``args`` is given -- then one 'id,x,y' row per point,
+    the coordinates as ``str(float64)`` prints them."""
+    header = "t-SNE coordinates file"
+    if chops:
+        header += "\nchops: %s" % str(chops).replace('(', '').replace(')', '').replace('[', '').replace(']', '').strip()
+    if args:
+        header = generate_summary(args, header=header)
+    data = np.hstack((np.array([ids]).transpose(), np.asarray(tsne_data, dtype=np.float64).astype(str)))
+    np.savetxt(filename, data, fmt='%s', delimiter=',', header=header)
+
+
+def read_tsne_file(tsne_file):
+    """(ids, points (n, 2) float64, chops) of a t-SNE coordinates file (scripts/fileIO.py:217-237); ``chops`` is the list
+    of ints of the header's 'chops:' line, or None."""
+    if not tsne_file:
+        raise ValueError("t-SNE file is None")
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)    # (NumPy remarks on the comment lines when dtype is str)
+        data = np.loadtxt(tsne_file, dtype=str, delimiter=',', ndmin=2)
+    ids = list(data[:, 0].transpose())
+    points = data[:, 1:].astype(float)
+    chops = None
+    with open(tsne_file, 'r') as f:
+        for line in f:
+            if line.startswith('#') and 'chops' in line:
+                chops = [int(c) for c in line.split(":")[1].strip().split(',')]
+    return ids, points, chops

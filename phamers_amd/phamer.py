@@ -86,6 +86,15 @@ class phamer_scorer(object):
         self.k_clusters_negative = 20
         self.eps = [1, 1]
         self.min_samples = [2, 2]
+        # t-SNE (scripts/phamer.py:66, 91-96); use_tsne_python and the plot are not ported
+        self.tsne_data = None
+        self.tsne_perplexity = 30.0
+        self.early_exaggeration = 1.0
+        self.tsne_init = "pca"
+        self.tsne_learning_rate = 2000
+        self.tsne_seed = 10
+        self.pca_preprocess = True
+        self.pca_preprocess_red = 50
         # centroids of the last kmeans / combo call (inspection, tests)
         self.positive_centroids = self.negative_centroids = None
         self.scores = None
@@ -258,6 +267,31 @@ class phamer_scorer(object):
 
     def get_phamer_output_filename(self):
         return os.path.join(self.output_directory, "phamer_scores.csv")
+
+    def get_tsne_output_filename(self):
+        """scripts/phamer.py:443-445."""
+        return os.path.join(self.output_directory, "tsne_coordinates.csv")
+
+    # ---- t-SNE (scripts/phamer.py:325-366) ---------------------------------------------------------------
+    def do_tsne(self):
+        """Embeds queries, positive and negative rows (in that order) into ``tsne_data`` (n, 2) on the device: PCA to
+        ``pca_preprocess_red`` components when ``pca_preprocess``, then manifold.TSNE with the reference's parameters.
+        ``data_points``, ``positive_data`` and ``negative_data`` stay as they were."""
+        from . import manifold
+        all_data = np.vstack((self.data_points, self.positive_data, self.negative_data))
+        if self.pca_preprocess:
+            logger.info("Pre-processing with PCA...")
+            all_data = manifold.PCA(n_components=self.pca_preprocess_red).fit_transform(all_data)
+        self.tsne_data = manifold.TSNE(perplexity=self.tsne_perplexity, early_exaggeration=self.early_exaggeration,
+                                       random_state=self.tsne_seed, init=self.tsne_init,
+                                       learning_rate=self.tsne_learning_rate).fit_transform(all_data)
+        logger.info("t-SNE complete.")
+
+    def save_tsne_data(self, args=None):
+        """Writes ``tsne_data`` with the ids of the three row groups to get_tsne_output_filename()."""
+        ids = np.concatenate((self.data_ids, self.positive_ids, self.negative_ids))
+        chops = (len(self.data_ids), len(self.positive_ids), len(self.negative_ids))
+        fileIO.save_tsne_data(self.get_tsne_output_filename(), self.tsne_data, ids, args=args, chops=chops)
 
     def make_summary_file(self, args=None):
         """phamer_scores.csv (scripts/phamer.py:316-323)."""
