@@ -365,6 +365,32 @@ int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const
 int phk_dbscan(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, double eps, uint64_t min_samples, int64_t *labels,
                uint8_t *core, uint64_t *n_clusters);
 
+/* ---- batched per-contig placement (results_analyzer.get_taxonomy_prediction_dict, scripts/analysis.py:754-792; DESIGN.md
+ * 4.9).  The reference rows X[n][D] stay on the device; phk_placement_run solves, for each of the B rows of Z[B][D], the
+ * problem "k-means of X with the row appended (row n), then the silhouettes of the members of that row's cluster", the
+ * problems of a chunk (`chunk` problems, 0 = the default) side by side in every launch.  Host pointers, float64.
+ *   seeding: scikit-learn's k-means++ on the mean-centred rows with the caller's draws: first_seed = the first centre's
+ *     row, draws[(k - 1)][T] = the uniform(size = T) of each further centre, T = 2 + int(ln k); seeds[B][k] (may be NULL) =
+ *     the chosen rows; seed_margin[b] = the closest call of the fit's seeding decisions, relative to the potential (a
+ *     draw's distance to the nearer prefix-sum value around it; the gap between the best trial's potential and the best
+ *     trial on another row) -- scikit-learn's distances and sums round differently, the caller trusts the seeds above a guard;
+ *   Lloyd: phk_kmeans_lloyd's iteration (same arithmetic: equal labels, sweeps and min_gap for equal centred rows and
+ *     seeds), tolerance tol_rel * mean column variance of the appended matrix; labels[B][n + 1], n_iter[B], min_gap[B];
+ *   silhouettes: sil[b][0 .. n_members[b]) = those of the members of row n's cluster, reference members in row order,
+ *     the appended row last (sil is [B][n + 1]); sums in an order fixed by the labels alone;
+ *   status[b]: PHK_PLACEMENT_DUPLICATE (the row equals a reference row bit for bit: every decision between the twins is an
+ *     exact tie) | PHK_PLACEMENT_EMPTY (a cluster ran empty in some sweep; scikit-learn relocates it).
+ * A problem's results do not depend on B, on its place in Z or on `chunk`.  PHK_ERR_NAN for NaN / infinite rows. */
+#define PHK_PLACEMENT_DUPLICATE 1u
+#define PHK_PLACEMENT_EMPTY 2u
+typedef struct phk_placement phk_placement;
+int phk_placement_create(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, phk_placement **out);
+int phk_placement_destroy(phk_ctx *ctx, phk_placement *pl);
+int phk_placement_run(phk_ctx *ctx, phk_placement *pl, const double *Z, uint64_t B, uint32_t k, uint32_t first_seed,
+                      const double *draws, double tol_rel, int max_iter, uint32_t chunk, uint32_t *labels, uint32_t *seeds,
+                      double *sil, uint32_t *n_members, uint32_t *status, int32_t *n_iter, double *min_gap,
+                      double *seed_margin);
+
 /* ---- PCA and t-SNE (phamer_scorer.do_tsne, scripts/phamer.py:337-366).  Host pointers, float64 throughout;
  * every sum is taken in an order fixed by the shapes alone (no floating-point atomics): results are bit-identical from run
  * to run.  The callers (phamers_amd/manifold.py) reject NaN / infinite input first. ---- */

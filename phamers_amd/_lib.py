@@ -94,6 +94,10 @@ SIGNATURES = {
     "phk_distances": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_silhouettes": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_void_p]),
     "phk_dbscan": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_double, c_u64, c_void_p, c_void_p, P(c_u64)]),
+    "phk_placement_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, P(c_void_p)]),
+    "phk_placement_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_placement_run": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u32, c_u32, c_void_p, c_double, c_int, c_u32, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_pca_covariance": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p]),
     "phk_pca_project": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u64, c_void_p]),
     "phk_tsne_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
@@ -363,6 +367,66 @@ class Model(object):
         out = np.empty(Q.shape[0], dtype=np.float64)
         check(self.ctx.lib.phk_score(self.ctx.handle, self.handle, ptr(Q), Q.shape[0], METHODS[method], ptr(out)))
         return out
+
+
+PLACEMENT_DUPLICATE, PLACEMENT_EMPTY = 1, 2
+
+
+class Placement(object):
+    """Device-resident reference rows of the batched per-contig placement (phk_placement): ``run`` solves, for every row
+    of ``Z``, k-means of the reference rows with that row appended and the silhouettes of the row's cluster."""
+
+    def __init__(self, ctx, reference):
+        self.ctx = ctx
+        X = np.ascontiguousarray(reference, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("reference rows must be a non-empty 2-D array")
+        self.n, self.D = X.shape
+        h = ctypes.c_void_p()
+        rc = ctx.lib.phk_placement_create(ctx.handle, ptr(X), self.n, self.D, ctypes.byref(h))
+        if rc == PHK_ERR_NAN:
+            raise ValueError("Input contains NaN.")
+        check(rc)
+        self.handle = h
+
+    def run(self, Z, k, first_seed, draws, tol=1e-4, max_iter=300, chunk=0):
+        """dict of per-problem arrays: labels (B, n + 1) uint32, seeds (B, k), sil (B, n + 1) of which the first
+        n_members[b] count, n_members, status (PLACEMENT_* bits), n_iter, min_gap, seed_margin."""
+        if not getattr(self, "handle", None):
+            raise ValueError("this Placement is closed")
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.ndim != 2 or Z.shape[1] != self.D:
+            raise ValueError("contig rows must be (B, %d)" % self.D)
+        B, n1, k = Z.shape[0], self.n + 1, int(k)
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        trials = 2 + int(np.log(k))
+        if draws.shape != (k - 1, trials):
+            raise ValueError("draws must be (%d, %d)" % (k - 1, trials))
+        out = {"labels": np.empty((B, n1), dtype=np.uint32), "seeds": np.empty((B, k), dtype=np.uint32),
+               "sil": np.empty((B, n1), dtype=np.float64), "n_members": np.empty(B, dtype=np.uint32),
+               "status": np.empty(B, dtype=np.uint32), "n_iter": np.empty(B, dtype=np.int32),
+               "min_gap": np.empty(B, dtype=np.float64), "seed_margin": np.empty(B, dtype=np.float64)}
+        rc = self.ctx.lib.phk_placement_run(self.ctx.handle, self.handle, ptr(Z), B, k, int(first_seed), ptr(draws), float(tol),
+                                            int(max_iter), int(chunk), ptr(out["labels"]), ptr(out["seeds"]), ptr(out["sil"]),
+                                            ptr(out["n_members"]), ptr(out["status"]), ptr(out["n_iter"]), ptr(out["min_gap"]),
+                                            ptr(out["seed_margin"]))
+        if rc == PHK_ERR_NAN:
+            raise ValueError("Input contains NaN.")
+        if rc == PHK_ERR_ARG:
+            raise ValueError(last_error())
+        check(rc)
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx.lib.phk_placement_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def kde_log_density(ctx, Q, X, h):

@@ -9,6 +9,8 @@ scripts/fileIO.py (host I/O):
     save_tsne_data(filename, tsne_data, ids, args=None, chops=None) scripts/fileIO.py:199-214
     read_tsne_file(tsne_file)                                       scripts/fileIO.py:217-237
     generate_summary(args, line_start='', header='')                scripts/basic.py:22-37
+    read_lineage_file(lineage_file, extend=False)                   scripts/fileIO.py:98-109
+    read_label_file(label_file)                                     scripts/fileIO.py:112-122
 
 The writers are native (csrc/csvio.cpp: rows formatted on all cores -- the features cache of a 1 M-contig FASTA is
 ~0.7 GB of text); what they must reproduce is the output of the reference's np.savetxt calls, and
@@ -37,6 +39,28 @@ def generate_summary(args, line_start='', header=''):
     for old, new in (('Namespace(', line_start), (')', ''), (', ', '\n' + line_start), ('=', ':\t')):
         fields = fields.replace(old, new)
     return line_start + header + '\n' + fields + '\n'
+
+
+def read_label_file(label_file):
+    """{id: [labels]} of a tab-separated file with one header line: the id, then the labels separated by ';'
+    (scripts/fileIO.py:112-122).  TypeError when no file is named, as the reference."""
+    if not label_file:
+        raise TypeError("No label file provided.")
+    with open(label_file, 'r') as f:
+        lines = f.readlines()[1:]
+    return {line.split('\t')[0]: [kind.strip() for kind in line.split('\t')[1].strip().split(';')] for line in lines}
+
+
+def read_lineage_file(lineage_file, extend=False):
+    """{phage id: lineage} of a lineage file (scripts/fileIO.py:98-109); ``extend`` pads every lineage with its last rank
+    to the length of the longest one (taxonomy.extend_lineages)."""
+    dictionary = read_label_file(lineage_file)
+    if extend:
+        from . import taxonomy
+        ids = list(dictionary.keys())
+        lineages = taxonomy.extend_lineages(list(dictionary.values()))
+        dictionary = {ids[i]: lineages[i] for i in range(len(ids))}
+    return dictionary
 
 
 def _comment_block(header, comments='# '):

@@ -10,6 +10,7 @@ learning.py -- drop-in for the hot-path helpers of PhaMers' scripts/learning.py.
     dbscan(data, eps, min_samples, ...)           scripts/learning.py:149-163   -> GPU (neighbour counts + lock-free union-find)
     silhouettes(data, assignment)                 scripts/learning.py:84-92     -> GPU (float64 cluster distance sums)
     cluster_silhouettes(data, assignment, c)      scripts/learning.py:95-104    -> GPU silhouettes of one cluster's members
+    place_contigs(reference, contigs, k)          scripts/analysis.py:771-776   -> GPU, all contigs as one batch (phk_placement_run)
     silhouette_score(data, labels)                (sklearn.metrics name)        -> mean of the GPU silhouettes
     cluster_deviations(data, assignment)          scripts/learning.py:31-44     -> NumPy (O(n D))
     sort_assignment_by_size(assignment, ...)      scripts/learning.py:166-182   -> NumPy
@@ -208,6 +209,81 @@ def kmeans(data, k, verbose=False, sort_by_size=False, _ctx=None):
     if sort_by_size:
         assignment = sort_assignment_by_size(assignment, ascending=False)   # scripts/learning.py:144-145
     return assignment
+
+
+SEED_MIN_MARGIN = 1e-10   # below this relative margin of a seeding decision the host seeding decides
+
+
+def placement_draws(n_samples, k, seed=kmeans_seed):
+    """The random draws of scikit-learn's k-means++ for ``n_samples`` rows and ``k`` centres from a fresh
+    ``RandomState(seed)``: (first centre's row, uniforms (k - 1, 2 + int(ln k))).  They do not depend on the data
+    (kmeans_plusplus_seeds: one ``choice`` over uniform weights, then one ``uniform(size=trials)`` per centre)."""
+    rs = np.random.RandomState(seed)
+    weight = np.ones(n_samples, dtype=np.float64)
+    first = int(rs.choice(n_samples, p=weight / weight.sum()))
+    trials = 2 + int(np.log(k))
+    draws = np.array([rs.uniform(size=trials) for _ in range(1, k)], dtype=np.float64).reshape(k - 1, trials)
+    return first, draws
+
+
+def _place_on_host(reference, contig, k):
+    """One contig the reference's way (scripts/analysis.py:771-776) on the single-problem paths."""
+    appended = np.vstack((reference, contig[None, :]))
+    assignments = np.asarray(kmeans(appended, k))
+    return assignments, cluster_silhouettes(appended, assignments, assignments[-1])
+
+
+def place_contigs(reference, contigs, k_clusters=86, _chunk=0, _details=None):
+    """For every row of ``contigs``: k-means (the reference's ``KMeans(n_clusters=k, random_state=10)``) of the ``reference``
+    rows with that row appended, and the silhouettes of the row's cluster -- what scripts/analysis.py:771-776 computes per
+    contig -- for all contigs in one batched device call (phk_placement_run; the reference rows go up once).  Returns one
+    dict per contig: ``labels`` (n + 1,) int32, scikit-learn's; ``cluster`` = the contig's; ``members`` = the reference
+    rows in it; ``silhouettes`` = theirs in row order, the contig's last; ``route``: 'device', or 'host' where the device
+    declined (a seeding decision within SEED_MIN_MARGIN of a tie, an assignment within KMEANS_MIN_GAP of one, an empty
+    cluster, a contig equal to a reference row) and the contig went through ``kmeans`` + ``cluster_silhouettes`` instead:
+    the same results, only slower.  PHAMERS_KMEANS=sklearn sends every contig that way; PHAMERS_KMEANS=gpu (other seeds
+    than the reference's) is not supported here."""
+    import os
+    mode = os.environ.get("PHAMERS_KMEANS", "device")
+    if mode == "gpu":
+        raise NotImplementedError("place_contigs reproduces the reference's seeds; PHAMERS_KMEANS=gpu selects others")
+    X = _check_rows(reference)
+    Z = _check_rows(np.asarray(contigs, dtype=np.float64).reshape(-1, X.shape[1]) if np.size(contigs) == 0 else contigs)
+    if Z.shape[1] != X.shape[1]:
+        raise ValueError("all the input array dimensions except for the concatenation axis must match exactly, but along "
+                         "dimension 1, the array at index 0 has size %d and the array at index 1 has size %d"
+                         % (X.shape[1], Z.shape[1]))
+    n, k = X.shape[0], int(k_clusters)
+    if k < 1 or k > n + 1:
+        raise ValueError("n_samples=%d should be >= n_clusters=%d." % (n + 1, k))
+    B = Z.shape[0]
+    if B == 0:
+        return []
+    out = None
+    if mode != "sklearn":
+        first, draws = placement_draws(n + 1, k)
+        ctx = _lib.get_context()
+        pl = _lib.Placement(ctx, X)
+        try:
+            out = pl.run(Z, k, first, draws, chunk=_chunk)
+        finally:
+            pl.close()
+        if _details is not None:
+            _details.update(out)
+    records = []
+    for b in range(B):
+        host = out is None or bool(out["status"][b]) or not (out["seed_margin"][b] >= SEED_MIN_MARGIN) \
+            or not (out["min_gap"][b] >= KMEANS_MIN_GAP)
+        if host:
+            labels, sil = _place_on_host(X, Z[b], k)
+            labels = np.asarray(labels).astype(np.int32)
+        else:
+            labels = out["labels"][b].astype(np.int32)
+            sil = out["sil"][b, :out["n_members"][b]].copy()
+        cluster = int(labels[-1])
+        records.append({"labels": labels, "cluster": cluster, "members": np.flatnonzero(labels[:-1] == cluster),
+                        "silhouettes": np.asarray(sil), "route": "host" if host else "device"})
+    return records
 
 
 def get_centroids(data, assignment):
