@@ -110,9 +110,14 @@ int phk_count_ascii(phk_ctx *ctx, const char *bases, const uint64_t *offsets, ui
                     const char *symbols4, int64_t *counts);
 
 /* kmer.normalize_counts (scripts/kmer.py:209-221): out[r][j] = (double)counts[r][j] /
- * (double)sum_j counts[r][j]; a zero row gives NaN exactly as the reference does. */
+ * (double)sum_j counts[r][j]; a zero row gives NaN exactly as the reference does, and a row with entries that sums to
+ * zero (negative entries) gives +-inf and NaN as NumPy's division does.  The row sum is formed in 64-bit integers and
+ * converted once, where the reference converts every entry and sums in float64: the two are equal, and the result bit
+ * for bit the reference's, while the entries' magnitudes sum to less than 2^53 (any count matrix); beyond that the
+ * integer entry point is not exact -- pass such a matrix as float64 to phk_normalize_f64. */
 int phk_normalize_i64(phk_ctx *ctx, const int64_t *counts, uint64_t n, uint64_t D, double *out);
-/* same for an already-float matrix (row sum taken left to right in float64) */
+/* same for an already-float matrix: the row sum in the order of NumPy's np.sum on a contiguous float64 row (pairwise in
+ * pieces of 8 192 elements, the pieces' sums added in order), the quotient an IEEE division */
 int phk_normalize_f64(phk_ctx *ctx, const double *rows, uint64_t n, uint64_t D, double *out);
 
 /* transform_kmers.transform_kmers (scripts/transform_kmers.py:68-88): out[r][j] = rows[r][perm[j]]; the
@@ -218,7 +223,8 @@ int phk_batch_from_fasta_part(phk_ctx *ctx, const char *path, uint32_t part, uin
  * (scripts/phamer.py:132-136, scripts/fileIO.py:134-166): counts[n][D] int64 row-major, D = 4^k.  The run then scores from
  * the same resident integers as one that counted the FASTA file (the reference normalises the cached counts to float rows
  * first: the scores are equal to rounding, and equal bit for bit to the cold run's here).  total_bases of such a batch is 0.
- * PHK_ERR_UNSUPPORTED: D is not 4^k with k <= PHK_MAX_K, or an entry is negative or >= 2^32. */
+ * PHK_ERR_UNSUPPORTED: D is not 4^k with k <= PHK_MAX_K, an entry is negative or >= 2^32, or a row's sum is >= 2^32 (a
+ * batch keeps its row sums as uint32). */
 int phk_batch_from_counts(phk_ctx *ctx, const int64_t *counts, uint64_t n, uint64_t D, phk_batch **out);
 int phk_batch_shape(const phk_batch *b, uint64_t *n, uint64_t *D, uint64_t *total_bases, int *any_invalid);
 /* borrowed device pointers (valid until phk_batch_free): counts[n][D] uint32, row sums[n] uint32 */
@@ -237,7 +243,7 @@ int phk_batch_select(phk_ctx *ctx, const phk_batch *b, const uint64_t *rows, uin
 int phk_batch_column_sums(phk_ctx *ctx, const phk_batch *b, int64_t *sums);
 /* transform_kmers.transform_kmers (scripts/transform_kmers.py:68-88) on resident counts: a new batch with
  * out[r][j] = counts[r][table[j]] (table: 4^k host entries, each < 4^k; the reference's tables are not permutations, so
- * the row sums are recomputed on the device). */
+ * the row sums are recomputed on the device).  PHK_ERR_UNSUPPORTED, and no batch, when a gathered row's sum is >= 2^32. */
 int phk_batch_gather_columns(phk_ctx *ctx, const phk_batch *b, const uint32_t *table, phk_batch **out);
 /* phamer_scorer.score_points (scripts/phamer.py:177-195) on a batch: scores[n] float64 to the host.  PHK_ERR_NAN
  * when a row has no counted window (the reference's NaN row makes scikit-learn raise). */

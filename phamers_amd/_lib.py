@@ -549,7 +549,7 @@ class Batch(object):
     @classmethod
     def from_counts(cls, ctx, counts):
         """A batch from an integer count matrix (n, 4^k) on the host -- the features cache of an earlier run (phk_batch_from_counts).
-        None when the matrix is not such a one (another width, negative or huge entries): the caller keeps the float rows."""
+        None when the matrix is not such a one (another width, negative entries, an entry or a row sum of 2^32 or more): the caller keeps the float rows."""
         c = np.ascontiguousarray(counts, dtype=np.int64)
         if c.ndim != 2:
             return None
@@ -590,7 +590,9 @@ class Batch(object):
         return out
 
     def gather_columns(self, table):
-        """A new resident batch whose column j is this batch's column table[j] (phk_batch_gather_columns)."""
+        """A new resident batch whose column j is this batch's column table[j] (phk_batch_gather_columns).  A table that is
+        not a permutation can lift a row's sum to 2^32 or more, which a batch cannot hold: PhkError with code
+        PHK_ERR_UNSUPPORTED then, and no batch (transform the host matrix with transform_kmers.transform_kmers instead)."""
         table = np.ascontiguousarray(table, dtype=np.uint32)
         if table.shape != (self.D,):
             raise ValueError("gather_columns: the table must have %d entries" % self.D)

@@ -262,13 +262,30 @@ extern "C" int phk_batch_from_ascii(phk_ctx *ctx, const char *bases, const uint6
     return phk_batch_build(ctx, bases, nullptr, offsets, n, k, symbols4, out);
 }
 
-__global__ void phk_rowsum_kernel(const uint32_t *__restrict__ counts, uint64_t N, uint64_t D, uint32_t *__restrict__ out);
+// Row sums of a count matrix that came from the host, one wave per row: formed in 64 bits, and a row whose sum does not fit
+// the batch's uint32 row sums is counted in *overflow (a wrapped sum would be taken for the row's T by every scorer).
+// (phk_rowsum_kernel, score_f16.hip, stays as it is for the scorers: their counts come from the count kernels, whose row
+// sums cannot pass the contig's length.)
+__global__ __launch_bounds__(256) void phk_rowsum_checked_kernel(const uint32_t *__restrict__ counts, uint64_t N, uint64_t D,
+                                                                 uint32_t *__restrict__ out, uint32_t *__restrict__ overflow) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t r = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (r >= N) return;
+    unsigned long long s = 0;
+    for (uint64_t d = lane; d < D; d += 64) s += counts[r * D + d];
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) s += __shfl_xor(s, sh);
+    if (lane == 0) {
+        out[r] = (uint32_t)s;
+        if (s >> 32) atomicAdd(overflow, 1u);
+    }
+}
 
 // A batch from a count matrix the host already holds -- the features cache of an earlier run, read back by
 // fileIO.read_feature_file (scripts/phamer.py:132-136): int64 counts [n][4^k] go up once, narrowed to uint32 on the way into
 // the pinned staging buffers, row sums are formed on the device, and the run scores from the same resident integers as a
-// run that counted the FASTA.  PHK_ERR_UNSUPPORTED when D is not 4^k (k <= PHK_MAX_K) or an entry is negative / >= 2^32
-// (the facade then keeps the reference's float rows).
+// run that counted the FASTA.  PHK_ERR_UNSUPPORTED when D is not 4^k (k <= PHK_MAX_K), an entry is negative / >= 2^32 or a
+// row's sum is >= 2^32 (the facade then keeps the reference's float rows).
 extern "C" int phk_batch_from_counts(phk_ctx *ctx, const int64_t *counts, uint64_t n, uint64_t D, phk_batch **out) {
     PHK_ENTER(ctx, "phk_batch_from_counts");
     PHK_REQUIRE(out && (n == 0 || counts), "phk_batch_from_counts: NULL");
@@ -295,6 +312,9 @@ extern "C" int phk_batch_from_counts(phk_ctx *ctx, const int64_t *counts, uint64
             return PHK_ERR_NOMEM;
         }
         PHK_TRY(phk_stage_ensure(ctx));
+        void *d_over;
+        PHK_TRY(phk_ws(ctx, WS_FLAGS, 64, &d_over));
+        PHK_HIP(hipMemsetAsync(d_over, 0, 4, ctx->stream));
         for (int i = 0; i < 2; ++i) PHK_HIP(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
         const uint64_t total = n * D, per = BATCH_CHUNK / sizeof(uint32_t), nchunks = phk_div_up(total, per);
         std::vector<uint8_t> bad(nchunks, 0);
@@ -326,10 +346,17 @@ extern "C" int phk_batch_from_counts(phk_ctx *ctx, const int64_t *counts, uint64
         }
         for (uint64_t r0 = 0; r0 < n; r0 += 1ull << 24) {   // (one wave per row: 2^24 rows per launch keep the grid below 2^32 threads)
             const uint64_t nr = n - r0 < (1ull << 24) ? n - r0 : 1ull << 24;
-            PHK_LAUNCH(ctx, "phk_rowsum_kernel",
-                       phk_rowsum_kernel<<<dim3((unsigned)phk_div_up(nr, 4)), dim3(256), 0, ctx->stream>>>(b->d_counts + r0 * D, nr, D, b->d_nwin + r0));
+            PHK_LAUNCH(ctx, "phk_rowsum_checked_kernel",
+                       phk_rowsum_checked_kernel<<<dim3((unsigned)phk_div_up(nr, 4)), dim3(256), 0, ctx->stream>>>(
+                           b->d_counts + r0 * D, nr, D, b->d_nwin + r0, (uint32_t *)d_over));
         }
+        uint32_t over = 0;
+        PHK_HIP(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream));
         PHK_HIP(hipStreamSynchronize(ctx->stream));
+        if (over) {
+            phk_set_error("phk_batch_from_counts: the sum of %u row(s) does not fit 32 bits", over);
+            return PHK_ERR_UNSUPPORTED;
+        }
         return PHK_OK;
     };
     rc = body();
@@ -497,10 +524,12 @@ extern "C" int phk_batch_column_sums(phk_ctx *ctx, const phk_batch *b, int64_t *
 }
 
 // out[r][j] = counts[r][table[j]] for every row of a resident batch, and the new rows' sums (the reference's tables are
-// not permutations, so a row's sum can change): one wave per row, the row read once into LDS.
+// not permutations, so a row's sum can change): one wave per row, the row read once into LDS.  The new sum is formed in 64
+// bits; rows whose sum no longer fits the batch's uint32 row sums are counted in *overflow.
 __global__ __launch_bounds__(256) void phk_gather_columns_kernel(const uint32_t *__restrict__ counts, uint64_t n, uint64_t D,
                                                                  const uint32_t *__restrict__ table,
-                                                                 uint32_t *__restrict__ out, uint32_t *__restrict__ out_nwin) {
+                                                                 uint32_t *__restrict__ out, uint32_t *__restrict__ out_nwin,
+                                                                 uint32_t *__restrict__ overflow) {
     extern __shared__ uint32_t gc_row[];   // one row of D per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t nw = blockDim.x >> 6;
@@ -509,7 +538,7 @@ __global__ __launch_bounds__(256) void phk_gather_columns_kernel(const uint32_t 
     for (uint64_t r = (uint64_t)blockIdx.x * nw + wave; r < n; r += total) {
         for (uint64_t j = lane; j < D; j += 64) row[j] = counts[r * D + j];
         __builtin_amdgcn_wave_barrier();
-        uint32_t s = 0;
+        unsigned long long s = 0;
         for (uint64_t j = lane; j < D; j += 64) {
             const uint32_t v = row[table[j]];
             out[r * D + j] = v;
@@ -517,13 +546,16 @@ __global__ __launch_bounds__(256) void phk_gather_columns_kernel(const uint32_t 
         }
 #pragma unroll
         for (int sh = 32; sh > 0; sh >>= 1) s += __shfl_xor(s, sh);
-        if (lane == 0) out_nwin[r] = s;
+        if (lane == 0) {
+            out_nwin[r] = (uint32_t)s;
+            if (s >> 32) atomicAdd(overflow, 1u);
+        }
         __builtin_amdgcn_wave_barrier();
     }
 }
 
 // transform_kmers.transform_kmers (scripts/transform_kmers.py:68-88) on a resident batch: a new batch whose column j is
-// the source's column table[j] (host table, D entries, each < D).
+// the source's column table[j] (host table, D entries, each < D).  PHK_ERR_UNSUPPORTED when a gathered row's sum is >= 2^32.
 extern "C" int phk_batch_gather_columns(phk_ctx *ctx, const phk_batch *b, const uint32_t *table, phk_batch **out) {
     PHK_ENTER(ctx, "phk_batch_gather_columns");
     PHK_REQUIRE(b && table && out, "phk_batch_gather_columns: NULL");
@@ -536,20 +568,28 @@ extern "C" int phk_batch_gather_columns(phk_ctx *ctx, const phk_batch *b, const 
         *out = s;
         return PHK_OK;
     }
-    void *d_tab;
+    void *d_tab, *d_over = nullptr;
     int rc = phk_ws(ctx, WS_OFFSETS, D * 4, &d_tab);
+    if (rc == PHK_OK) rc = phk_ws(ctx, WS_FLAGS, 64, &d_over);
     if (rc == PHK_OK && (hipMalloc(&s->d_counts, s->n * D * sizeof(uint32_t)) != hipSuccess ||
                          hipMalloc(&s->d_nwin, s->n * sizeof(uint32_t)) != hipSuccess))
         rc = PHK_ERR_NOMEM;
     auto body = [&]() -> int {
         PHK_HIP(hipMemcpyAsync(d_tab, table, D * 4, hipMemcpyHostToDevice, ctx->stream));
+        PHK_HIP(hipMemsetAsync(d_over, 0, 4, ctx->stream));
         const uint64_t nw = 4 * D * sizeof(uint32_t) <= 65536 ? 4 : 1;   // waves (rows in LDS) per block: 64 KiB of dynamic LDS
         uint64_t blocks = phk_div_up(s->n, nw);
         if (blocks > (uint64_t)ctx->num_cus * 16) blocks = (uint64_t)ctx->num_cus * 16;
         PHK_LAUNCH(ctx, "phk_gather_columns_kernel",
                    phk_gather_columns_kernel<<<dim3((unsigned)blocks), dim3((unsigned)(64 * nw)), nw * D * sizeof(uint32_t), ctx->stream>>>(
-                       b->d_counts, s->n, D, (const uint32_t *)d_tab, s->d_counts, s->d_nwin));
+                       b->d_counts, s->n, D, (const uint32_t *)d_tab, s->d_counts, s->d_nwin, (uint32_t *)d_over));
+        uint32_t over = 0;
+        PHK_HIP(hipMemcpyAsync(&over, d_over, 4, hipMemcpyDeviceToHost, ctx->stream));
         PHK_HIP(hipStreamSynchronize(ctx->stream));
+        if (over) {
+            phk_set_error("phk_batch_gather_columns: the sum of %u gathered row(s) does not fit 32 bits", over);
+            return PHK_ERR_UNSUPPORTED;
+        }
         return PHK_OK;
     };
     if (rc == PHK_OK) rc = body();

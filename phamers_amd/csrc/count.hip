@@ -1396,13 +1396,19 @@ __global__ __launch_bounds__(256) void phk_normalize_int_kernel(const T *__restr
 #pragma unroll
         for (int sh = 32; sh > 0; sh >>= 1) s += __shfl_xor(s, sh);
         const double ds = (double)s, ry = 1.0 / ds;
-        for (uint64_t j = lane; j < D; j += 64) out[r * D + j] = phk_div_row((double)row[j], ds, ry);
+        if (s != 0) {
+            for (uint64_t j = lane; j < D; j += 64) out[r * D + j] = phk_div_row((double)row[j], ds, ry);
+        } else {   // ry = inf makes every Newton residual NaN: a zero-sum int64 row with entries (1, -1) is +-inf there, NaN elsewhere
+            for (uint64_t j = lane; j < D; j += 64) out[r * D + j] = (double)row[j] / ds;
+        }
     }
 }
 
 // float rows: the row sum follows NumPy's pairwise summation (what np.sum does on a
 // contiguous float64 row: 8 running partial sums per <=128-element block, blocks combined by
-// halving) so that renormalising float rows matches the reference bit for bit.
+// halving; a row wider than 8 192 elements in pieces of 8 192 whose sums are added in order) so that renormalising
+// float rows matches the reference bit for bit (tests/test_gpu_rows.py; the order itself is pinned to np.sum by
+// tests/test_rows_host.py).
 // (The halving is a recursion in NumPy; here its frames live in an explicit stack in LDS, one per wave, walked by lane 0:
 // as a recursive device function it was the library's last kernel with a call stack in scratch memory.)
 __device__ __forceinline__ double phk_np_pairwise_leaf(const double *a, uint64_t n) {   // n <= 128
@@ -1423,6 +1429,7 @@ __device__ __forceinline__ double phk_np_pairwise_leaf(const double *a, uint64_t
 }
 
 #define PW_DEPTH 48   // frames: a row of 2^40 elements halves 34 times
+#define PW_NP_BUFSIZE 8192   // np.getbufsize(): the most elements one call of NumPy's reduction loop sees
 struct PwStack {
     uint64_t off[PW_DEPTH], len[PW_DEPTH];
     double left[PW_DEPTH];
@@ -1471,7 +1478,13 @@ __global__ __launch_bounds__(256) void phk_normalize_f64_kernel(const double *__
     for (uint64_t r = wave; r < n; r += total) {
         const double *row = rows + r * D;
         double s = 0.0;
-        if (lane == 0) s = phk_np_pairwise_sum(row, D, stacks[threadIdx.x >> 6]);
+        if (lane == 0) {
+            // NumPy hands its reduction loop at most PW_NP_BUFSIZE elements at a time: each piece is summed pairwise and
+            // the pieces' sums are added to the first piece's one after another
+            s = phk_np_pairwise_sum(row, D < PW_NP_BUFSIZE ? D : PW_NP_BUFSIZE, stacks[threadIdx.x >> 6]);
+            for (uint64_t o = PW_NP_BUFSIZE; o < D; o += PW_NP_BUFSIZE)
+                s += phk_np_pairwise_sum(row + o, D - o < PW_NP_BUFSIZE ? D - o : PW_NP_BUFSIZE, stacks[threadIdx.x >> 6]);
+        }
         s = __shfl(s, 0);
         for (uint64_t j = lane; j < D; j += 64) out[r * D + j] = row[j] / s;
     }

@@ -242,8 +242,16 @@ static inline void phk_parallel_for(uint64_t n, F fn) {
 // decision kernel spent a third of its vector instructions dividing).  The result IS the correctly rounded quotient, bit
 // for bit what `x / T` returns: with y the correctly rounded reciprocal and q within one ulp of x / T,
 // RN(q + (x - T q) y) = RN(x / T) (Markstein's theorem; fma makes the residual exact), and the first step brings
-// q = RN(x y) within one ulp.  0 / 0 stays NaN (y = inf).  Checked on the device by the normalise kernel's bit-exact
-// tests against NumPy's division (tests/test_gpu_count.py), and in exact rational arithmetic by tools/diag/div_exact_check.py.
+// q = RN(x y) within one ulp.  0 / 0 stays NaN (y = inf) -- and so does x / 0: a caller whose T can be zero beside non-zero
+// entries divides such a row for real (phk_normalize_int_kernel).  tests/test_gpu_rows.py checks the result against NumPy's
+// division, bit for bit, through every normalise entry point (row sums of 2^m - 1, 2^m, 2^m + 1 up to 2^52, entries up to
+// 2^32 - 1, over 2 * 10^6 distinct (entry, row sum) pairs each): that pins the division as a whole -- q0 alone, a reciprocal
+// approximation or relaxed floating-point flags fail there.  It does NOT pin the second step: for the integer operands
+// every caller passes (|x|, |T| < 2^53; the signs change nothing) q1 is already the rounded quotient.
+// q0 + (x - T q0) y differs from x / T by |x / T - q0| |T y - 1| < ulp * 2^-53, while x / T stays ulp / (2 T) or more away
+// from every rounding midpoint: no misrounding is possible below T = 2^51, and above it the quotients nearest to a
+// midpoint (x 2^54 = m T +- 1, m odd: quotients in [1/2, 1)) were searched in exact arithmetic without a case
+// (tools/diag/div_exact_check.py --midpoints).  The second step is kept as the form the theorem covers for every operand.
 __device__ __forceinline__ double phk_div_row(double x, double T, double y) {
     const double q0 = x * y;
     const double q1 = __builtin_fma(__builtin_fma(-q0, T, x), y, q0);

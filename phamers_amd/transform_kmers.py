@@ -61,7 +61,9 @@ def _table(D, reverse, complement, exact):
 def transform_batch(batch, reverse=True, complement=False, exact=False):
     """transform_kmers on a device-resident batch (``_lib.Batch``): a new resident batch whose counts are the
     transformed ones -- a device-to-device column gather (phk_batch_gather_columns), nothing crosses the bus but the
-    4^k-entry table.  Same tables, same IndexError as ``transform_kmers``."""
+    4^k-entry table.  Same tables, same IndexError as ``transform_kmers``.  The reference's tables are not permutations:
+    where one lifts a row's sum to 2^32 or more (a batch keeps uint32 row sums) the call raises ``_lib.PhkError`` with code
+    ``PHK_ERR_UNSUPPORTED``; ``transform_kmers`` on the host matrix has no such limit."""
     if not reverse and not complement:
         return batch
     return batch.gather_columns(_table(batch.D, reverse, complement, exact))

@@ -32,3 +32,32 @@ for x,T in cases():
     if div5(xf,Tf,y)!=w: bad5+=1; print("bad5",x,T) if bad5<5 else None
     if div3(xf,Tf,y)!=w: bad3+=1
 print(n,"cases; mismatches 5-op:",bad5," 3-op:",bad3)
+
+
+# ---- does the one-step form ever misround?  The quotients nearest to a rounding midpoint: x 2^54 = m T +- 1 with m an odd
+# 54-bit integer (x / T in [1/2, 1), as close to the midpoint m / 2^54 as an integer pair can be), T odd in [2^50, 2^53),
+# and again with T >= 0.9 * 2^53, m >= 0.85 * 2^54 and a reciprocal whose rounding error is at least 3/4 of its bound -- the
+# corner where the error of q1 before rounding, |x / T - q0| |T y - 1|, is largest against the distance 1 / (T 2^54).
+def nearest_to_midpoint(lo, hi, tries, m_min=2**53, delta_min=0.0):
+    cnt = bad3 = bad5 = 0
+    for _ in range(tries):
+        T = random.randrange(lo, hi) | 1
+        Tf = float(T); y = 1.0 / Tf
+        if delta_min and abs(Fraction(y) * T - 1) * 2**53 < delta_min: continue
+        inv = pow(T, -1, 2**54)
+        for sign in (1, -1):
+            m = (-sign * inv) % 2**54
+            if m < m_min: continue
+            x = (m * T + sign) >> 54
+            if not 0 < x < T: continue
+            cnt += 1
+            xf = float(x)
+            bad3 += div3(xf, Tf, y) != xf / Tf
+            bad5 += div5(xf, Tf, y) != xf / Tf
+    return cnt, bad3, bad5
+if "--midpoints" in sys.argv:
+    for lo, hi in ((2**52, 2**53), (2**51, 2**52), (2**50, 2**51)):
+        print("T in [2^%d, 2^%d): (cases, 3-op mismatches, 5-op mismatches) =" % (lo.bit_length() - 1, hi.bit_length() - 1),
+              nearest_to_midpoint(lo, hi, 60000))
+    print("T >= 0.9 * 2^53, m >= 0.85 * 2^54, |T y - 1| >= 0.75 * 2^-53:",
+          nearest_to_midpoint(int(0.9 * 2**53), 2**53, 1500000, int(0.85 * 2**54), 0.75))
