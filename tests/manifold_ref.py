@@ -103,14 +103,16 @@ def kth_gap(Z, k):
 
 
 # ---- affinities --------------------------------------------------------------------------------------------------------
-def binary_search_perplexity(d2, perplexity):
+def binary_search_perplexity(d2, perplexity, margins=False):
     """sklearn/manifold/_utils.pyx _binary_search_perplexity on float64 squared distances: (P, beta).  The target is
-    log(float32(perplexity)), scikit-learn's argument being a C float."""
+    log(float32(perplexity)), scikit-learn's argument being a C float.  ``margins``: also, per row, the smallest
+    | |diff| - 1e-5 | over the steps it took -- how far the row's stopping decisions are from flipping under another exp."""
     d2 = np.asarray(d2, np.float64)
     n, k = d2.shape
     target = np.log(float(np.float32(perplexity)))
     P = np.zeros((n, k))
     beta_out = np.empty(n)
+    margin = np.full(n, np.inf)
     for i in range(n):
         d = d2[i]
         beta, bmin, bmax = 1.0, -np.inf, np.inf
@@ -122,6 +124,7 @@ def binary_search_perplexity(d2, perplexity):
             p = p / sum_p
             H = np.log(sum_p) + beta * float(np.cumsum(d * p)[-1])
             diff = H - target
+            margin[i] = min(margin[i], abs(abs(diff) - 1e-5))
             if abs(diff) <= 1e-5:
                 break
             if diff > 0.0:
@@ -131,7 +134,7 @@ def binary_search_perplexity(d2, perplexity):
                 bmax = beta
                 beta = beta / 2.0 if bmin == -np.inf else (beta + bmin) / 2.0
         P[i], beta_out[i] = p, beta
-    return P, beta_out
+    return (P, beta_out, margin) if margins else (P, beta_out)
 
 
 def symmetrize(idx, P):
@@ -194,8 +197,10 @@ def kl_gradient(Y, csr, exaggeration=1.0, rows=None):
 
 
 def gradient_descent(Y0, csr, it, max_iter, exaggeration, momentum, learning_rate, min_gain=0.01, n_iter_check=50,
-                     n_iter_without_progress=300, min_grad_norm=1e-7):
-    """sklearn/manifold/_t_sne.py _gradient_descent: (Y, error, last iteration)."""
+                     n_iter_without_progress=300, min_grad_norm=1e-7, log=None):
+    """sklearn/manifold/_t_sne.py _gradient_descent: (Y, error, last iteration).  ``log``: a list that receives one
+    (iteration, error, best error before the check, gradient norm, iterations since the best after the check, limit,
+    min_grad_norm) per check."""
     p = np.array(Y0, np.float64)
     update, gains = np.zeros_like(p), np.ones_like(p)
     error = best_error = np.finfo(float).max
@@ -213,6 +218,9 @@ def gradient_descent(Y0, csr, it, max_iter, exaggeration, momentum, learning_rat
         update = momentum * update - learning_rate * grad
         p = p + update
         if check:
+            if log is not None:
+                log.append((i, error, best_error, float(np.linalg.norm(grad)), i - (i if error < best_error else best_iter),
+                            n_iter_without_progress, min_grad_norm))
             if error < best_error:
                 best_error, best_iter = error, i
             elif i - best_iter > n_iter_without_progress:
@@ -226,13 +234,13 @@ def descend(Y0, csr, n_steps, exaggeration=1.0, momentum=0.8, learning_rate=200.
     return gradient_descent(Y0, csr, 0, n_steps, exaggeration, momentum, learning_rate, min_gain, n_iter_check=1 << 62)[0]
 
 
-def tsne(Y0, csr, early_exaggeration, learning_rate, max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7):
-    """TSNE._tsne: (Y, KL, n_iter)."""
+def tsne(Y0, csr, early_exaggeration, learning_rate, max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7, log=None):
+    """TSNE._tsne: (Y, KL, n_iter).  ``log``: see gradient_descent; both phases append to it."""
     Y, err, it = gradient_descent(Y0, csr, 0, 250, early_exaggeration, 0.5, learning_rate, n_iter_without_progress=250,
-                                  min_grad_norm=min_grad_norm)
+                                  min_grad_norm=min_grad_norm, log=log)
     if it < 250 or max_iter > 250:
         Y, err, it = gradient_descent(Y, csr, it + 1, max_iter, 1.0, 0.8, learning_rate,
-                                      n_iter_without_progress=n_iter_without_progress, min_grad_norm=min_grad_norm)
+                                      n_iter_without_progress=n_iter_without_progress, min_grad_norm=min_grad_norm, log=log)
     return Y, err, it
 
 
@@ -283,3 +291,188 @@ def reference_rows(golden_dir, n_each):
     order = np.concatenate((dup, rest))[:n_each]
     X = np.vstack((pos[order], neg[:n_each]))
     return X / X.sum(axis=1, keepdims=True)
+
+
+# ---- references and inputs of tests/test_gpu_manifold_shapes.py (conditions on them: tests/test_manifold_host.py) -------
+LD = np.longdouble
+
+
+def covariance(X):
+    """Two-pass mean and covariance in np.longdouble: (mean, cov, |Xc|^T |Xc|) -- the last is what a rounding bound of
+    any summation of the products scales with."""
+    X = np.asarray(X, np.float64).astype(LD)
+    mean = X.sum(axis=0) / X.shape[0]
+    Xc = X - mean
+    return mean, Xc.T @ Xc / (X.shape[0] - 1), np.abs(Xc).T @ np.abs(Xc)
+
+
+def covariance_one_pass(X):
+    """(sum x x^T - n mean mean^T) / (n - 1) in float64: the formula the device does NOT use."""
+    X = np.asarray(X, np.float64)
+    n = X.shape[0]
+    mean = X.sum(axis=0) / n
+    return (X.T @ X - n * np.outer(mean, mean)) / (n - 1)
+
+
+def pca_chunk_rows(n, D):
+    """tsne.hip's pca_chunk_rows: rows per chunk of the PCA sums."""
+    cap = min(65535, max(1, (256 << 20) // (D * D * 8)))
+    R = max(1024, -(-n // cap))
+    return (R + 3) & ~3
+
+
+def covariance_bound(n, D, abs_gram):
+    """Elementwise bound on the device covariance: every entry is a sum of n products of centred values, accumulated in
+    chains of at most R rows (one chunk, on the matrix pipe) and then over the chunks in order.  With u = eps / 2 the unit
+    roundoff: each centred factor carries <= u, each product <= u, every addition <= u, so the entry is off by at most
+    (R + chunks + 3) u sum|xc_a xc_b| (Higham, Accuracy and Stability, (3.5)).  The bound used is twice that -- c = 1 with
+    eps in place of u -- and the spare half covers the second-order term n delta_a delta_b of the device mean's own error
+    delta <= (R + chunks) u mean|x|."""
+    R = pca_chunk_rows(n, D)
+    chain = R + -(-n // R) + 3
+    return chain * MACHINE_EPSILON * np.asarray(abs_gram, np.float64) / (n - 1), chain
+
+
+def spectrum_data(seed, n, D, offset=0.0):
+    """Gaussian rows whose column scales fall geometrically (clear eigenvalue gaps at the top), plus a common offset."""
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((n, D)) * (0.8 ** np.minimum(np.arange(D), 40)) + offset
+
+
+PCA_CASES = [(1023, 7, 0.0), (1024, 64, 0.0), (1025, 65, 0.0), (1027, 100, 0.0), (2049, 257, 0.0), (5000, 300, 0.0),
+             (40, 100, 0.0), (3000, 16, 1e6)]
+PCA_CAP_CASE = (2101, 4096)     # 256 MiB / (8 D^2) = 2 chunks at most: 1052 rows per chunk, above the floor of 1024
+
+
+def lattice_rows(seed, n, side, d):
+    """n rows drawn from the integer grid {0 .. side - 1}^d: every squared distance is a small integer, shared by many."""
+    return np.random.default_rng(seed).integers(0, side, (n, d)).astype(np.float64)
+
+
+# (seed, n, side, d, k): 64 cells x ~47 rows, 125 cells x ~24 rows, 16 cells x ~100 rows; k cuts a class of several hundred equal distances
+LATTICE_CASES = [(21, 3001, 8, 2, 700), (22, 3001, 5, 3, 300), (23, 1601, 4, 2, 900)]
+
+
+def tie_cut(Drow, k):
+    """For one row of squared distances (self = inf): (members of the class of the k-th smallest value, how many of them
+    the selection takes)."""
+    T = np.partition(Drow, k - 1)[k - 1]
+    members = np.flatnonzero(Drow == T)
+    return members, k - int(np.sum(Drow < T))
+
+
+def affinity_edge_cases():
+    """(name, d2, perplexity) of the perplexity-search edge tests: sorted positive rows as a neighbour search gives them,
+    scaled by 1e6 (every exp underflows at beta = 1: the sum_p == 0 branch, then halving) and 1e-6 (doubling), and k = 4096."""
+    rng = np.random.default_rng(31)
+    base = np.sort(rng.chisquare(3, (400, 91)) + 0.05, axis=1)
+    wide = np.sort(rng.chisquare(3, (64, 4096)) + 0.05, axis=1)
+    return [("x1e6", base * 1e6, 30.0), ("x1e-6", base * 1e-6, 30.0), ("plain", base, 30.0), ("k4096", wide, 1365.0),
+            ("k4096_p30", wide, 30.0)]
+
+
+def control_problem():
+    """(X, Y0) of the control-loop cases: 90 rows in three blobs, perplexity CONTROL_PERPLEXITY, the first two coordinates as
+    the initial embedding (a start in the basin the descent contracts in -- from scikit-learn's 1e-4 start the symmetry
+    breaking amplifies rounding by many orders of magnitude)."""
+    X = synthetic(11, 90, 5)
+    return X, np.ascontiguousarray(X[:, :2])
+
+
+CONTROL_PERPLEXITY = 8.0
+# name -> TSNE arguments.  Learning rates are low on purpose: at scikit-learn's 'auto' rate the gains rule makes a 90-row
+# descent chaotic within a hundred steps (a 1e-13 change of the start moves the result by tenths of the span), and no
+# tolerance could then hold the device to the restatement.  'stall' has learning rate 0: the embedding does not move, every
+# check after a phase's first compares an error with itself, so the progress rule alone decides, with j - best_iter equal to
+# the limit exactly at iteration 349 ('>' goes on to 399, '>=' would stop at 349).
+CONTROL_CASES = {
+    "max_iter_250": dict(early_exaggeration=1.0, learning_rate=5.0, max_iter=250),
+    "max_iter_251": dict(early_exaggeration=12.0, learning_rate=1.0, max_iter=251),
+    "max_iter_333": dict(early_exaggeration=1.0, learning_rate=5.0, max_iter=333),
+    "full_1000": dict(early_exaggeration=1.0, learning_rate=2.0, max_iter=1000),
+    "grad_norm_phase_1": dict(early_exaggeration=12.0, learning_rate=1.0, max_iter=1000, min_grad_norm=1e3),
+    "grad_norm_phase_2": dict(early_exaggeration=1.0, learning_rate=5.0, max_iter=1000, min_grad_norm=0.03),
+    "stall": dict(early_exaggeration=1.0, learning_rate=0.0, max_iter=1000, n_iter_without_progress=50),
+}
+CONTROL_EXPECTED_N_ITER = {"max_iter_250": 250, "max_iter_251": 250, "max_iter_333": 332, "full_1000": 999,
+                           "grad_norm_phase_1": 99, "grad_norm_phase_2": 299, "stall": 399}
+
+
+def control_reference(name, log=None):
+    """ref.tsne of a control case on the restatement's own affinities: (Y, KL, n_iter)."""
+    X, Y0 = control_problem()
+    k = min(X.shape[0] - 1, int(3 * CONTROL_PERPLEXITY + 1))
+    idx, d2 = neighbors(X, k)
+    csr = symmetrize(idx, binary_search_perplexity(d2, CONTROL_PERPLEXITY)[0])
+    kw = dict(CONTROL_CASES[name])
+    return tsne(Y0, csr, kw.pop("early_exaggeration"), kw.pop("learning_rate"), log=log, **kw)
+
+
+def decision_margins(log, moved=True):
+    """The smallest relative margin of the decisions of a check log: error < best and grad_norm <= min_grad_norm.  Where
+    the embedding did not move (learning rate 0) an error equal to the best is the same number computed twice, not a close
+    call, and is left out."""
+    m = np.inf
+    for (i, error, best, gnorm, since, limit, min_gn) in log:
+        if moved or error != best:
+            m = min(m, abs(error - best) / max(abs(error), abs(best)))
+        if min_gn > 0:
+            m = min(m, abs(gnorm - min_gn) / max(gnorm, min_gn))
+    return m
+
+
+def lattice_embedding(seed, n, side):
+    """(Y (n, 2), cells (side^2, 2), counts): n points on the cells of a side x side integer grid, seeded multiplicities."""
+    rng = np.random.default_rng(seed)
+    cell = rng.integers(0, side * side, n)
+    cells = np.stack(np.divmod(np.arange(side * side), side), axis=1).astype(np.float64)
+    return cells[cell], cells, np.bincount(cell, minlength=side * side)
+
+
+def ring_csr(n, seed):
+    """A sparse P for large n: up to three entries per row (i + 1, i + 7919 or i + n // 3, a seeded column; wrapped), values summing to 1."""
+    rng = np.random.default_rng(seed)
+    i = np.arange(n, dtype=np.int64)
+    far = 7919 if n > 2 * 7919 else n // 3
+    cols = np.sort(np.stack(((i + 1) % n, (i + far) % n, (i + rng.integers(2, n - 1, n)) % n), axis=1), axis=1)
+    keep = np.concatenate((np.ones((n, 1), bool), cols[:, 1:] != cols[:, :-1]), axis=1) & (cols != i[:, None])
+    indptr = np.concatenate(([0], np.cumsum(keep.sum(axis=1)))).astype(np.int64)
+    vals = rng.random(int(indptr[-1])) + 0.5
+    return indptr, cols[keep].astype(np.int32), vals / vals.sum()
+
+
+def kl_gradient_lattice(Y, cells, counts, csr, rows, exaggeration=1.0):
+    """(KL, grad of ``rows``, Z, sum |repulsive terms| of ``rows`` (len, 2), sum |attractive terms| (len, 2), sum |KL terms|)
+    for an embedding whose points lie on ``cells`` with multiplicities ``counts``, in np.longdouble:
+    Z = sum_ab c_a c_b w(a - b) - n (O(cells^2)), r_i = sum_b c_b w^2 (y_i - y_b) (O(cells) per row)."""
+    indptr, cols, vals = csr
+    Y = np.asarray(Y, np.float64)
+    n = Y.shape[0]
+    C, c = cells.astype(LD), counts.astype(LD)
+    Z = LD(0)
+    for s in range(0, len(C), 256):
+        d = C[s:s + 256, None, :] - C[None, :, :]
+        Z += ((1 / (1 + (d ** 2).sum(axis=2))) * c[None, :] * c[s:s + 256, None]).sum()
+    Z -= n
+    d = Y[rows].astype(LD)[:, None, :] - C[None, :, :]
+    w2 = (1 / (1 + (d ** 2).sum(axis=2))) ** 2 * c[None, :]
+    rep = (w2[:, :, None] * d).sum(axis=1)
+    rep_abs = (w2[:, :, None] * np.abs(d)).sum(axis=1)
+    src = np.repeat(np.arange(n), np.diff(indptr))
+    p = vals.astype(LD) * exaggeration
+    de = Y[src].astype(LD) - Y[cols].astype(LD)
+    w = 1 / (1 + (de ** 2).sum(axis=1))
+    terms = p * np.log(np.maximum(p, MACHINE_EPSILON) / np.maximum(w / Z, MACHINE_EPSILON))
+    att, att_abs = np.zeros((len(rows), 2), LD), np.zeros((len(rows), 2), LD)
+    for a, i in enumerate(rows):
+        e = slice(indptr[i], indptr[i + 1])
+        att[a] = ((p[e] * w[e])[:, None] * de[e]).sum(axis=0)
+        att_abs[a] = ((p[e] * w[e])[:, None] * np.abs(de[e])).sum(axis=0)
+    return terms.sum(), 4 * (att - rep / Z), Z, rep_abs, att_abs, np.abs(terms).sum()
+
+
+def gradient_ranges(n):
+    """tsne.hip's column ranges of the gradient: (tiles, G, [first row of range g for g in 0..G])."""
+    tiles = -(-n // 256)
+    G = min(max(1, -(-2048 // tiles)), tiles)
+    return tiles, G, [min(n, 256 * (tiles * g // G)) for g in range(G + 1)]

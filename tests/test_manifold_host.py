@@ -165,3 +165,106 @@ def test_what_is_refused():
     t = manifold.TSNE()
     assert (t.perplexity, t.early_exaggeration, t.learning_rate, t.max_iter, t.n_iter_without_progress, t.min_grad_norm,
             t.init, t.method, t.angle) == (30.0, 12.0, 'auto', 1000, 300, 1e-7, 'pca', 'barnes_hut', 0.5)
+
+
+# ---- conditions on the inputs and references of tests/test_gpu_manifold_shapes.py ---------------------------------------
+@pytest.mark.parametrize("seed,n,side,d,k", ref.LATTICE_CASES)
+def test_lattice_cases_cut_a_class_of_hundreds_of_equal_distances(seed, n, side, d, k):
+    """Some row's threshold class has more than 256 members and is cut inside; the taken members span several 256-entry
+    scan steps, and in the cut's own step members of an earlier wave precede it."""
+    Z = ref.lattice_rows(seed, n, side, d)
+    assert n % 64 != 0
+    D = ref.sqdist_rows(Z, np.arange(n))
+    assert np.array_equal(D, np.round(D))
+    D[np.arange(n), np.arange(n)] = np.inf
+    big = steps = waves = 0
+    for i in range(n):
+        members, need = ref.tie_cut(D[i], k)
+        if len(members) > 256 and 0 < need < len(members):
+            taken, cut = members[:need], members[need - 1]
+            big += 1
+            steps += bool(members[0] // 256 < cut // 256)
+            waves += bool(np.any((taken // 256 == cut // 256) & ((taken % 256) // 64 < (cut % 256) // 64)))
+    assert big >= 100 and steps >= 100 and waves >= 100, (big, steps, waves)
+
+
+def test_affinity_edge_cases_keep_their_rows():
+    """At least 95% of each case's rows stop with a margin >= 1e-9 to the 1e-5 threshold at every step; the scaled cases
+    take the branches they are there for."""
+    for name, d2, perplexity in ref.affinity_edge_cases():
+        P, beta, margin = ref.binary_search_perplexity(d2, perplexity, margins=True)
+        assert np.mean(margin >= 1e-9) >= 0.95, name
+        assert np.allclose(P.sum(axis=1), 1.0, rtol=1e-12), name
+    cases = {name: d2 for name, d2, _ in ref.affinity_edge_cases()}
+    assert np.exp(-cases["x1e6"]).max() == 0.0          # sum_p == 0 at beta = 1
+    assert ref.binary_search_perplexity(cases["x1e6"][:8], 30.0)[1].max() < 1e-5      # ... halved ~19 times
+    assert ref.binary_search_perplexity(cases["x1e-6"][:8], 30.0)[1].min() > 1e5      # doubled ~20 times
+    P, beta = ref.binary_search_perplexity(np.zeros((2, 40)), 5.0)
+    assert np.all(beta == 2.0 ** 100) and np.all(P == 1.0 / 40)
+
+
+@pytest.mark.parametrize("name", sorted(ref.CONTROL_CASES))
+def test_control_cases_decide_with_a_margin(name):
+    """Every decision of every control-loop case has a relative margin >= 1e-6 on the reference side, and the case ends
+    where it was chosen to end."""
+    log = []
+    Y, kl, it = ref.control_reference(name, log)
+    kw = ref.CONTROL_CASES[name]
+    assert it == ref.CONTROL_EXPECTED_N_ITER[name]
+    assert ref.decision_margins(log, moved=kw["learning_rate"] > 0) >= 1e-6
+    if name == "max_iter_250":
+        assert kl == np.finfo(float).max and not [l for l in log if l[0] > 249]
+    if name == "grad_norm_phase_1":        # stopped at the first check of each phase: phase 2 began at it + 1 = 50
+        assert [l[0] for l in log] == [49, 99]
+    if name == "grad_norm_phase_2":        # phase 1 ran through, phase 2 stopped at its first check
+        assert [l[0] for l in log] == [49, 99, 149, 199, 249, 299] and log[-1][3] <= kw["min_grad_norm"] < log[-2][3]
+    if name == "stall":                    # 349: j - best_iter == limit, not an improvement, goes on; 399: stops
+        assert [(l[0], l[4]) for l in log if l[0] > 249] == [(299, 0), (349, 50), (399, 100)] and log[-1][5] == 50
+        assert log[-2][1] == log[-2][2]
+
+
+def test_one_pass_covariance_misses_the_bound_the_device_is_held_to():
+    n, D, offset = ref.PCA_CASES[-1]
+    assert offset == 1e6
+    X = ref.spectrum_data(n, n, D, offset)
+    mean, cov, gram = ref.covariance(X)
+    bound, chain = ref.covariance_bound(n, D, gram)
+    two_pass = (X - X.mean(axis=0)).T @ (X - X.mean(axis=0)) / (n - 1)
+    assert np.all(np.abs(two_pass - cov) <= bound)                     # float64, two passes: inside
+    err = np.abs(ref.covariance_one_pass(X) - cov).astype(np.float64)
+    assert np.max(err / bound) > 100.0                                  # float64, one pass: far outside
+
+
+def test_chunk_rows_of_the_cap_case():
+    n, D = ref.PCA_CAP_CASE
+    assert ref.pca_chunk_rows(n, D) == 1052 > 1024 and ref.pca_chunk_rows(n, 2048) == 1024
+    assert n * D * 8 < 80e6 and (n - 1052) % 4 != 0
+    assert ref.pca_chunk_rows(2049, 257) == 1024 and ref.pca_chunk_rows(5000, 300) == 1024
+
+
+def test_lattice_reference_is_the_pairwise_one():
+    n = 3000
+    Y, cells, counts = ref.lattice_embedding(41, n, 16)
+    csr = ref.ring_csr(n, 42)
+    assert counts.max() > 1 and np.all(np.diff(csr[0]) >= 2) and abs(csr[2].sum() - 1.0) < 1e-12
+    rows = np.array([0, 1, 255, 256, 1500, n - 1])
+    kl, g, Z, rep_abs, att_abs, kl_abs = ref.kl_gradient_lattice(Y, cells, counts, csr, rows)
+    kl_r, g_r = ref.kl_gradient(Y, csr, rows=rows)
+    assert abs(float(kl) - kl_r) <= 1e-12 * abs(kl_r)
+    assert rel(g.astype(np.float64), g_r) < 1e-11
+    assert rep_abs.shape == att_abs.shape == (len(rows), 2) and kl_abs >= abs(kl)
+    assert ref.gradient_ranges(11521)[:2] == (46, 45) and ref.gradient_ranges(20000)[:2] == (79, 26)
+    assert ref.gradient_ranges(524288 + 257)[:2] == (2050, 1) and ref.gradient_ranges(8448)[:2] == (33, 33)
+
+
+def test_perplexity_above_the_sort_width_never_reaches_the_device(monkeypatch):
+    from phamers_amd import manifold
+
+    def no_device(*a, **k):
+        raise AssertionError("the device was reached")
+    monkeypatch.setattr(manifold._lib, "get_context", no_device)
+    X = ref.synthetic(3, 4200, 2)
+    with pytest.raises(ValueError, match="k=4097 neighbours"):
+        manifold.neighbors(X, 4097)
+    with pytest.raises(ValueError, match="k=4099 neighbours: must be between 1 and min"):
+        manifold.TSNE(perplexity=1366).fit_transform(X)
