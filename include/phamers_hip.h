@@ -446,6 +446,37 @@ int phk_tsne_fit(phk_ctx *ctx, double *Y, uint64_t n, const int64_t *indptr, con
  * direct-difference form sqrt(sum_d (q_d - x_d)^2).  Host pointers. */
 int phk_distances(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, double *out);
 
+/* ---- evaluation of score vectors (scripts/learning.py:185-243) ---- */
+
+#define PHK_SORT_TILE 4096        /* keys per tile of the radix sort */
+#define PHK_SORT_MAX_BLOCKS 512   /* workgroups of a sort pass; beyond PHK_SORT_TILE x this many keys a workgroup takes several tiles */
+
+/* perm[n] = the permutation that orders keys[n] ascending (descending != 0: descending), STABLE both ways: equal keys stay
+ * in index order; -0.0 and +0.0 are equal.  What np.argsort(keys, kind='stable') (of -keys when descending) returns.  A
+ * least-significant-digit radix sort on order-preserving 64-bit images of the keys.  PHK_ERR_NAN when a key is NaN or
+ * infinite, PHK_ERR_UNSUPPORTED for n >= 2^32; n == 0 is success.  Host pointers; the _dev form takes device pointers and
+ * is stream ordered. */
+int phk_argsort_f64(phk_ctx *ctx, const double *keys, uint64_t n, int descending, uint32_t *perm);
+int phk_argsort_f64_dev(phk_ctx *ctx, const double *d_keys, uint64_t n, int descending, uint32_t *d_perm);
+
+/* scikit-learn's roc_curve(labels, scores, drop_intermediate = flag) in integers: scores sorted descending, one point per
+ * run of equal scores -- tps = positives (label != 0) so far, fps = 1 + index - tps, threshold = the run's score -- with the
+ * flag set and more than two points every interior point at which the second differences of fps and tps are both zero
+ * dropped, and (0, 0, +inf) put first.  fps, tps, thresholds: caller arrays of n + 1 places, *m = the points written;
+ * *area2 = sum_i (fps_i - fps_i-1)(tps_i + tps_i-1) = 2 P N AUC exactly.  The rates fps / fps[m - 1], tps / tps[m - 1] and
+ * area2 / (2 P N) are the caller's divisions.  Sort, scans and compaction run on the device; only the m points come back.
+ * PHK_ERR_NAN when a score is NaN or infinite, PHK_ERR_UNSUPPORTED for n >= 2^32; a class without members is no error.
+ * phk_roc_curve: host pointers.  _dev: d_scores[n] float64 (as phk_score_dev writes them) and d_labels[n] uint8 on the
+ * device, the outputs on the host. */
+int phk_roc_curve(phk_ctx *ctx, const double *scores, const uint8_t *labels, uint64_t n, int drop_intermediate, uint64_t *fps,
+                  uint64_t *tps, double *thresholds, uint64_t *m, uint64_t *area2);
+int phk_roc_curve_dev(phk_ctx *ctx, const double *d_scores, const uint8_t *d_labels, uint64_t n, int drop_intermediate,
+                      uint64_t *fps, uint64_t *tps, double *thresholds, uint64_t *m, uint64_t *area2);
+
+/* counts[4] = tp, fp, fn, tn at `threshold` (scripts/learning.py:206-209): positives (label != 0) with score >= threshold,
+ * negatives with >=, positives with <, negatives with <.  Host pointers. */
+int phk_truth_counts(phk_ctx *ctx, const double *scores, const uint8_t *labels, uint64_t n, double threshold, uint64_t *counts);
+
 /* ---- device API -------------------------------------------------------------------- */
 /* ASCII -> packed stream (+ mask).  d_any_invalid (one uint32, device) is set non-zero when
  * some base is not one of symbols4; it may be NULL. */

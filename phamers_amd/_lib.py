@@ -18,6 +18,7 @@ PHK_ERR_ARG, PHK_ERR_HIP, PHK_ERR_NOMEM, PHK_ERR_UNSUPPORTED, PHK_ERR_NAN, PHK_E
 METHOD_KNN, METHOD_KMEANS, METHOD_COMBO, METHOD_DENSITY, METHOD_SVM = 1, 2, 3, 4, 5
 METHODS = {"knn": METHOD_KNN, "kmeans": METHOD_KMEANS, "combo": METHOD_COMBO, "density": METHOD_DENSITY, "svm": METHOD_SVM}
 MAX_K = 7
+SORT_TILE, SORT_MAX_BLOCKS = 4096, 512   # PHK_SORT_TILE, PHK_SORT_MAX_BLOCKS
 ABI_VERSION = 2
 
 c_void_p, c_int, c_u32, c_u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64
@@ -108,6 +109,11 @@ SIGNATURES = {
                                  c_u64, P(c_double)]),
     "phk_tsne_fit": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_u64, c_u64, c_double,
                              P(c_double), P(c_u64)]),
+    "phk_argsort_f64": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_void_p]),
+    "phk_argsort_f64_dev": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_void_p]),
+    "phk_roc_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p, c_void_p, P(c_u64), P(c_u64)]),
+    "phk_roc_curve_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p, c_void_p, P(c_u64), P(c_u64)]),
+    "phk_truth_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p]),
     "phk_pack_ascii_dev": (c_int, [c_void_p, c_void_p, c_u64, c_char_p, c_void_p, c_void_p, c_void_p]),
     "phk_count_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_int,
                               c_void_p, c_void_p]),

@@ -26,6 +26,7 @@ The reference shuffles the fold assignment with the unseeded global NumPy genera
 ``scoring_function`` (anything but phamer.score_points) is honoured with the reference's per-fold calls.
 """
 import logging
+import os
 
 import numpy as np
 
@@ -35,6 +36,9 @@ from . import phamer
 
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.WARNING)
+
+
+ALL_METHODS = ('dbscan', 'kmeans', 'knn', 'svm', 'density', 'combo')   # scripts/cross_validate.py:304
 
 
 class FoldPlan(object):
@@ -68,6 +72,9 @@ class cross_validator(object):
         self.k_neighbors = 3                         # scripts/phamer.py:79
         self.positive_bandwidth = 0.005              # scripts/phamer.py:82-83 (method 'density')
         self.negative_bandwidth = 0.01
+        self.score_threshold = 0                     # scripts/cross_validate.py:53
+        self.output_directory = "cross_validation"   # scripts/cross_validate.py:55
+        self.methods = list(ALL_METHODS)             # what cross_validate_all_algorithms runs (scripts/cross_validate.py:304)
 
     # ---- the reference's entry point ----------------------------------------------------------------------
     def cross_validate(self):
@@ -156,3 +163,121 @@ class cross_validator(object):
             n_p = int(out_p.sum())
             pos_scores[out_p], neg_scores[out_n] = scores[:n_p], scores[n_p:]
         return pos_scores, neg_scores
+
+    # ---- evaluation of the last run (scripts/cross_validate.py:135-238; the plots stay out) ---------------
+    def performance(self):
+        """(fpr, tpr, auc) of the last run's scores: learning.predictor_performance, what the reference's plot_ROC draws."""
+        if self.positive_scores is None or self.negative_scores is None:
+            raise ValueError("performance: no scores yet, call cross_validate() first")
+        return learning.predictor_performance(self.positive_scores, self.negative_scores)
+
+    def _open_output(self, file_name):
+        directory = os.path.dirname(file_name)
+        if directory and not os.path.isdir(directory):
+            os.makedirs(directory)
+        return open(file_name, 'w')
+
+    def make_metrics_file(self):
+        """metrics.txt (scripts/cross_validate.py:156-172): the header line, then one ``name<TAB>value`` line per metric of
+        learning.get_predictor_metrics at ``score_threshold``, values by ``repr``.  (The reference appends a pandas
+        Series.to_csv to the header: the same lines under a pandas-version dependent column line, which is not written.)"""
+        metrics = learning.get_predictor_metrics(self.positive_scores, self.negative_scores, threshold=self.score_threshold)
+        with self._open_output(self.get_metric_filename()) as f:
+            f.write("# Cross Validation Performance Metrics\n")
+            for name in learning.METRIC_NAMES:
+                f.write("%s\t%r\n" % (name, metrics[name]))
+
+    def make_summary_file(self, id_label_map=None):
+        """scores.txt (scripts/cross_validate.py:174-192): every positive id with its score, ascending, and its label when a
+        map is given -- the reference's text.  The order is the device argsort of the scores (learning.argsort_scores,
+        stable): ids with equal scores stay in ``positive_ids`` order, which is what the reference's
+        ``sorted(zip(score, id))`` gives when the ids of tied scores already ascend as strings; where they do not, the
+        reference orders the tied ids as strings and this file keeps them in input order."""
+        scores = np.asarray(self.positive_scores, dtype=np.float64)
+        order = learning.argsort_scores(scores)
+        text = "# Cross Validation Scores"
+        for i in order:
+            id, score = self.positive_ids[i], scores[i]
+            if id_label_map is None:
+                text += "\n{id}\t{score}".format(id=id, score=score)
+            else:
+                text += "\n{id}\t{score}\t{label}".format(id=id, score=score, label=id_label_map[id])
+        with self._open_output(self.get_summary_filename()) as f:
+            f.write(text)
+
+    def cross_validate_all_algorithms(self):
+        """{method: (fpr, tpr, auc)} for every method of ``self.methods`` (scripts/cross_validate.py:194-222 without the
+        plot).  Each method runs ``cross_validate()`` afresh: with ``seed`` set all of them use the same fold plan."""
+        results = {}
+        for method in self.methods:
+            self.method = method
+            logger.info("%d-Fold Cross Validation" % self.N)
+            logger.info("Algorithm: %s" % method.upper())
+            positive_scores, negative_scores = self.cross_validate()
+            results[method] = learning.predictor_performance(positive_scores, negative_scores)
+        return results
+
+    # filename makers (scripts/cross_validate.py:224-238)
+    def get_metric_filename(self):
+        return os.path.join(self.output_directory, "metrics.txt")
+
+    def get_summary_filename(self):
+        return os.path.join(self.output_directory, "scores.txt")
+
+    def get_all_algorithms_filename(self):
+        return os.path.join(self.output_directory, "all_algorithms_auc.txt")
+
+
+def main(argv=None):
+    """The reference's command line (scripts/cross_validate.py:240-307) without its plots: metrics.txt and scores.txt in the
+    output directory, with -a also all_algorithms_auc.txt (``method<TAB>repr(auc)`` per line).  --seed and --kmeans are
+    this project's additions."""
+    import argparse
+    from . import fileIO, kmer
+    parser = argparse.ArgumentParser(description="This script is for doing N-fold cross validation of the Phamer scoring algorithm",
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    input_group = parser.add_argument_group("Inputs")
+    input_group.add_argument('-pf', '--positive_features_file', required=True, help="Positive features file")
+    input_group.add_argument('-nf', '--negative_features_file', required=True, help="Negative features file")
+    output_group = parser.add_argument_group("Outputs")
+    output_group.add_argument('-out', '--output_directory', default="cross_validation", help="Output directory")
+    options_group = parser.add_argument_group("Options")
+    options_group.add_argument('-N', '--N_fold', default=20, type=int, help="Number of iteration in N-fold cross validation")
+    options_group.add_argument('-m', '--method', default='combo', help="Scoring algorithm method")
+    options_group.add_argument('-a', '--test_all', action='store_true', help="Flag to cross validate all algorithms")
+    options_group.add_argument('-l', '--labels_file', help="Label file mapping id to label")
+    options_group.add_argument('-equal', '--equalize_reference', action='store_true', help="Use same number of reference data from each")
+    options_group.add_argument('--seed', type=int, default=None, help="Seed of the fold assignment (unseeded as the reference when absent)")
+    options_group.add_argument('--kmeans', default='sklearn', choices=('sklearn', 'gpu'), help="Per-fold k-means fit")
+    console_options_group = parser.add_argument_group("Console Options")
+    console_options_group.add_argument('-v', '--verbose', action='store_true', default=False, help="Verbose output")
+    console_options_group.add_argument('--debug', action='store_true', default=False, help="Debug console")
+    args = parser.parse_args(argv)
+    logger.setLevel(logging.DEBUG if args.debug else logging.INFO if args.verbose else logging.WARNING)
+
+    validator = cross_validator()
+    validator.method, validator.N = args.method, args.N_fold
+    validator.output_directory = args.output_directory
+    validator.seed, validator.kmeans = args.seed, args.kmeans
+    validator.positive_ids, positive_data = fileIO.read_feature_file(args.positive_features_file)
+    validator.negative_ids, negative_data = fileIO.read_feature_file(args.negative_features_file)
+    validator.positive_data = kmer.normalize_counts(positive_data)
+    validator.negative_data = kmer.normalize_counts(negative_data)
+    validator.equalize_reference = args.equalize_reference
+    validator.cross_validate()
+    validator.make_metrics_file()
+    id_label_map = fileIO.read_label_file(args.labels_file) if args.labels_file else None
+    validator.make_summary_file(id_label_map=id_label_map)
+    if args.test_all:
+        validator.methods = list(ALL_METHODS)
+        results = validator.cross_validate_all_algorithms()
+        with validator._open_output(validator.get_all_algorithms_filename()) as f:
+            for method in validator.methods:
+                f.write("%s\t%r\n" % (method, results[method][2]))
+    logger.info("Cross validation complete.")
+    return 0
+
+
+if __name__ == '__main__':
+    import sys
+    sys.exit(main())

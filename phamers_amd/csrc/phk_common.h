@@ -79,6 +79,7 @@ enum PhkSlot {
     WS_CTL,         // small control words the kernels keep zeroed themselves (no memset per call): the count planner's two
                     // alternating blocks (PhkCountCtl), see phk_launch_count
     WS_KDE,         // density scoring: per-chunk (max, sum) partials + query norms (density.hip)
+    WS_SORT,        // evaluation: the radix sort's key / index pairs and histograms, the ROC curve's points (evaluate.hip)
     WS_SLOTS
 };
 

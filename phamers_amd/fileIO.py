@@ -123,11 +123,15 @@ def _read_feature_file_native(feature_file):
     return ids, features
 
 
-def read_feature_file(feature_file, normalize=False, id=None):
+def read_feature_file(feature_file, normalize=False, id=None, old=False):
     """'id,c0,c1,...' rows ('#' comment lines skipped) -> (ids, int features), optionally row
-    normalised on the GPU (kmer.normalize_counts); ``id`` selects one row's features."""
-    native = _read_feature_file_native(feature_file)
-    if native is not None:
+    normalised on the GPU (kmer.normalize_counts); ``id`` selects one row's features.  ``old``: a legacy file without the
+    id column (scripts/fileIO.py:143-145) -- every id is 'No_ID', the features are np.loadtxt's floats."""
+    native = None if old else _read_feature_file_native(feature_file)
+    if old:
+        features = np.atleast_2d(np.loadtxt(feature_file, delimiter=','))
+        ids = np.array(['No_ID'] * features.shape[0])
+    elif native is not None:
         ids, features = native
     else:   # any other shape of file: the reference's own parse
         data = np.atleast_2d(np.loadtxt(feature_file, delimiter=',', dtype=str))

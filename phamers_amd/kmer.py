@@ -97,6 +97,75 @@ def count(data, kmer_length, symbols=DNA, normalize=False):
     return kmer_count
 
 
+def cut_plan(lengths, cut_size):
+    """The pieces of ``count_cuts`` for sequences of the given lengths: (offsets, keep, owner, index).  Sequence r is cut at
+    every ``cut_size`` bases from its start; ``offsets`` (uint64, pieces + 1) are the piece boundaries in the concatenated
+    bases, tails included; ``keep`` = the pieces of exactly ``cut_size`` bases, by position; ``owner`` / ``index`` = the
+    sequence each kept piece comes from and its number within it."""
+    cut_size = int(cut_size)
+    if cut_size < 1:
+        raise ValueError("cut_size must be >= 1, got %r" % (cut_size,))
+    lengths = np.asarray(lengths, dtype=np.int64)
+    full = lengths // cut_size
+    pieces = full + (lengths % cut_size != 0)                     # a shorter tail is one more piece
+    first = np.concatenate(([0], np.cumsum(pieces)))              # first piece of every sequence
+    starts = np.concatenate(([0], np.cumsum(lengths)))
+    owner_all = np.repeat(np.arange(len(lengths)), pieces)
+    index_all = np.arange(first[-1]) - first[owner_all]
+    offsets = np.empty(first[-1] + 1, dtype=np.uint64)
+    offsets[:-1] = starts[owner_all] + index_all * cut_size
+    offsets[-1] = starts[-1]
+    keep = np.flatnonzero(index_all < full[owner_all])
+    return offsets, keep, owner_all[keep], index_all[keep]
+
+
+def count_cuts(fasta_file_or_sequences, kmer_length, cut_size, symbols=DNA):
+    """k-mer counts of the consecutive, non-overlapping pieces of exactly ``cut_size`` bases of every sequence (a shorter
+    tail is dropped, a sequence shorter than ``cut_size`` gives no row): (ids, counts (pieces, 4^k) int64), id
+    ``<record id>_<piece index>``.  ``fasta_file_or_sequences``: a FASTA path (record id = Bio.SeqIO's record.id, the
+    first word of the title line: any FASTA file can be cut, whatever its headers look like) or a list of strings (record
+    ids '0', '1', ...).  The cut rule is this project's own: the reference reads cut
+    files (scripts/cut_validator.py) but ships nothing that writes them.  All pieces, tails included, are the contigs of
+    ONE device batch over the file's bases (phk_batch_from_ascii); phk_batch_select keeps the full-size ones."""
+    import ctypes
+    sym = _check_symbols(symbols)
+    k = int(kmer_length)
+    ctx = _lib.get_context()
+    fasta = None
+    if isinstance(fasta_file_or_sequences, str):
+        fasta = _lib.Fasta(fasta_file_or_sequences)
+    try:
+        if fasta is not None:
+            record_ids = fasta.ids()
+            lengths, total = fasta.lengths(), fasta.total_bases
+            bases_ptr, hold = ctypes.c_void_p(fasta._bases), None
+        else:
+            raw = [s.encode("latin-1", "replace") for s in fasta_file_or_sequences]
+            record_ids = [str(i) for i in range(len(raw))]
+            lengths, total = np.array([len(r) for r in raw], dtype=np.int64), sum(len(r) for r in raw)
+            hold = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
+            bases_ptr = _lib.ptr(np.ascontiguousarray(hold))
+        offsets, keep, owner, index = cut_plan(lengths, cut_size)
+        ids = ["%s_%d" % (record_ids[r], i) for r, i in zip(owner, index)]
+        if len(keep) == 0:
+            return ids, np.zeros((0, 4 ** k), dtype=np.int64)
+        h = ctypes.c_void_p()
+        _lib.check(ctx.lib.phk_batch_from_ascii(ctx.handle, bases_ptr, _lib.ptr(offsets), len(offsets) - 1, k, sym,
+                                                ctypes.byref(h)))
+        batch = _lib.Batch(ctx, h)
+        try:
+            chosen = batch.select(keep)
+            try:
+                return ids, chosen.counts()
+            finally:
+                chosen.close()
+        finally:
+            batch.close()
+    finally:
+        if fasta is not None:
+            fasta.close()
+
+
 def count_file(input_file, kmer_length, symbols=DNA, normalize=False):
     """Counts k-mers of every record of a FASTA file (scripts/kmer.py:114-140).  Returns
     (ids, counts): ids parsed by the reference's header rules (scripts/id_parser.py:89-100),

@@ -406,3 +406,130 @@ def sort_assignment_by_size(assignment, ascending=True):
     for new, cluster in enumerate(sorted_assignment):
         new_assignment[assignment == cluster] = new
     return new_assignment
+
+
+# ---- evaluation of score vectors (scripts/learning.py:185-243) -----------------------------------------------------------
+METRIC_NAMES = ('tp', 'fp', 'fn', 'tn', 'tpr', 'fpr', 'fnr', 'tnr', 'ppv', 'npv', 'fdr', 'acc')   # scripts/learning.py:232
+
+
+class Metrics(dict):
+    """The reference's twelve prediction metrics in its order, by key or by attribute (``m['tpr']``, ``m.tpr``): what
+    scripts/learning.py:223-243 returns as a pandas Series, without pandas."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        self[name] = value
+
+
+def _scores_1d(scores):
+    return np.ascontiguousarray(np.asarray(scores, dtype=np.float64).ravel())
+
+
+def _scores_and_labels(positive_scores, negative_scores):
+    pos, neg = _scores_1d(positive_scores), _scores_1d(negative_scores)
+    labels = np.zeros(len(pos) + len(neg), dtype=np.uint8)
+    labels[:len(pos)] = 1
+    return np.concatenate((pos, neg)), labels
+
+
+def argsort_scores(scores, descending=False):
+    """The stable permutation that orders ``scores``: ``np.argsort(scores, kind='stable')``, or of ``-scores`` when
+    ``descending`` (ties stay in index order both ways), sorted on the device (phk_argsort_f64).  ValueError for NaN or
+    infinite scores."""
+    x = _scores_1d(scores)
+    perm = np.empty(len(x), dtype=np.uint32)
+    ctx = _lib.get_context()
+    rc = ctx.lib.phk_argsort_f64(ctx.handle, _lib.ptr(x), len(x), 1 if descending else 0, _lib.ptr(perm))
+    if rc == _lib.PHK_ERR_NAN:
+        raise ValueError("Input contains NaN or infinity.")
+    _lib.check(rc)
+    return perm.astype(np.int64)
+
+
+def roc_points(scores, labels, drop_intermediate=True, _device=None):
+    """scikit-learn's ``roc_curve(labels, scores, drop_intermediate=...)`` before its divisions (phk_roc_curve): (fps, tps,
+    thresholds, area2) with integer fps / tps (uint64) and area2 = 2 P N AUC as a Python int.  ``_device`` = (d_scores,
+    d_labels, n): device pointers of resident scores (float64) and labels (uint8) instead (phk_roc_curve_dev)."""
+    import ctypes
+    ctx = _lib.get_context()
+    if _device is None:
+        x = _scores_1d(scores)
+        lab = np.ascontiguousarray(np.asarray(labels).ravel() != 0, dtype=np.uint8)
+        if lab.shape != x.shape:
+            raise ValueError("Found input variables with inconsistent numbers of samples: [%d, %d]" % (len(lab), len(x)))
+        n, fn, a, b = len(x), ctx.lib.phk_roc_curve, _lib.ptr(x), _lib.ptr(lab)
+    else:
+        a, b, n = _device
+        fn, a, b = ctx.lib.phk_roc_curve_dev, ctypes.c_void_p(int(a)), ctypes.c_void_p(int(b))
+    fps, tps = np.empty(n + 1, dtype=np.uint64), np.empty(n + 1, dtype=np.uint64)
+    thresholds = np.empty(n + 1, dtype=np.float64)
+    m, area2 = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = fn(ctx.handle, a, b, n, 1 if drop_intermediate else 0, _lib.ptr(fps), _lib.ptr(tps), _lib.ptr(thresholds),
+            ctypes.byref(m), ctypes.byref(area2))
+    if rc == _lib.PHK_ERR_NAN:
+        raise ValueError("Input contains NaN or infinity.")   # scikit-learn's roc_curve raises on such scores too
+    _lib.check(rc)
+    return fps[:m.value].copy(), tps[:m.value].copy(), thresholds[:m.value].copy(), int(area2.value)
+
+
+def rates_from_points(fps, tps, area2):
+    """(fpr, tpr, auc) from the integer curve: scikit-learn's own divisions ``fps / fps[-1]``, ``tps / tps[-1]`` (bit-identical
+    rates), and auc = area2 / (2 P N), one rounding of the exact area.  A class without members gives NaN rates and a NaN
+    area, as scikit-learn does (with its warning)."""
+    fps, tps = np.asarray(fps, dtype=np.float64), np.asarray(tps, dtype=np.float64)
+    n_neg, n_pos = int(fps[-1]), int(tps[-1])
+    fpr = fps / fps[-1] if n_neg else np.full(fps.shape, np.nan)
+    tpr = tps / tps[-1] if n_pos else np.full(tps.shape, np.nan)
+    auc = int(area2) / (2 * n_pos * n_neg) if n_pos and n_neg else float('nan')   # (Python's int / int rounds once)
+    return fpr, tpr, auc
+
+
+def predictor_performance(positive_scores, negative_scores):
+    """(false positive rate, true positive rate, ROC area) of a scoring (scripts/learning.py:185-196): scikit-learn's
+    ``roc_curve`` -- the rates bit-identical to it -- and ``auc``, from a sort and integer scans on the device."""
+    scores, labels = _scores_and_labels(positive_scores, negative_scores)
+    fps, tps, _, area2 = roc_points(scores, labels)
+    return rates_from_points(fps, tps, area2)
+
+
+def truth_counts(positive_scores, negative_scores, threshold=0):
+    """(tp, fp, fn, tn) at ``threshold``, >= / < as scripts/learning.py:206-209, counted on the device (phk_truth_counts)."""
+    scores, labels = _scores_and_labels(positive_scores, negative_scores)
+    counts = np.zeros(4, dtype=np.uint64)
+    ctx = _lib.get_context()
+    rc = ctx.lib.phk_truth_counts(ctx.handle, _lib.ptr(scores), _lib.ptr(labels), len(scores), float(threshold), _lib.ptr(counts))
+    if rc == _lib.PHK_ERR_ARG:
+        raise ValueError(_lib.last_error())
+    _lib.check(rc)
+    return tuple(int(c) for c in counts)
+
+
+def _rates(tp, fp, fn, tn):
+    tpr = float(tp) / (tp + fn) if tp + fn != 0 else 0      # scripts/learning.py:210-217
+    fpr = float(fp) / (fp + tn) if fp + tn != 0 else 0
+    return tpr, fpr, 1 - tpr, 1 - fpr
+
+
+def get_truth_table(positive_scores, negative_scores, threshold=0):
+    """(TPR, FPR, FNR, TNR) at ``threshold`` (scripts/learning.py:199-220)."""
+    return _rates(*truth_counts(positive_scores, negative_scores, threshold))
+
+
+def get_predictor_metrics(positive_scores, negative_scores, threshold=0):
+    """The reference's metrics (scripts/learning.py:223-243) as a ``Metrics`` mapping in its order: tp, fp, fn, tn, tpr, fpr,
+    fnr, tnr, ppv, npv, fdr, acc.  The counts are floats, as the cells of the reference's Series are.  ZeroDivisionError
+    where the reference raises it (nothing scored at or above / below the threshold)."""
+    tp, fp, fn, tn = truth_counts(positive_scores, negative_scores, threshold)
+    m = Metrics()
+    m.tp, m.fp, m.fn, m.tn = float(tp), float(fp), float(fn), float(tn)
+    m.tpr, m.fpr, m.fnr, m.tnr = _rates(tp, fp, fn, tn)
+    m.ppv = float(m.tp) / (m.tp + m.fp)
+    m.npv = float(m.tn) / (m.tn + m.fn)
+    m.fdr = 1 - m.ppv
+    m.acc = float(m.tp + m.tn) / (m.tp + m.fp + m.fn + m.tn)
+    return m
