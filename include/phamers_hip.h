@@ -397,6 +397,30 @@ int phk_placement_run(phk_ctx *ctx, phk_placement *pl, const double *Z, uint64_t
                       double *sil, uint32_t *n_members, uint32_t *status, int32_t *n_iter, double *min_gap,
                       double *seed_margin);
 
+/* ---- the silhouette-against-k sweep (scripts/cluster.py:31-47): S k-means problems on the SAME rows
+ * X[n][D] (resident, phk_sweep_create), problem s with its own k = ks[s], first centre first_seed[s] and draws, the problems
+ * of a chunk (`chunk` problems, 0 = the default, 64) side by side in every launch.  Host pointers, float64.
+ *   centring: the k-means stages run on X - column mean (NumPy's, bit for bit), the silhouettes on X as given;
+ *   seeding: scikit-learn's k-means++ with the caller's draws, as phk_placement_run: draws + draw_off[s] = the
+ *     (ks[s] - 1) x T_s uniforms of problem s, T_s = 2 + int(ln ks[s]) (draws may be NULL when every k is 1);
+ *     seeds (may be NULL) = the chosen rows of all problems, concatenated (ks[0], then ks[1], ...); seed_margin[s];
+ *   Lloyd: phk_kmeans_lloyd's iteration, tolerance tol_rel * mean column variance: labels[S][n], n_iter[S], min_gap[S]
+ *     equal the single-problem path's bit for bit for equal seeds;
+ *   silhouettes: sil[S][n] (may be NULL: the pass is skipped) = phk_silhouettes(X, labels[s], ks[s]) bit for bit, from ONE
+ *     pass over the pairs for all problems: the distances d[n][n] are stored (and kept in the handle) when n * n * 8 bytes
+ *     fit pair_budget (bytes; negative = a quarter of the free device memory at the call), else every problem takes
+ *     phk_silhouettes' own pass;
+ *   status[s]: PHK_SWEEP_EMPTY (a cluster ran empty in some sweep; scikit-learn relocates it).
+ * A problem's results do not depend on S, on its place or on `chunk`.  PHK_ERR_NAN for NaN / infinite rows (at create);
+ * PHK_ERR_ARG for k outside 1..n, with sil for k outside 2..n-1, for first_seed >= n, for k >= 2981. */
+#define PHK_SWEEP_EMPTY PHK_PLACEMENT_EMPTY
+typedef struct phk_sweep phk_sweep;
+int phk_sweep_create(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, phk_sweep **out);
+int phk_sweep_destroy(phk_ctx *ctx, phk_sweep *sw);
+int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint32_t *ks, const uint32_t *first_seed, const double *draws,
+                  const uint64_t *draw_off, double tol_rel, int max_iter, uint32_t chunk, int64_t pair_budget, uint32_t *labels,
+                  uint32_t *seeds, double *sil, uint32_t *status, int32_t *n_iter, double *min_gap, double *seed_margin);
+
 /* ---- PCA and t-SNE (phamer_scorer.do_tsne, scripts/phamer.py:337-366).  Host pointers, float64 throughout;
  * every sum is taken in an order fixed by the shapes alone (no floating-point atomics): results are bit-identical from run
  * to run.  The callers (phamers_amd/manifold.py) reject NaN / infinite input first. ---- */

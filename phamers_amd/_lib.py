@@ -99,6 +99,10 @@ SIGNATURES = {
     "phk_placement_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_placement_run": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u32, c_u32, c_void_p, c_double, c_int, c_u32, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_sweep_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, P(c_void_p)]),
+    "phk_sweep_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_sweep_run": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_u32,
+                              ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_pca_covariance": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p]),
     "phk_pca_project": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u64, c_void_p]),
     "phk_tsne_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
@@ -376,6 +380,7 @@ class Model(object):
 
 
 PLACEMENT_DUPLICATE, PLACEMENT_EMPTY = 1, 2
+SWEEP_EMPTY = 2
 
 
 class Placement(object):
@@ -426,6 +431,74 @@ class Placement(object):
     def close(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self.ctx.lib.phk_placement_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Sweep(object):
+    """Device-resident rows of the k-means sweep (phk_sweep): ``run`` solves one k-means problem per entry of ``ks`` on the
+    same rows, each with its own first centre and draws, and (optionally) the silhouettes of every row of every problem."""
+
+    def __init__(self, ctx, data):
+        self.ctx = ctx
+        X = np.ascontiguousarray(data, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("the rows must be a non-empty 2-D array")
+        self.n, self.D = X.shape
+        h = ctypes.c_void_p()
+        rc = ctx.lib.phk_sweep_create(ctx.handle, ptr(X), self.n, self.D, ctypes.byref(h))
+        if rc == PHK_ERR_NAN:
+            raise ValueError("Input contains NaN.")
+        check(rc)
+        self.handle = h
+
+    def run(self, ks, first_seeds, draws, silhouettes=True, tol=1e-4, max_iter=300, chunk=0, pair_budget=-1):
+        """``draws[s]`` = the (ks[s] - 1, 2 + int(ln ks[s])) uniforms of problem s.  dict of per-problem results: labels
+        (S, n) uint32, seeds (list of S arrays), sil (S, n) or None, status (SWEEP_EMPTY bit), n_iter, min_gap,
+        seed_margin.  ``pair_budget``: bytes the stored pair distances may take (-1: a quarter of the free memory)."""
+        if not getattr(self, "handle", None):
+            raise ValueError("this Sweep is closed")
+        ks = np.ascontiguousarray(ks, dtype=np.uint32)
+        S, n = len(ks), self.n
+        first = np.ascontiguousarray(first_seeds, dtype=np.uint32)
+        if first.shape != (S,) or len(draws) != S:
+            raise ValueError("one first seed and one set of draws per problem")
+        flat, offs, at = [], np.zeros(S, dtype=np.uint64), 0
+        for s in range(S):
+            k = int(ks[s])
+            d = np.ascontiguousarray(draws[s], dtype=np.float64)
+            if k >= 1 and d.size != (k - 1) * (2 + int(np.log(k))):
+                raise ValueError("draws of problem %d must be (%d, %d)" % (s, k - 1, 2 + int(np.log(k))))
+            offs[s] = at
+            at += d.size
+            flat.append(d.ravel())
+        flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0), dtype=np.float64)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.float64)
+        seeds = np.empty(int(ks.sum()), dtype=np.uint32)
+        out = {"labels": np.empty((S, n), dtype=np.uint32), "sil": np.empty((S, n), dtype=np.float64) if silhouettes else None,
+               "status": np.empty(S, dtype=np.uint32), "n_iter": np.empty(S, dtype=np.int32),
+               "min_gap": np.empty(S, dtype=np.float64), "seed_margin": np.empty(S, dtype=np.float64)}
+        rc = self.ctx.lib.phk_sweep_run(self.ctx.handle, self.handle, S, ptr(ks), ptr(first), ptr(flat), ptr(offs), float(tol),
+                                        int(max_iter), int(chunk), int(pair_budget), ptr(out["labels"]), ptr(seeds),
+                                        ptr(out["sil"]) if silhouettes else None, ptr(out["status"]), ptr(out["n_iter"]),
+                                        ptr(out["min_gap"]), ptr(out["seed_margin"]))
+        if rc == PHK_ERR_NAN:
+            raise ValueError("Input contains NaN.")
+        if rc == PHK_ERR_ARG:
+            raise ValueError(last_error())
+        check(rc)
+        out["seeds"] = np.split(seeds, np.cumsum(ks.astype(np.int64))[:-1]) if S else []
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx.lib.phk_sweep_destroy(self.ctx.handle, self.handle)
         self.handle = None
 
     def __del__(self):

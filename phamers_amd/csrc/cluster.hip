@@ -291,10 +291,11 @@ static uint32_t cl_groups(phk_ctx *ctx, uint64_t qblocks, uint64_t tiles) {
     return (uint32_t)(g ? g : 1);
 }
 
-extern "C" int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const uint32_t *labels, uint32_t n_labels,
-                               double *out) {
+// X = the rows on the host, or NULL with d_rows = the same rows already on the device (checked for NaN by their owner)
+static int cl_silhouettes(phk_ctx *ctx, const double *X, const double *d_rows, uint64_t n, uint64_t D, const uint32_t *labels,
+                          uint32_t n_labels, double *out) {
     PHK_ENTER(ctx, "phk_silhouettes");
-    PHK_REQUIRE(X && labels && out, "phk_silhouettes: NULL pointer");
+    PHK_REQUIRE((X || d_rows) && labels && out, "phk_silhouettes: NULL pointer");
     PHK_REQUIRE(D >= 1 && n < (1ull << 31), "phk_silhouettes: bad shape (%llu x %llu)", (unsigned long long)n,
                 (unsigned long long)D);
     PHK_REQUIRE(n_labels >= 2 && (uint64_t)n_labels <= n - 1 && n >= 3,
@@ -341,7 +342,12 @@ extern "C" int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64
     const uint64_t meta = (o_cf + nch + 255) & ~255ull;
     double *d_x;
     void *d_meta;
-    PHK_TRY(cl_upload(ctx, "phk_silhouettes", X, n, D, meta + B * K * sizeof(double) + n * sizeof(double), &d_x, &d_meta));
+    if (X) {
+        PHK_TRY(cl_upload(ctx, "phk_silhouettes", X, n, D, meta + B * K * sizeof(double) + n * sizeof(double), &d_x, &d_meta));
+    } else {
+        PHK_TRY(phk_ws(ctx, WS_WIDE, meta + B * K * sizeof(double) + n * sizeof(double), &d_meta));
+        d_x = const_cast<double *>(d_rows);
+    }
     char *mb = (char *)d_meta;
     double *d_sums = (double *)(mb + meta), *d_out = d_sums + B * K;
     PHK_HIP(hipMemcpyAsync(mb + o_perm, perm.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -368,6 +374,17 @@ extern "C" int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64
                        d_sums, (const uint32_t *)(mb + o_lab), (const uint32_t *)(mb + o_size), q0, nq, K, d_out));
     }
     return phk_copy_to_host(ctx, out, d_out, n * sizeof(double));
+}
+
+extern "C" int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const uint32_t *labels, uint32_t n_labels,
+                               double *out) {
+    PHK_REQUIRE(X, "phk_silhouettes: NULL pointer");
+    return cl_silhouettes(ctx, X, nullptr, n, D, labels, n_labels, out);
+}
+
+int phk_silhouettes_resident(phk_ctx *ctx, const double *d_rows, uint64_t n, uint64_t D, const uint32_t *labels, uint32_t n_labels,
+                             double *out) {
+    return cl_silhouettes(ctx, nullptr, d_rows, n, D, labels, n_labels, out);
 }
 
 // the largest double t with sqrt(t) <= eps (sqrt correctly rounded and monotone): s <= t  <=>  sqrt(s) <= eps

@@ -298,6 +298,9 @@ int phk_launch_synth(phk_ctx *ctx, uint64_t seed, uint64_t first, uint64_t n, ui
 int phk_launch_synth_ragged(phk_ctx *ctx, uint64_t seed, uint64_t first, uint64_t n, const uint64_t *d_offsets,
                             uint64_t total_bases, uint32_t gc_spread_permille, uint32_t invalid_ppm, uint32_t *d_packed,
                             uint32_t *d_mask);
+// cluster.hip: phk_silhouettes on rows that are on the device already (d_rows[n][D], free of NaN)
+int phk_silhouettes_resident(phk_ctx *ctx, const double *d_rows, uint64_t n, uint64_t D, const uint32_t *labels, uint32_t n_labels,
+                             double *out);
 // score.hip
 struct phk_model;
 int phk_score_rows(phk_ctx *ctx, const phk_model *m, const double *d_Q, const uint32_t *d_counts,

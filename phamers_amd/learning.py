@@ -11,6 +11,7 @@ learning.py -- drop-in for the hot-path helpers of PhaMers' scripts/learning.py.
     silhouettes(data, assignment)                 scripts/learning.py:84-92     -> GPU (float64 cluster distance sums)
     cluster_silhouettes(data, assignment, c)      scripts/learning.py:95-104    -> GPU silhouettes of one cluster's members
     place_contigs(reference, contigs, k)          scripts/analysis.py:771-776   -> GPU, all contigs as one batch (phk_placement_run)
+    kmeans_sweep(data, k_values, seeds)           scripts/cluster.py:38-47      -> GPU, all (k, seed) fits as one batch (phk_sweep_run)
     silhouette_score(data, labels)                (sklearn.metrics name)        -> mean of the GPU silhouettes
     cluster_deviations(data, assignment)          scripts/learning.py:31-44     -> NumPy (O(n D))
     sort_assignment_by_size(assignment, ...)      scripts/learning.py:166-182   -> NumPy
@@ -283,6 +284,83 @@ def place_contigs(reference, contigs, k_clusters=86, _chunk=0, _details=None):
         cluster = int(labels[-1])
         records.append({"labels": labels, "cluster": cluster, "members": np.flatnonzero(labels[:-1] == cluster),
                         "silhouettes": np.asarray(sil), "route": "host" if host else "device"})
+    return records
+
+
+SWEEP_MAX_K = 2981   # from here on 2 + int(ln k) exceeds the ten seeding trials per centre the device kernels are built for
+
+
+def _kmeans_seeded(data, k, seed):
+    """(labels, sweeps) of ``KMeans(n_clusters=k, random_state=seed).fit(data)`` on the single-problem paths: ``kmeans``'s
+    routes (host seeding + device Lloyd, else the host fit) for any seed -- ``kmeans`` itself is pinned to kmeans_seed."""
+    import os
+    if os.environ.get("PHAMERS_KMEANS", "device") != "sklearn":
+        got = kmeans_reference_on_device(data, k, seed=seed)
+        if got is not None:
+            return got
+    from sklearn.cluster import KMeans
+    fit = KMeans(n_clusters=k, random_state=seed).fit(data)
+    return np.asarray(fit.labels_).astype(np.int32), int(fit.n_iter_)
+
+
+def _silhouettes_of(data, labels):
+    return silhouettes(data, labels)   # (kmeans_sweep has an argument of that name)
+
+
+def kmeans_sweep(data, k_values, seeds=None, silhouettes=True, _chunk=0, _details=None, _pair_budget=-1):
+    """One k-means fit per (k, seed) of ``k_values`` x ``seeds`` (k outermost; ``seeds=None``: the reference's kmeans_seed)
+    on the same rows, and the silhouettes of every fit -- the work of scripts/cluster.py:38-47 -- as ONE batched device
+    call (phk_sweep_run): the rows go up once, seeding included, and all problems share one pass over the pairs.  Returns
+    one dict per problem: ``k``, ``seed``, ``labels`` (n,) int32 equal to ``KMeans(n_clusters=k, random_state=seed)
+    .fit(data).labels_``, ``n_iter``, ``silhouettes`` (n,) (None without ``silhouettes``), ``silhouette`` = their np.mean,
+    ``route``: 'device', or 'host' where the device declined (a seeding decision within SEED_MIN_MARGIN of a tie, an
+    assignment within KMEANS_MIN_GAP of one, an empty cluster), for k >= SWEEP_MAX_K and under PHAMERS_KMEANS=sklearn: such
+    a problem goes through the single-problem paths (_kmeans_seeded + silhouettes): the same results, only slower.
+    PHAMERS_KMEANS=gpu (other seeds than the reference's) is not supported here."""
+    import os
+    mode = os.environ.get("PHAMERS_KMEANS", "device")
+    if mode == "gpu":
+        raise NotImplementedError("kmeans_sweep reproduces the reference's seeds; PHAMERS_KMEANS=gpu selects others")
+    X = _check_rows(data)
+    n = X.shape[0]
+    problems = [(int(k), int(seed)) for k in np.asarray(k_values).ravel().tolist()
+                for seed in ([kmeans_seed] if seeds is None else list(seeds))]
+    for k, _ in problems:
+        if k < 1:
+            raise ValueError("The 'n_clusters' parameter of KMeans must be an int in the range [1, inf). Got %d instead." % k)
+        if k > n:
+            raise ValueError("n_samples=%d should be >= n_clusters=%d." % (n, k))
+        if silhouettes and not 2 <= k <= n - 1:
+            raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % k)
+    on_device = [i for i, (k, _) in enumerate(problems) if mode != "sklearn" and k < SWEEP_MAX_K]
+    out = None
+    if on_device:
+        drawn = [placement_draws(n, problems[i][0], problems[i][1]) for i in on_device]
+        ctx = _lib.get_context()
+        sw = _lib.Sweep(ctx, X)
+        try:
+            out = sw.run([problems[i][0] for i in on_device], [d[0] for d in drawn], [d[1] for d in drawn],
+                         silhouettes=silhouettes, chunk=_chunk, pair_budget=_pair_budget)
+        finally:
+            sw.close()
+        if _details is not None:
+            _details.update(out)
+            _details["problems"] = [problems[i] for i in on_device]
+    where = {i: j for j, i in enumerate(on_device)}
+    records = []
+    for i, (k, seed) in enumerate(problems):
+        j = where.get(i)
+        host = j is None or bool(out["status"][j]) or not (out["seed_margin"][j] >= SEED_MIN_MARGIN) \
+            or not (out["min_gap"][j] >= KMEANS_MIN_GAP)
+        if host:
+            labels, n_iter = _kmeans_seeded(X, k, seed)
+            sil = _silhouettes_of(X, labels) if silhouettes else None
+        else:
+            labels, n_iter = out["labels"][j].astype(np.int32), int(out["n_iter"][j])
+            sil = out["sil"][j].copy() if silhouettes else None
+        records.append({"k": k, "seed": seed, "labels": np.asarray(labels).astype(np.int32), "n_iter": int(n_iter),
+                        "silhouettes": sil, "silhouette": None if sil is None else float(np.mean(sil)),
+                        "route": "host" if host else "device"})
     return records
 
 
