@@ -226,6 +226,21 @@ int phk_batch_from_fasta_part(phk_ctx *ctx, const char *path, uint32_t part, uin
  * PHK_ERR_UNSUPPORTED: D is not 4^k with k <= PHK_MAX_K, an entry is negative or >= 2^32, or a row's sum is >= 2^32 (a
  * batch keeps its row sums as uint32). */
 int phk_batch_from_counts(phk_ctx *ctx, const int64_t *counts, uint64_t n, uint64_t D, phk_batch **out);
+/* Sliding windows: the rows of the batch are the windows [j step, j step + window) of every sequence, j = 0 ..
+ * (L - window) / step, sequence-major and ordered by start; a sequence shorter than `window` gives no row.  Row j holds
+ * what a count of seq[j step : j step + window] gives (same bins, k-mers touching an invalid base skipped).  Every base
+ * goes up and is packed once; the kernels derive a window from its predecessor (step k-mers enter, step leave).
+ * `segment` = windows per work unit (the first window of a unit is counted in full), 0 = chosen by the launch: the
+ * result does not depend on it.  The batch stands as one from phk_batch_from_ascii (total_bases = rows * window).
+ * PHK_ERR_ARG: window < k, step < 1, a NULL pointer, or no window at all; PHK_ERR_UNSUPPORTED: k > PHK_MAX_K. */
+int phk_batch_windows_from_ascii(phk_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n, int k,
+                                 const char *symbols4, uint64_t window, uint64_t step, uint32_t segment,
+                                 phk_batch **out);
+int phk_batch_windows_from_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const char *symbols4,
+                                 uint64_t window, uint64_t step, uint32_t segment, phk_batch **out);
+/* *segments = the work units one window launch at this k takes in a single pass of its grid (more are taken by the
+ * kernels' grid-stride loops): what a test has to exceed to reach those loops. */
+int phk_windows_grid_pass(int k, uint64_t *segments);
 int phk_batch_shape(const phk_batch *b, uint64_t *n, uint64_t *D, uint64_t *total_bases, int *any_invalid);
 /* borrowed device pointers (valid until phk_batch_free): counts[n][D] uint32, row sums[n] uint32 */
 int phk_batch_device_ptrs(const phk_batch *b, const uint32_t **d_counts, const uint32_t **d_rowsums);

@@ -56,6 +56,9 @@ SIGNATURES = {
     "phk_batch_from_ascii": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_char_p, P(c_void_p)]),
     "phk_batch_from_fasta": (c_int, [c_void_p, c_void_p, c_int, c_char_p, P(c_void_p)]),
     "phk_batch_from_counts": (c_int, [c_void_p, c_void_p, c_u64, c_u64, P(c_void_p)]),
+    "phk_batch_windows_from_ascii": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_char_p, c_u64, c_u64, c_u32, P(c_void_p)]),
+    "phk_batch_windows_from_fasta": (c_int, [c_void_p, c_void_p, c_int, c_char_p, c_u64, c_u64, c_u32, P(c_void_p)]),
+    "phk_windows_grid_pass": (c_int, [c_int, P(c_u64)]),
     "phk_batch_from_fasta_file": (c_int, [c_void_p, c_char_p, c_int, c_char_p, c_int, P(c_void_p), P(c_void_p)]),
     "phk_batch_from_fasta_part": (c_int, [c_void_p, c_char_p, c_u32, c_u32, c_int, c_char_p, c_int, P(c_void_p), P(c_void_p)]),
     "phk_batch_shape": (c_int, [c_void_p, P(c_u64), P(c_u64), P(c_u64), P(c_int)]),
@@ -626,6 +629,28 @@ class Batch(object):
         return cls(ctx, h)
 
     @classmethod
+    def windows_from_fasta(cls, ctx, fasta, kmer_length, window, step, symbols=b"ATGC", segment=0):
+        """The sliding windows of a parsed file's records as rows (phk_batch_windows_from_fasta)."""
+        h = ctypes.c_void_p()
+        check(ctx.lib.phk_batch_windows_from_fasta(ctx.handle, fasta.handle, int(kmer_length), symbols, int(window), int(step),
+                                                   int(segment), ctypes.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def windows_from_sequences(cls, ctx, sequences, kmer_length, window, step, symbols=b"ATGC", segment=0):
+        """The sliding windows [j step, j step + window) of every sequence as rows (phk_batch_windows_from_ascii): every base
+        goes up once whatever the overlap.  ``segment`` = windows per work unit, 0 = chosen by the launch."""
+        raw = [s.encode("latin-1", "replace") for s in sequences]
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        if raw:
+            offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
+        h = ctypes.c_void_p()
+        check(ctx.lib.phk_batch_windows_from_ascii(ctx.handle, ptr(np.ascontiguousarray(bases)), ptr(offsets), len(raw),
+                                                   int(kmer_length), symbols, int(window), int(step), int(segment), ctypes.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
     def from_counts(cls, ctx, counts):
         """A batch from an integer count matrix (n, 4^k) on the host -- the features cache of an earlier run (phk_batch_from_counts).
         None when the matrix is not such a one (another width, negative entries, an entry or a row sum of 2^32 or more): the caller keeps the float rows."""
@@ -649,6 +674,15 @@ class Batch(object):
         """uint32 (n, 4^k) on the host, as the device holds them (what the features-cache writer takes)."""
         out = np.zeros((self.n, self.D), dtype=np.uint32)
         check(self.ctx.lib.phk_batch_counts_u32(self.ctx.handle, self.handle, ptr(out)))
+        return out
+
+    def row_sums(self):
+        """uint32 (n,): the counted k-mers of every row (0 = a row that normalises to NaN)."""
+        out = np.zeros(self.n, dtype=np.uint32)
+        if self.n:
+            d = ctypes.c_void_p()
+            check(self.ctx.lib.phk_batch_device_ptrs(self.handle, None, ctypes.byref(d)))
+            check(self.ctx.lib.phk_memcpy_d2h(self.ctx.handle, ptr(out), d, out.nbytes))
         return out
 
     def normalized(self):

@@ -39,7 +39,8 @@ static void batch_release(phk_batch *b) {
 // supplies the bytes: fill(o, len, dst) writes bases [o, o + len) of the concatenated sequences to dst; it is called for
 // consecutive chunks in increasing order, from this thread.
 int phk_batch_build(phk_ctx *ctx, const char *bases, const std::function<void(uint64_t, uint64_t, char *)> *fill,
-                    const uint64_t *offsets, uint64_t n, int k, const char *symbols4, phk_batch **out) {
+                    const uint64_t *offsets, uint64_t n, int k, const char *symbols4, phk_batch **out,
+                    const PhkWindowSpec *windows) {
     PHK_ENTER(ctx, "phk_batch_build");   // (every caller's device work starts here: phk_batch_from_ascii, _from_fasta, _from_fasta_file)
     PHK_REQUIRE(out, "phk_batch_from_ascii: NULL out");
     PHK_REQUIRE(k >= 1, "phk_batch_from_ascii: k must be >= 1 (got %d)", k);
@@ -57,13 +58,18 @@ int phk_batch_build(phk_ctx *ctx, const char *bases, const std::function<void(ui
     }
     const uint64_t T = n ? offsets[n] : 0;
     PHK_REQUIRE(T == 0 || bases || fill, "phk_batch_from_ascii: NULL bases");
+    // rows of the batch: the sequences, or (windows.hip) their sliding windows
+    const uint64_t rows = windows ? phk_windows_rows(offsets, n, windows->window, windows->step) : n;
+    PHK_REQUIRE(!windows || rows > 0, "phk_batch_windows: no sequence is as long as the window of %llu bases",
+                (unsigned long long)windows->window);
     phk_batch *b = new phk_batch();
-    b->n = n;
+    b->n = rows;
     b->k = k;
     b->D = phk_pow4(k);
-    b->T = T;
-    b->len.resize(n);
-    for (uint64_t c = 0; c < n; ++c) b->len[c] = offsets[c + 1] - offsets[c];
+    b->T = windows ? rows * windows->window : T;
+    b->len.resize(rows);
+    if (windows) b->len.assign(rows, windows->window);
+    else for (uint64_t c = 0; c < n; ++c) b->len[c] = offsets[c + 1] - offsets[c];
     if (n == 0) {
         *out = b;
         return PHK_OK;
@@ -73,9 +79,9 @@ int phk_batch_build(phk_ctx *ctx, const char *bases, const std::function<void(ui
     hipEvent_t copied[2] = {nullptr, nullptr}, packed_ev[2] = {nullptr, nullptr};
     void *d_chunk[2] = {nullptr, nullptr};
     auto body = [&]() -> int {
-        if (hipMalloc(&b->d_counts, n * b->D * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&b->d_nwin, n * sizeof(uint32_t)) != hipSuccess) {
-            phk_set_error("phk_batch: cannot allocate %llu x %llu counts on the device", (unsigned long long)n,
+        if (hipMalloc(&b->d_counts, rows * b->D * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc(&b->d_nwin, rows * sizeof(uint32_t)) != hipSuccess) {
+            phk_set_error("phk_batch: cannot allocate %llu x %llu counts on the device", (unsigned long long)rows,
                           (unsigned long long)b->D);
             return PHK_ERR_NOMEM;
         }
@@ -133,8 +139,12 @@ int phk_batch_build(phk_ctx *ctx, const char *bases, const std::function<void(ui
         if (nchunks) PHK_HIP(hipMemcpyAsync(flags.data(), d_flags, nchunks * 4, hipMemcpyDeviceToHost, ctx->stream));
         PHK_HIP(hipStreamSynchronize(ctx->stream));
         for (uint32_t f : flags) b->any_invalid = b->any_invalid || f != 0;
-        PHK_TRY(phk_launch_count(ctx, (const uint32_t *)d_packed, b->any_invalid ? (const uint32_t *)d_mask : nullptr, T,
-                                 (const uint64_t *)d_off, n, k, b->d_counts, b->d_nwin));
+        if (windows)
+            PHK_TRY(phk_launch_windows(ctx, (const uint32_t *)d_packed, b->any_invalid ? (const uint32_t *)d_mask : nullptr, T, offsets,
+                                       n, k, windows->window, windows->step, windows->segment, b->d_counts, b->d_nwin));
+        else
+            PHK_TRY(phk_launch_count(ctx, (const uint32_t *)d_packed, b->any_invalid ? (const uint32_t *)d_mask : nullptr, T,
+                                     (const uint64_t *)d_off, n, k, b->d_counts, b->d_nwin));
         PHK_HIP(hipStreamSynchronize(ctx->stream));
         return PHK_OK;
     };

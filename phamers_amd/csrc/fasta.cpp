@@ -1008,6 +1008,19 @@ extern "C" int phk_batch_from_fasta(phk_ctx *ctx, const phk_fasta *f, int k, con
     return phk_batch_from_ascii(ctx, f->bases.data(), f->offsets.data(), f->offsets.size() - 1, k, symbols4, out);
 }
 
+extern "C" int phk_batch_windows_from_ascii(phk_ctx *ctx, const char *bases, const uint64_t *offsets, uint64_t n, int k,
+                                            const char *symbols4, uint64_t window, uint64_t step, uint32_t segment,
+                                            phk_batch **out);
+
+// the sliding windows of a parsed file's records as the rows of a batch (windows.hip)
+extern "C" int phk_batch_windows_from_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const char *symbols4, uint64_t window,
+                                            uint64_t step, uint32_t segment, phk_batch **out) {
+    PHK_REQUIRE(ctx && f, "phk_batch_windows_from_fasta: NULL");
+    PHK_REQUIRE(f->bases.data() || f->offsets.back() == 0, "phk_batch_windows_from_fasta: the file was only indexed (phk_fasta_index)");
+    return phk_batch_windows_from_ascii(ctx, f->bases.data(), f->offsets.data(), f->offsets.size() - 1, k, symbols4, window, step,
+                                        segment, out);
+}
+
 extern "C" int phk_count_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const char *symbols4, int64_t *counts) {
     PHK_REQUIRE(ctx && f, "phk_count_fasta: NULL");
     PHK_REQUIRE(f->bases.data() || f->offsets.back() == 0, "phk_count_fasta: the file was only indexed (phk_fasta_index)");

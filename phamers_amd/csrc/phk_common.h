@@ -178,8 +178,15 @@ int phk_ws(phk_ctx *ctx, int slot, uint64_t bytes, void **out);
 // a plain stream-ordered copy.  phk_copy_to_host returns with the data in place; phk_copy_to_device is stream ordered.
 struct phk_batch;
 // (batch.hip) the sequence bytes of a batch -> device, packed and counted; see there
+// `windows` (windows.hip): the rows of the batch are not the sequences but their sliding windows [j step, j step + window),
+// sequence-major by start, counted by phk_launch_windows instead of phk_launch_count; no window at all is PHK_ERR_ARG.
+struct PhkWindowSpec {
+    uint64_t window, step;
+    uint32_t segment;   // windows per work unit, 0 = the launch chooses
+};
 int phk_batch_build(phk_ctx *ctx, const char *bases, const std::function<void(uint64_t, uint64_t, char *)> *fill,
-                    const uint64_t *offsets, uint64_t n, int k, const char *symbols4, phk_batch **out);
+                    const uint64_t *offsets, uint64_t n, int k, const char *symbols4, phk_batch **out,
+                    const PhkWindowSpec *windows = nullptr);
 // (batch.hip) the same from the RAW bytes of a FASTA file (title lines, line ends and all) + one layout entry per record:
 // the bytes go up as they are and the device drops what is not sequence (phk_deline_pack_kernel, count.hip).
 // phk_raw_to_device puts the file's bytes into the context's WS_ASCII workspace (staged copies; it may run on a thread of its
@@ -291,6 +298,10 @@ int phk_launch_permute_columns(phk_ctx *ctx, const int64_t *d_in, uint64_t n, ui
                                int64_t *d_out);
 int phk_launch_check_counts(phk_ctx *ctx, const uint32_t *d_counts, const uint32_t *d_other, uint64_t n, uint64_t D,
                             uint64_t expected_rowsum, uint64_t *d_result);
+// windows.hip: rows = the windows of every sequence (`offsets` is the HOST array); phk_windows_rows counts them
+uint64_t phk_windows_rows(const uint64_t *offsets, uint64_t n, uint64_t window, uint64_t step);
+int phk_launch_windows(phk_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t T, const uint64_t *offsets,
+                       uint64_t n, int k, uint64_t window, uint64_t step, uint32_t segment, uint32_t *d_counts, uint32_t *d_nwin);
 // synth.hip
 int phk_launch_synth(phk_ctx *ctx, uint64_t seed, uint64_t first, uint64_t n, uint64_t L,
                      uint32_t invalid_ppm, uint32_t *d_packed, uint32_t *d_mask,

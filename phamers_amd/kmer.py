@@ -166,6 +166,70 @@ def count_cuts(fasta_file_or_sequences, kmer_length, cut_size, symbols=DNA):
             fasta.close()
 
 
+def window_plan(lengths, window, step):
+    """The sliding windows of ``count_windows`` for sequences of the given lengths: (owner, start) as int64 arrays in row
+    order.  Sequence r of length L >= ``window`` has the windows starting at ``j * step``, j = 0 .. (L - window) // step;
+    rows are sequence-major and ordered by start; a shorter sequence has none."""
+    window, step = int(window), int(step)
+    if window < 1:
+        raise ValueError("window must be >= 1, got %r" % (window,))
+    if step < 1:
+        raise ValueError("step must be >= 1, got %r" % (step,))
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    per = np.where(lengths >= window, (lengths - window) // step + 1, 0)
+    first = np.concatenate(([0], np.cumsum(per))).astype(np.int64)
+    owner = np.repeat(np.arange(len(lengths), dtype=np.int64), per)
+    start = (np.arange(first[-1], dtype=np.int64) - first[owner]) * step
+    return owner, start
+
+
+def _windows_batch(fasta_file_or_sequences, kmer_length, window, step, symbols=DNA, _segment=0):
+    """(record ids, lengths, device batch or None) of ``count_windows``: the windows of ``window_plan`` as the rows of one
+    device-resident batch (phk_batch_windows_from_ascii / _from_fasta); None when there is no window at all.  The caller
+    closes the batch."""
+    sym = _check_symbols(symbols)
+    k, window, step = int(kmer_length), int(window), int(step)
+    if window < k:
+        raise ValueError("window (%d) must be at least kmer_length (%d)" % (window, k))
+    if step < 1:
+        raise ValueError("step must be >= 1, got %r" % (step,))
+    ctx = _lib.get_context()
+    if isinstance(fasta_file_or_sequences, str):
+        fasta = _lib.Fasta(fasta_file_or_sequences)
+        try:
+            record_ids, lengths = fasta.ids(), fasta.lengths()
+            if not (lengths >= window).any():
+                return record_ids, lengths, None
+            return record_ids, lengths, _lib.Batch.windows_from_fasta(ctx, fasta, k, window, step, sym, _segment)
+        finally:
+            fasta.close()
+    sequences = list(fasta_file_or_sequences)
+    record_ids = [str(i) for i in range(len(sequences))]
+    lengths = np.array([len(s) for s in sequences], dtype=np.int64)
+    if not (lengths >= window).any():
+        return record_ids, lengths, None
+    return record_ids, lengths, _lib.Batch.windows_from_sequences(ctx, sequences, k, window, step, sym, _segment)
+
+
+def count_windows(fasta_file_or_sequences, kmer_length, window, step, symbols=DNA, _segment=0):
+    """k-mer counts of the overlapping windows of ``window`` bases every ``step`` bases along every sequence
+    (``window_plan``): (ids, counts (n_windows, 4^k) int64), id ``<record id>_<0-based start>``; row j of a sequence is
+    what ``count_string(seq[j * step : j * step + window], k)`` returns.  Input kinds, alphabet and k rules are those of
+    ``count_cuts``.  Every base goes to the device once, whatever the overlap: the kernel adds the k-mers entering a
+    window and subtracts those leaving it.  ``_segment``: windows per work unit of that kernel
+    (0 = chosen by the launch; the result does not depend on it).  ValueError for ``window < kmer_length`` or
+    ``step < 1``."""
+    record_ids, lengths, batch = _windows_batch(fasta_file_or_sequences, kmer_length, window, step, symbols, _segment)
+    owner, start = window_plan(lengths, window, step)
+    ids = ["%s_%d" % (record_ids[r], s) for r, s in zip(owner, start)]
+    if batch is None:
+        return ids, np.zeros((0, 4 ** int(kmer_length)), dtype=np.int64)
+    try:
+        return ids, batch.counts()
+    finally:
+        batch.close()
+
+
 def count_file(input_file, kmer_length, symbols=DNA, normalize=False):
     """Counts k-mers of every record of a FASTA file (scripts/kmer.py:114-140).  Returns
     (ids, counts): ids parsed by the reference's header rules (scripts/id_parser.py:89-100),
