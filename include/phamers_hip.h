@@ -125,6 +125,10 @@ int phk_normalize_f64(phk_ctx *ctx, const double *rows, uint64_t n, uint64_t D, 
  * host facade). */
 int phk_permute_columns_i64(phk_ctx *ctx, const int64_t *rows, uint64_t n, uint64_t D, const uint32_t *perm,
                             int64_t *out);
+/* Strand-symmetric counts of a host matrix: out[r][c] = counts[r][c] + counts[r][rc(c)], rc(c) = the column of the
+ * reverse-complement k-mer (the k base-4 digits of c reversed, bit 0 of each flipped: see phk_batch_fold_strands).  64-bit
+ * sums: no limit on the entries.  PHK_ERR_UNSUPPORTED when D is not 4^k with 1 <= k <= PHK_MAX_K. */
+int phk_fold_strands_i64(phk_ctx *ctx, const int64_t *counts, uint64_t n, uint64_t D, int64_t *out);
 
 /* ---- host API: FASTA ingest --------------------------------------------------------- */
 /* One multi-threaded pass over a FASTA file (plain, or gzip when the name ends in ".gz") replacing
@@ -260,6 +264,23 @@ int phk_batch_column_sums(phk_ctx *ctx, const phk_batch *b, int64_t *sums);
  * out[r][j] = counts[r][table[j]] (table: 4^k host entries, each < 4^k; the reference's tables are not permutations, so
  * the row sums are recomputed on the device).  PHK_ERR_UNSUPPORTED, and no batch, when a gathered row's sum is >= 2^32. */
 int phk_batch_gather_columns(phk_ctx *ctx, const phk_batch *b, const uint32_t *table, phk_batch **out);
+/* Folds the two strands of every row, IN PLACE: counts[r][c] += counts[r][rc(c)] for the resident rows of a batch from
+ * any producer, and every stored row sum doubled.  rc(c) is the column of the reverse-complement k-mer: the k base-4
+ * digits of c in reverse order with the digits paired 0 <-> 1, 2 <-> 3 -- A <-> T(U), G <-> C under the symbol orders
+ * "ATGC" (DNA) and "AUGC" (RNA); a batch counted over another order is paired by digit all the same.  The result is what
+ * counting every sequence and its reverse complement gives, characters outside the symbols included, so a sequence and
+ * its reverse complement fold to the same row.  Palindromic k-mers (rc(c) == c, 4^(k/2) of them at even k) are doubled.
+ * The batch remembers that it is folded (phk_batch_strands; phk_batch_select and phk_batch_gather_columns hand the mark
+ * on): a second fold is PHK_ERR_ARG and changes nothing.  Every row sum is checked on the device before anything is
+ * written: with one of 2^31 or more the call returns PHK_ERR_UNSUPPORTED (the text has the number of such rows) and the
+ * batch is untouched; below that no entry can overflow either (an entry and its partner are both part of the row sum).
+ * n == 0 is PHK_OK. */
+int phk_batch_fold_strands(phk_ctx *ctx, phk_batch *b);
+/* *folded = 1 when the rows of the batch are folded (phk_batch_fold_strands), else 0 */
+int phk_batch_strands(const phk_batch *b, int *folded);
+/* *rows = the rows one launch of the fold kernel at this k takes in a single pass of its grid (more are taken by its
+ * grid-stride loop): what a test has to exceed to reach that loop. */
+int phk_fold_grid_pass(int k, uint64_t *rows);
 /* phamer_scorer.score_points (scripts/phamer.py:177-195) on a batch: scores[n] float64 to the host.  PHK_ERR_NAN
  * when a row has no counted window (the reference's NaN row makes scikit-learn raise). */
 int phk_batch_score(phk_ctx *ctx, const phk_model *model, const phk_batch *b, int method, double *scores);

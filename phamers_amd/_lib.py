@@ -42,6 +42,7 @@ SIGNATURES = {
     "phk_normalize_i64": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_normalize_f64": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_permute_columns_i64": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p]),
+    "phk_fold_strands_i64": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_fasta_read": (c_int, [c_char_p, c_int, P(c_void_p)]),
     "phk_fasta_index": (c_int, [c_char_p, c_int, P(c_void_p)]),
     "phk_fasta_read_range": (c_int, [c_char_p, c_u64, c_u64, c_int, P(c_void_p)]),
@@ -77,6 +78,9 @@ SIGNATURES = {
     "phk_batch_select": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, P(c_void_p)]),
     "phk_batch_column_sums": (c_int, [c_void_p, c_void_p, c_void_p]),
     "phk_batch_gather_columns": (c_int, [c_void_p, c_void_p, c_void_p, P(c_void_p)]),
+    "phk_batch_fold_strands": (c_int, [c_void_p, c_void_p]),
+    "phk_batch_strands": (c_int, [c_void_p, P(c_int)]),
+    "phk_fold_grid_pass": (c_int, [c_int, P(c_u64)]),
     "phk_batch_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "phk_batch_free": (c_int, [c_void_p, c_void_p]),
     "phk_kmeans": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_u32, c_u64, c_int, c_void_p, c_void_p, P(c_int)]),
@@ -610,6 +614,13 @@ class Batch(object):
         check(ctx.lib.phk_batch_shape(handle, ctypes.byref(n), ctypes.byref(D), ctypes.byref(T), ctypes.byref(inv)))
         self.n, self.D, self.total_bases, self.any_invalid = n.value, D.value, T.value, bool(inv.value)
 
+    @property
+    def folded(self):
+        """True once the rows hold both strands (``fold_strands``); a selection and a column gather inherit it."""
+        f = ctypes.c_int()
+        check(self.ctx.lib.phk_batch_strands(self.handle, ctypes.byref(f)))
+        return bool(f.value)
+
     @classmethod
     def from_fasta(cls, ctx, fasta, kmer_length, symbols=b"ATGC"):
         h = ctypes.c_void_p()
@@ -712,6 +723,14 @@ class Batch(object):
         h = ctypes.c_void_p()
         check(self.ctx.lib.phk_batch_gather_columns(self.ctx.handle, self.handle, ptr(table), ctypes.byref(h)))
         return Batch(self.ctx, h)
+
+    def fold_strands(self):
+        """Adds to every resident row its reverse-complement permutation, in place (phk_batch_fold_strands): the counts of
+        the sequence and of its reverse complement together, row sums doubled.  Returns the batch.  PhkError with code
+        PHK_ERR_ARG when the batch is folded already, PHK_ERR_UNSUPPORTED (batch untouched) when a row's sum is 2^31 or
+        more."""
+        check(self.ctx.lib.phk_batch_fold_strands(self.ctx.handle, self.handle))
+        return self
 
     def score(self, model, method="combo"):
         out = np.empty(self.n, dtype=np.float64)

@@ -231,7 +231,7 @@ class cross_validator(object):
 def main(argv=None):
     """The reference's command line (scripts/cross_validate.py:240-307) without its plots: metrics.txt and scores.txt in the
     output directory, with -a also all_algorithms_auc.txt (``method<TAB>repr(auc)`` per line).  --seed and --kmeans are
-    this project's additions."""
+    this project's additions, and so is --both_strands."""
     import argparse
     from . import fileIO, kmer
     parser = argparse.ArgumentParser(description="This script is for doing N-fold cross validation of the Phamer scoring algorithm",
@@ -249,6 +249,8 @@ def main(argv=None):
     options_group.add_argument('-equal', '--equalize_reference', action='store_true', help="Use same number of reference data from each")
     options_group.add_argument('--seed', type=int, default=None, help="Seed of the fold assignment (unseeded as the reference when absent)")
     options_group.add_argument('--kmeans', default='sklearn', choices=('sklearn', 'gpu'), help="Per-fold k-means fit")
+    options_group.add_argument('--both_strands', action='store_true',
+                               help="Fold both feature files with their reverse complement before normalising")
     console_options_group = parser.add_argument_group("Console Options")
     console_options_group.add_argument('-v', '--verbose', action='store_true', default=False, help="Verbose output")
     console_options_group.add_argument('--debug', action='store_true', default=False, help="Debug console")
@@ -261,6 +263,9 @@ def main(argv=None):
     validator.seed, validator.kmeans = args.seed, args.kmeans
     validator.positive_ids, positive_data = fileIO.read_feature_file(args.positive_features_file)
     validator.negative_ids, negative_data = fileIO.read_feature_file(args.negative_features_file)
+    if args.both_strands:
+        from . import transform_kmers
+        positive_data, negative_data = transform_kmers.fold_strands(positive_data), transform_kmers.fold_strands(negative_data)
     validator.positive_data = kmer.normalize_counts(positive_data)
     validator.negative_data = kmer.normalize_counts(negative_data)
     validator.equalize_reference = args.equalize_reference

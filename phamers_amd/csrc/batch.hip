@@ -15,16 +15,6 @@
 #include "phk_common.h"
 #include "score_model.h"
 
-struct phk_batch {
-    uint64_t n = 0, D = 0, T = 0;
-    int k = 0;
-    uint32_t *d_counts = nullptr;   // [n][D]
-    uint32_t *d_nwin = nullptr;     // [n] row sums (= counted windows)
-    bool any_invalid = false;       // some base of the source batch was not one of the symbols (inherited by a selection:
-                                    // "may hold invalid bases", not re-derived per row)
-    std::vector<uint64_t> len;      // [n] bases per contig (host): what a selection's total_bases is summed from
-};
-
 #define BATCH_CHUNK PHK_STAGE_BYTES   // bases per upload chunk = one staging buffer (a multiple of 32: chunks pack independently)
 
 static void batch_release(phk_batch *b) {
@@ -462,6 +452,7 @@ extern "C" int phk_batch_select(phk_ctx *ctx, const phk_batch *b, const uint64_t
     s->k = b->k;
     s->D = b->D;
     s->any_invalid = b->any_invalid;
+    s->folded = b->folded;
     s->len.resize(m);
     for (uint64_t i = 0; i < m; ++i) {
         s->len[i] = b->len[rows[i]];
@@ -573,7 +564,7 @@ extern "C" int phk_batch_gather_columns(phk_ctx *ctx, const phk_batch *b, const 
     for (uint64_t j = 0; j < D; ++j)
         PHK_REQUIRE(table[j] < D, "phk_batch_gather_columns: index %u is out of bounds for %llu columns", table[j], (unsigned long long)D);
     phk_batch *s = new phk_batch();
-    s->n = b->n; s->k = b->k; s->D = D; s->T = b->T; s->any_invalid = b->any_invalid; s->len = b->len;
+    s->n = b->n; s->k = b->k; s->D = D; s->T = b->T; s->any_invalid = b->any_invalid; s->folded = b->folded; s->len = b->len;
     if (b->n == 0) {
         *out = s;
         return PHK_OK;

@@ -176,7 +176,18 @@ int phk_ws(phk_ctx *ctx, int slot, uint64_t bytes, void **out);
 // host threads copying on one side while the bus works on the other: an array handed to hipMemcpy as it is has its pages
 // pinned inside the runtime and costs 0.05 - 0.1 s per GB to free afterwards (tools/diag/fasta_free_time.py).  Below 128 MB
 // a plain stream-ordered copy.  phk_copy_to_host returns with the data in place; phk_copy_to_device is stream ordered.
-struct phk_batch;
+// (batch.hip, strands.hip) a device-resident batch: what the opaque phk_batch of the header is
+struct phk_batch {
+    uint64_t n = 0, D = 0, T = 0;
+    int k = 0;
+    uint32_t *d_counts = nullptr;   // [n][D]
+    uint32_t *d_nwin = nullptr;     // [n] row sums (= counted windows; twice that once folded)
+    bool any_invalid = false;       // some base of the source batch was not one of the symbols (inherited by a selection:
+                                    // "may hold invalid bases", not re-derived per row)
+    bool folded = false;            // the rows are strand-symmetric: phk_batch_fold_strands has run (inherited by a selection
+                                    // and by a column gather)
+    std::vector<uint64_t> len;      // [n] bases per contig (host): what a selection's total_bases is summed from
+};
 // (batch.hip) the sequence bytes of a batch -> device, packed and counted; see there
 // `windows` (windows.hip): the rows of the batch are not the sequences but their sliding windows [j step, j step + window),
 // sequence-major by start, counted by phk_launch_windows instead of phk_launch_count; no window at all is PHK_ERR_ARG.

@@ -12,6 +12,10 @@ Same names, argument meaning, defaults and return shapes as the reference:
     kmers(k, symbols=DNA), sequence_to_integers, get_kmer_index         scripts/kmer.py:183-251
     main()   `python -m phamers_amd.kmer <fasta | dir> <out.csv> -k K`     scripts/kmer.py:283-334
 
+Every counting function takes a trailing ``both_strands=False`` (this project's own; `--both_strands` on the command
+line): with it a row holds the k-mers of the sequence AND of its reverse complement -- the forward counts folded on the
+device (phk_batch_fold_strands) -- so a contig counts the same whichever strand it was written on.
+
 Scope notes: only 4-symbol alphabets run on the GPU (the reference's
 integer-replacement branch with DNA/RNA); other alphabets raise NotImplementedError --
 there is no CPU fallback in this package.
@@ -44,10 +48,25 @@ def _check_symbols(symbols):
         raise NotImplementedError("symbols must be single-byte characters")
 
 
-def _count_batch(sequences, kmer_length, symbols):
-    """n sequences -> (n, 4^k) int64 via phk_count_ascii (one upload, one launch chain)."""
+def _check_strands(symbols, both_strands):
+    """The reverse complement pairs the symbols by their digit (0 <-> 1, 2 <-> 3): A <-> T(U), G <-> C for DNA / RNA only."""
+    if both_strands and symbols not in (DNA, RNA):
+        raise NotImplementedError("both_strands needs symbols 'ATGC' (DNA) or 'AUGC' (RNA), whose order pairs each base "
+                                  "with its complement; got %r" % (symbols,))
+    return bool(both_strands)
+
+
+def _count_batch(sequences, kmer_length, symbols, both_strands=False):
+    """n sequences -> (n, 4^k) int64 via phk_count_ascii (one upload, one launch chain); ``both_strands``: through a
+    resident batch, folded on the device."""
     k = int(kmer_length)
     sym = _check_symbols(symbols)
+    if _check_strands(symbols, both_strands):
+        batch = _lib.Batch.from_sequences(_lib.get_context(), sequences, k, sym)
+        try:
+            return batch.fold_strands().counts()
+        finally:
+            batch.close()
     n = len(sequences)
     D = 4 ** k
     raw = [s.encode('latin-1', 'replace') for s in sequences]
@@ -62,13 +81,13 @@ def _count_batch(sequences, kmer_length, symbols):
     return out
 
 
-def count_string(sequence, kmer_length, symbols=DNA, normalize=False):
+def count_string(sequence, kmer_length, symbols=DNA, normalize=False, both_strands=False):
     """k-mer counting function (scripts/kmer.py:32-79): forward-strand, stride-1 windows;
     windows touching a character outside ``symbols`` (case-sensitive) are skipped; bin index
     has the first base as the most significant base-4 digit ('AAAT' -> 1).  Returns a 1-D
     int64 array of length 4^k, or float64 frequencies when ``normalize`` (all zeros stay
-    zeros)."""
-    counts = _count_batch([sequence], kmer_length, symbols)[0]
+    zeros).  ``both_strands``: the sequence and its reverse complement counted together (the row sum doubles)."""
+    counts = _count_batch([sequence], kmer_length, symbols, both_strands)[0]
     if normalize:
         counts = counts.astype(float)
         if np.sum(counts) > 0:
@@ -76,21 +95,21 @@ def count_string(sequence, kmer_length, symbols=DNA, normalize=False):
     return counts
 
 
-def count(data, kmer_length, symbols=DNA, normalize=False):
+def count(data, kmer_length, symbols=DNA, normalize=False, both_strands=False):
     """K-mer counting dispatcher (scripts/kmer.py:82-111): str -> 1-D; list of one string ->
     1-D; list of n strings -> (n, 4^k); anything else -> None (logged)."""
     if isinstance(data, list):
         if len(data) == 1:
-            return count(data[0], kmer_length, symbols=symbols, normalize=normalize)
+            return count(data[0], kmer_length, symbols=symbols, normalize=normalize, both_strands=both_strands)
         logger.info("Counting %d-mers in %d sequences..." % (kmer_length, len(data)))
-        kmer_count = _count_batch(data, kmer_length, symbols)
+        kmer_count = _count_batch(data, kmer_length, symbols, both_strands)
         if normalize:
             # per-row count_string(normalize=True): zero rows stay zero (scripts/kmer.py:77)
             sums = kmer_count.sum(axis=1)
             kmer_count = normalize_counts(kmer_count) if len(data) else kmer_count.astype(float)
             kmer_count[sums == 0] = 0.0
     elif isinstance(data, str):
-        kmer_count = count_string(data, kmer_length, symbols=symbols, normalize=normalize)
+        kmer_count = count_string(data, kmer_length, symbols=symbols, normalize=normalize, both_strands=both_strands)
     else:
         logger.info("Data was not str or list: %s\n%s ..." % (type(data), data.__str__()[:25]))
         kmer_count = None
@@ -119,16 +138,18 @@ def cut_plan(lengths, cut_size):
     return offsets, keep, owner_all[keep], index_all[keep]
 
 
-def count_cuts(fasta_file_or_sequences, kmer_length, cut_size, symbols=DNA):
+def count_cuts(fasta_file_or_sequences, kmer_length, cut_size, symbols=DNA, both_strands=False):
     """k-mer counts of the consecutive, non-overlapping pieces of exactly ``cut_size`` bases of every sequence (a shorter
     tail is dropped, a sequence shorter than ``cut_size`` gives no row): (ids, counts (pieces, 4^k) int64), id
     ``<record id>_<piece index>``.  ``fasta_file_or_sequences``: a FASTA path (record id = Bio.SeqIO's record.id, the
     first word of the title line: any FASTA file can be cut, whatever its headers look like) or a list of strings (record
     ids '0', '1', ...).  The cut rule is this project's own: the reference reads cut
     files (scripts/cut_validator.py) but ships nothing that writes them.  All pieces, tails included, are the contigs of
-    ONE device batch over the file's bases (phk_batch_from_ascii); phk_batch_select keeps the full-size ones."""
+    ONE device batch over the file's bases (phk_batch_from_ascii); phk_batch_select keeps the full-size ones.
+    ``both_strands``: every piece with its reverse complement (the kept rows are folded on the device)."""
     import ctypes
     sym = _check_symbols(symbols)
+    both_strands = _check_strands(symbols, both_strands)
     k = int(kmer_length)
     ctx = _lib.get_context()
     fasta = None
@@ -156,6 +177,8 @@ def count_cuts(fasta_file_or_sequences, kmer_length, cut_size, symbols=DNA):
         try:
             chosen = batch.select(keep)
             try:
+                if both_strands:
+                    chosen.fold_strands()
                 return ids, chosen.counts()
             finally:
                 chosen.close()
@@ -211,31 +234,36 @@ def _windows_batch(fasta_file_or_sequences, kmer_length, window, step, symbols=D
     return record_ids, lengths, _lib.Batch.windows_from_sequences(ctx, sequences, k, window, step, sym, _segment)
 
 
-def count_windows(fasta_file_or_sequences, kmer_length, window, step, symbols=DNA, _segment=0):
+def count_windows(fasta_file_or_sequences, kmer_length, window, step, symbols=DNA, _segment=0, both_strands=False):
     """k-mer counts of the overlapping windows of ``window`` bases every ``step`` bases along every sequence
     (``window_plan``): (ids, counts (n_windows, 4^k) int64), id ``<record id>_<0-based start>``; row j of a sequence is
     what ``count_string(seq[j * step : j * step + window], k)`` returns.  Input kinds, alphabet and k rules are those of
     ``count_cuts``.  Every base goes to the device once, whatever the overlap: the kernel adds the k-mers entering a
     window and subtracts those leaving it.  ``_segment``: windows per work unit of that kernel
-    (0 = chosen by the launch; the result does not depend on it).  ValueError for ``window < kmer_length`` or
-    ``step < 1``."""
+    (0 = chosen by the launch; the result does not depend on it).  ``both_strands``: every window with its reverse
+    complement (the window rows are folded on the device).  ValueError for ``window < kmer_length`` or ``step < 1``."""
+    both_strands = _check_strands(symbols, both_strands)
     record_ids, lengths, batch = _windows_batch(fasta_file_or_sequences, kmer_length, window, step, symbols, _segment)
     owner, start = window_plan(lengths, window, step)
     ids = ["%s_%d" % (record_ids[r], s) for r, s in zip(owner, start)]
     if batch is None:
         return ids, np.zeros((0, 4 ** int(kmer_length)), dtype=np.int64)
     try:
+        if both_strands:
+            batch.fold_strands()
         return ids, batch.counts()
     finally:
         batch.close()
 
 
-def count_file(input_file, kmer_length, symbols=DNA, normalize=False):
+def count_file(input_file, kmer_length, symbols=DNA, normalize=False, both_strands=False):
     """Counts k-mers of every record of a FASTA file (scripts/kmer.py:114-140).  Returns
     (ids, counts): ids parsed by the reference's header rules (scripts/id_parser.py:89-100),
     counts (n, 4^k).  An unreadable file gives (None, None).  The file is parsed once by the
-    native multi-threaded reader (phk_fasta_read; plain or .gz) and counted on the GPU."""
+    native multi-threaded reader (phk_fasta_read; plain or .gz) and counted on the GPU.  ``both_strands``: every record
+    with its reverse complement."""
     sym = _check_symbols(symbols)
+    both_strands = _check_strands(symbols, both_strands)
     try:
         fasta = _lib.Fasta(input_file)
     except IOError:
@@ -248,6 +276,8 @@ def count_file(input_file, kmer_length, symbols=DNA, normalize=False):
             # bases up once, counts down once (device-resident batch)
             batch = _lib.Batch.from_fasta(_lib.get_context(), fasta, kmer_length, sym)
             try:
+                if both_strands:
+                    batch.fold_strands()
                 got = batch.counts()
                 if normalize:
                     sums = got.sum(axis=1)
@@ -261,17 +291,19 @@ def count_file(input_file, kmer_length, symbols=DNA, normalize=False):
     return ids, counts
 
 
-def count_directory(directory, kmer_length, identifier='fna', symbols=DNA, sum_file=True, sample=0):
+def count_directory(directory, kmer_length, identifier='fna', symbols=DNA, sum_file=True, sample=0, both_strands=False):
     """Counts k-mers of all FASTA files of a directory whose base name contains `identifier`
     (scripts/kmer.py:143-181): one row per file -- with sum_file the column sums over the file's records,
     labelled with the id of its first record (how the reference matrix is regenerated from genome files) --
     as a float array like the reference's.  Unreadable / empty / all-zero files are skipped with a warning;
-    `sample` > 0 shuffles the files and stops after that many rows."""
+    `sample` > 0 shuffles the files and stops after that many rows.  ``both_strands``: every record with its reverse
+    complement (folded on the device before the column sums)."""
     selected_files = [os.path.join(directory, f) for f in os.listdir(directory) if identifier in os.path.basename(f)]
     if sample:
         random.shuffle(selected_files)
     ids, rows = [], []
     sym = _check_symbols(symbols)
+    both_strands = _check_strands(symbols, both_strands)
     for path in selected_files:
         # one file = one device-resident batch; with sum_file its column sums are reduced on the device
         # (phk_batch_column_sums) and only the 4^k sums come back -- the per-record count matrix never does
@@ -289,6 +321,8 @@ def count_directory(directory, kmer_length, identifier='fna', symbols=DNA, sum_f
         finally:
             fasta.close()
         try:
+            if both_strands:
+                batch.fold_strands()
             if sum_file:
                 file_counts = batch.column_sums()
             elif batch.n == 1:
@@ -386,6 +420,7 @@ def _parser():
     ap.add_argument('-k', '--kmer_length', type=int, default=4, help='Length of k-mer to count')
     ap.add_argument('-s', '--sample', type=int, help='Number of sequences to sample and count')
     ap.add_argument('-sym', '--symbols', type=str, default=DNA, help='Symbols to use in k-mer counting')
+    ap.add_argument('--both_strands', action='store_true', help='Count every sequence together with its reverse complement')
     ap.add_argument('-v', '--verbose', action='store_true', help='verbose output')
     ap.add_argument('--debug', action='store_true', help='Debug console')
     return ap
@@ -400,12 +435,13 @@ def main(argv=None):
     logger.setLevel(logging.DEBUG if args.debug else logging.INFO if args.verbose else logging.WARNING)
     logger.info("Counting k-mers...")
     if args.input_file and os.path.isfile(args.input_file):
-        ids, counts = count_file(args.input_file, args.kmer_length, symbols=args.symbols)
+        ids, counts = count_file(args.input_file, args.kmer_length, symbols=args.symbols, both_strands=args.both_strands)
         if ids is None:
             raise SystemExit(1)
     elif args.input_file and os.path.isdir(args.input_file):
         ids, counts = count_directory(args.input_file, args.kmer_length, symbols=args.symbols,
-                                      identifier=args.file_identifier, sample=args.sample or 0)
+                                      identifier=args.file_identifier, sample=args.sample or 0,
+                                      both_strands=args.both_strands)
     else:
         logger.error("%s was not an acceptable file or directory" % args.input_file)
         raise SystemExit(1)

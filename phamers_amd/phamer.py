@@ -16,6 +16,12 @@ reference meaning (the normalised float64 matrix) but is materialised from the d
 assigning it (as phamer.score_points and the cross-validation do) switches the object to host rows, which are
 scored through the float64-row entry point.
 
+``phamer_scorer.both_strands`` (this project's own; `--both_strands`): every count row -- the two reference matrices
+and the query contigs -- is folded with its reverse-complement permutation before it is normalised
+(transform_kmers.fold_strands / phk_batch_fold_strands), so a contig scores bit for bit the same
+whichever strand the assembler wrote.  The features cache always holds FORWARD counts: a run that starts from the cache
+folds after loading it, so a cache is never folded twice and serves a forward-only run as well.
+
 The k-means fit that yields the centroids is scikit-learn's, as in the reference (learning.kmeans); the density
 method needs none (a dense float64 Gaussian kernel density per class, density.hip).  The svm method fits scikit-learn's
 NuSVC() on the device (svm.hip) and scores 1.0 / 0.0 by its predict; dbscan clusters each class with learning.dbscan
@@ -80,6 +86,7 @@ class phamer_scorer(object):
         self.kmer_length = 4
         self.k_clusters = 86
         self.k_neighbors = 3
+        self.both_strands = False           # fold every count row with its reverse complement (module docstring)
         self.positive_bandwidth = 0.005     # scripts/phamer.py:82-83 (density method)
         self.negative_bandwidth = 0.01
         self.k_clusters_positive = 86       # scripts/phamer.py:80-89 (dbscan method: its k-means fallback, eps, min_samples)
@@ -147,6 +154,13 @@ class phamer_scorer(object):
         self._load_queries(length_requirement)
 
     def _load_reference(self):
+        if self.both_strands:     # the counts are folded before they are normalised
+            from . import kmer, transform_kmers
+            self.positive_ids, counts = fileIO.read_feature_file(self.positive_features_file)
+            self.positive_data = kmer.normalize_counts(transform_kmers.fold_strands(counts))
+            self.negative_ids, counts = fileIO.read_feature_file(self.negative_features_file)
+            self.negative_data = kmer.normalize_counts(transform_kmers.fold_strands(counts))
+            return
         self.positive_ids, self.positive_data = fileIO.read_feature_file(self.positive_features_file, normalize=True)
         self.negative_ids, self.negative_data = fileIO.read_feature_file(self.negative_features_file, normalize=True)
 
@@ -169,6 +183,11 @@ class phamer_scorer(object):
             if batch is not None:
                 self._batch = batch
                 self.kmer_length = int(round(np.log(batch.D) / np.log(4)))
+                if self.both_strands:      # the cache holds forward counts: folded here, after loading, never in the file
+                    batch.fold_strands()
+            elif self.both_strands:
+                from . import transform_kmers
+                self.data_points = kmer.normalize_counts(transform_kmers.fold_strands(counts))
             else:
                 self.data_points = kmer.normalize_counts(counts)
             del counts
@@ -204,6 +223,8 @@ class phamer_scorer(object):
             self._write_cache_async(counts, ids, path)
         else:
             fileIO.save_counts(counts, ids, path)
+        if self.both_strands:      # after the forward counts have been taken for the cache
+            self._batch.fold_strands()
         return lengths
 
     def _write_cache_async(self, counts, ids, path):
@@ -499,13 +520,22 @@ def score_with_scorer(scoring_data, positive_training_data, negative_training_da
     return scorer.score_points()
 
 
-def score_contigs(sequences, positive_training_data, negative_training_data, kmer_length=4, method='combo'):
+def score_contigs(sequences, positive_training_data, negative_training_data, kmer_length=4, method='combo', both_strands=False,
+                  k_clusters=None):
     """Count -> normalise -> score a list of contig strings, device resident (what load_data + score_points do for a
-    FASTA input, scripts/phamer.py:131,139,579)."""
+    FASTA input, scripts/phamer.py:131,139,579).  ``both_strands``: the contigs' counts are folded with their reverse
+    complement on the device before scoring; the training data are taken as given -- pass matrices normalised from
+    folded counts (transform_kmers.fold_strands).  ``k_clusters``: clusters per class of the kmeans / combo fit (default:
+    phamer_scorer's 86)."""
     scorer = phamer_scorer()
     scorer.scoring_method = method
+    if k_clusters is not None:
+        scorer.k_clusters = int(k_clusters)
     scorer.kmer_length = kmer_length
+    scorer.both_strands = bool(both_strands)
     scorer._batch = _lib.Batch.from_sequences(_lib.get_context(), list(sequences), kmer_length)
+    if both_strands:
+        scorer._batch.fold_strands()
     scorer.positive_data, scorer.negative_data = positive_training_data, negative_training_data
     try:
         return scorer.score_points()
@@ -562,6 +592,8 @@ def _parser():
             (('-l', '--length_requirement'), dict(type=int, default=5000, help='Input sequence length requirement')),
             (('-equal', '-e', '--equalize_reference'), dict(action='store_true', help='Same number of reference points')),
             (('--gpus',), dict(type=int, default=1, help='GPUs of this node to shard the contigs over (one process per GPU)')),
+            (('--both_strands',), dict(action='store_true', help='Fold every count row with its reverse complement: a contig '
+                                                                 'scores the same on either strand')),
             (('-v', '--verbose'), dict(action='store_true')),
             (('--debug',), dict(action='store_true')),
             # the rest of the reference's command line (scripts/phamer.py:515-553), so that its launch scripts
@@ -587,6 +619,7 @@ def _run(ap, args):
 
     scorer = phamer_scorer()
     scorer.kmer_length = args.kmer_length
+    scorer.both_strands = args.both_strands
     scorer.input_directory, scorer.fasta_file, scorer.features_file = args.input_directory, args.fasta_file, args.features_file
     if args.data_directory:
         scorer.data_directory = args.data_directory
@@ -623,11 +656,13 @@ def _run(ap, args):
     return scorer
 
 
-def _rank_count_and_score(fasta_file, part, kmer_length, method, positive, negative, cpos, cneg, k_neighbors, keep_of, gpu):
+def _rank_count_and_score(fasta_file, part, kmer_length, method, positive, negative, cpos, cneg, k_neighbors, keep_of, gpu,
+                          both_strands=False):
     """One rank's share of the FASTA file on its GPU: the records that begin in byte range ``part`` = (rank, world) are parsed
     straight into the upload's staging buffers (phk_batch_from_fasta_part), counted, screened (``keep_of(ids, lengths)`` ->
     boolean mask over this rank's records, decided with every rank's ids) and scored.  Returns (ids, counts uint32 of every
-    record, keep mask, scores of the kept).  (A module-level function so that the CPU tests can put the oracle in its
+    record, keep mask, scores of the kept).  ``both_strands``: the rank folds its own rows after the forward counts have
+    been taken for the cache; nothing more is exchanged.  (A module-level function so that the CPU tests can put the oracle in its
     place: the product has no CPU path.)"""
     ctx = _lib.get_context(gpu)
     threads = max(1, (os.cpu_count() or 1) // max(1, part[1]))
@@ -642,6 +677,8 @@ def _rank_count_and_score(fasta_file, part, kmer_length, method, positive, negat
         scores = np.zeros(0)
         if keep.any():
             sub = batch if keep.all() else batch.select(np.flatnonzero(keep))
+            if both_strands:
+                sub.fold_strands()
             cen = method in _CENTROID_METHODS
             model = _lib.Model(ctx, positive, negative, cpos if cen else None, cneg if cen else None, k_neighbors=k_neighbors)
             try:
@@ -679,6 +716,7 @@ def _run_rank(ap, args):
     try:
         scorer = phamer_scorer()
         scorer.kmer_length = args.kmer_length
+        scorer.both_strands = args.both_strands
         scorer.input_directory, scorer.fasta_file, scorer.features_file = args.input_directory, args.fasta_file, args.features_file
         if args.data_directory:
             scorer.data_directory = args.data_directory
@@ -726,9 +764,10 @@ def _run_rank(ap, args):
                     keep_of.all_keep, keep_of.kept_ids = k_all, long_ids
             return keep_of.all_keep[first:first + len(ids)]
 
+        strands = {"both_strands": True} if scorer.both_strands else {}
         ids, counts, keep, scores = _rank_count_and_score(scorer.fasta_file, (rank, world), scorer.kmer_length, scorer.scoring_method,
                                                           scorer.positive_data, scorer.negative_data, cpos, cneg, scorer.k_neighbors,
-                                                          keep_of, gpu)
+                                                          keep_of, gpu, **strands)
         all_scores = pdist.gather_variable(torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float64)).to(dev)).cpu().numpy()
         all_counts = pdist.gather_rows_to_root(torch.from_numpy(np.ascontiguousarray(counts).view(np.int32)).to(dev))
         if rank == 0:

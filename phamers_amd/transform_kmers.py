@@ -15,6 +15,10 @@ Two families of index tables:
 * ``exact_indices`` -- what the docstring of the reference describes: the column of the reversed / complemented /
   reverse-complemented k-mer, a true permutation for every k (``transform_kmers(..., exact=True)``).  For all-valid
   sequences counts(transform(sequence)) == transform_kmers(counts(sequence), exact=True).
+
+``fold_strands`` / ``fold_batch`` add a count row to its reverse-complement permutation: the
+counts of a sequence and of its reverse complement together, for every string, so that a contig gives the same row
+whichever strand the assembler wrote.
 """
 import numpy as np
 
@@ -85,3 +89,31 @@ def transform_kmers(counts, reverse=True, complement=False, symbols='ATGC', exac
     ctx = _lib.get_context()
     _lib.check(ctx.lib.phk_permute_columns_i64(ctx.handle, _lib.ptr(src), n, D, _lib.ptr(perm), _lib.ptr(out)))
     return out.astype(counts.dtype, copy=False)
+
+
+def fold_strands(counts):
+    """counts + counts[:, exact_indices(k, True, True)] for an integer count matrix (n, 4^k) of the host
+    (phk_fold_strands_i64): what counting every sequence AND its reverse complement gives; the row sums double.  int64
+    out, no limit on the entries.  TypeError for float rows: folding normalised rows does not reproduce
+    normalise-after-fold bit for bit, so fold the counts and normalise then.  ValueError for a width that is not 4^k,
+    1 <= k <= 7."""
+    counts = np.asarray(counts)
+    if not (np.issubdtype(counts.dtype, np.integer) or counts.dtype == np.bool_):
+        raise TypeError("fold_strands takes integer counts (got %s): fold the counts first, then normalise" % counts.dtype)
+    if counts.ndim != 2:
+        raise ValueError("fold_strands expects an (n, 4^k) matrix")
+    n, D = counts.shape
+    if D not in [4 ** k for k in range(1, _lib.MAX_K + 1)]:
+        raise ValueError("fold_strands: %d columns is not 4^k for 1 <= k <= %d" % (D, _lib.MAX_K))
+    src = np.ascontiguousarray(counts, dtype=np.int64)
+    out = np.empty_like(src)
+    ctx = _lib.get_context()
+    _lib.check(ctx.lib.phk_fold_strands_i64(ctx.handle, _lib.ptr(src), n, D, _lib.ptr(out)))
+    return out
+
+
+def fold_batch(batch):
+    """``fold_strands`` on a device-resident batch (``_lib.Batch``), in place (phk_batch_fold_strands); returns the
+    batch.  A batch keeps uint32 row sums: one of 2^31 or more raises ``_lib.PhkError`` (PHK_ERR_UNSUPPORTED, batch
+    untouched); folding a folded batch raises it with PHK_ERR_ARG."""
+    return batch.fold_strands()

@@ -5,11 +5,13 @@ regions the windows above a threshold merge to.
     regions = call_regions(track, threshold=0.0, min_windows=2)
 
     python -m phamers_amd.windows -in genome.fasta -out DIR -data DATA_DIR [-w 5000 -s 500 -k 4 -m combo -t 0 -min 1]
+                                  [--both_strands]
 
 The windows are the rows of ONE device-resident batch (``kmer.count_windows``' kernel: every base goes to the device once,
 whatever the overlap); normalisation and every scoring method then apply to it as to any batch of
-contigs.  This is this project's own tool: the reference scores whole contigs only.  Not here: sharding the windows over
-several GPUs, folding reverse complements, plots; ``python -m phamers_amd.phamer``'s command line is unchanged.
+contigs.  With ``both_strands`` the window rows are folded with their reverse complement on the device (DESIGN.md section
+4.13): the track of a sequence is then the track of its reverse complement read backwards.  This is this project's own
+tool: the reference scores whole contigs only.  Not here: sharding the windows over several GPUs, plots.
 """
 import argparse
 import os
@@ -39,12 +41,14 @@ class WindowTrack(object):
 
 
 def score_windows(fasta_file_or_sequences, positive, negative, window=5000, step=500, kmer_length=4, method='combo',
-                  k_clusters=86):
+                  k_clusters=86, both_strands=False):
     """Scores every window of ``window`` bases, every ``step`` bases, of every sequence (a FASTA path or a list of strings,
     as ``kmer.count_windows``) against the normalised reference matrices ``positive`` / ``negative`` -> WindowTrack.
     A window without a single valid k-mer (a scaffold gap of N) would be a NaN query row: it is left out of the scored
     batch and its score is nan.  The model (and, for kmeans / combo, the centroids: k-means with ``k_clusters``) is built
-    once per call, as ``phamer.score_contigs`` builds it."""
+    once per call, as ``phamer.score_contigs`` builds it.  ``both_strands``: the window rows are folded with their reverse
+    complement before scoring; ``positive`` / ``negative`` are taken as given -- pass references normalised from folded
+    counts (transform_kmers.fold_strands), as the command line does."""
     from . import phamer
     record_ids, lengths, batch = kmer._windows_batch(fasta_file_or_sequences, kmer_length, window, step)
     owner, start = kmer.window_plan(lengths, window, step)
@@ -59,6 +63,8 @@ def score_windows(fasta_file_or_sequences, positive, negative, window=5000, step
             batch.close()
             batch = chosen
         if batch.n:
+            if both_strands:
+                batch.fold_strands()
             scorer.scoring_method, scorer.kmer_length, scorer.k_clusters = method, int(kmer_length), int(k_clusters)
             scorer.positive_data, scorer.negative_data = positive, negative
             scorer._batch = batch
@@ -150,7 +156,9 @@ def _parser():
             (('-k', '--kmer_length'), dict(type=int, default=4, help='k-mer length')),
             (('-m', '--method'), dict(default='combo', help='Scoring method')),
             (('-t', '--threshold'), dict(type=float, default=0.0, help='A window is a hit when its score is above this')),
-            (('-min', '--min_windows'), dict(type=int, default=1, help='Fewest consecutive hits that make a region'))):
+            (('-min', '--min_windows'), dict(type=int, default=1, help='Fewest consecutive hits that make a region')),
+            (('--both_strands',), dict(action='store_true', help='Fold windows and reference counts with their reverse '
+                                                                 'complement'))):
         ap.add_argument(*flags, **kw)
     return ap
 
@@ -160,6 +168,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from . import phamer
     scorer = phamer.phamer_scorer()
+    scorer.both_strands = args.both_strands      # (_load_reference folds the reference counts it reads)
     if args.data_directory:
         scorer.data_directory = args.data_directory
         scorer.find_data_files()
@@ -169,7 +178,7 @@ def main(argv=None):
         ap.error("give -data <dir with reference_features/> or -pf and -nf")
     scorer._load_reference()
     track = score_windows(args.fasta_file, scorer.positive_data, scorer.negative_data, window=args.window, step=args.step,
-                          kmer_length=args.kmer_length, method=args.method)
+                          kmer_length=args.kmer_length, method=args.method, both_strands=args.both_strands)
     regions = call_regions(track, threshold=args.threshold, min_windows=args.min_windows)
     os.makedirs(args.output_directory, exist_ok=True)
     save_track(os.path.join(args.output_directory, "window_scores.csv"), track, args=args)
