@@ -1,4 +1,5 @@
-"""CPU-only: the window plan, region calling, the track file and the command line of phamers_amd.windows."""
+"""CPU-only: the window plan, region calling, the track file and the command line of phamers_amd.windows; the reference of
+the GPU window tests (tests/windows_ref.py) against the oracle."""
 import argparse
 import os
 
@@ -121,3 +122,80 @@ def test_command_line_parses():
 def test_windows_module_does_not_import_oracle():
     text = open(os.path.join(REPO, "phamers_amd", "windows.py")).read()
     assert "import oracle" not in text and "from oracle" not in text
+
+
+# ---- tests/windows_ref.py, the reference of the GPU window tests, against the oracle -----------------------------------
+def noisy_seqs(seed, W):
+    """Lengths below, at and above W, around it and in the middle of a packed word; N and lower case (both invalid)."""
+    rng = np.random.RandomState(seed)
+    alphabet, p = list("ATGCNatgc"), [0.22] * 4 + [0.04] + [0.02] * 4
+    lengths = (0, 5, W - 1, W, W + 1, 63, 2 * W + 3, 300)
+    seqs = ["".join(rng.choice(alphabet, L, p=p)) if L else "" for L in lengths]
+    s = list(seqs[-1])
+    s[100:100 + W + 5] = "N" * (W + 5)             # windows without a single valid k-mer
+    s[200:230] = "".join(s[200:230]).lower()
+    seqs[-1] = "".join(s)
+    return seqs
+
+
+@pytest.mark.parametrize("W,S", [(24, 1), (24, 7), (24, 24), (24, 31), (7, 3)])
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7])
+def test_windows_ref_equals_the_oracle_row_by_row(k, W, S):
+    from oracle import oracle
+    from phamers_amd import kmer
+    from tests import windows_ref
+    seqs = noisy_seqs(10 * k + S, W)
+    owner, start, counts, sums = windows_ref.window_counts(seqs, k, W, S)
+    plan_owner, plan_start = kmer.window_plan([len(s) for s in seqs], W, S)
+    assert owner.dtype == np.int64 and start.dtype == np.int64
+    assert np.array_equal(owner, plan_owner) and np.array_equal(start, plan_start)
+    assert counts.dtype == np.int64 and counts.shape == (len(owner), 4 ** k)
+    assert sums.dtype == np.int64 and np.array_equal(sums, counts.sum(axis=1))
+    assert len(owner) >= 10 and (sums > 0).any() and (sums < W - k + 1).any()
+    if S <= 6:                                      # (a larger step can miss the run of N)
+        assert (sums == 0).any()
+    for i, (r, a) in enumerate(zip(owner, start)):
+        assert np.array_equal(counts[i], oracle.count_string(seqs[r][a:a + W], k)), (i, r, a)
+
+
+def test_windows_ref_takes_no_window_and_other_symbols():
+    from oracle import oracle
+    from tests import windows_ref
+    owner, start, counts, sums = windows_ref.window_counts(["ACG", ""], 2, 4, 1)
+    assert owner.shape == start.shape == sums.shape == (0,) and counts.shape == (0, 16)
+    owner, start, counts, sums = windows_ref.window_counts([], 3, 4, 1)
+    assert owner.shape == (0,) and counts.shape == (0, 64)
+    s = "AUGCCGUAAUGTTAUG"                            # T is no RNA symbol: invalid
+    _, start, counts, _ = windows_ref.window_counts([s], 2, 6, 2, symbols="AUGC")
+    for i, a in enumerate(start):
+        assert np.array_equal(counts[i], oracle.count_string(s[a:a + 6], 2, symbols="AUGC"))
+
+
+@pytest.mark.parametrize("k", [1, 3, 4, 5])
+def test_windows_ref_folded_is_the_slice_plus_its_reverse_complement(k):
+    from oracle import oracle
+    from tests import strands_ref, windows_ref
+    W, S = 24, 5
+    seqs = noisy_seqs(k, W)
+    owner, start, counts, sums = windows_ref.window_counts_folded(seqs, k, W, S)
+    fwd = windows_ref.window_counts(seqs, k, W, S)
+    assert np.array_equal(owner, fwd[0]) and np.array_equal(start, fwd[1])
+    assert np.array_equal(sums, counts.sum(axis=1)) and np.array_equal(sums, 2 * fwd[3])
+    assert np.array_equal(counts, strands_ref.fold(fwd[2]))
+    for i, (r, a) in enumerate(zip(owner, start)):
+        piece = seqs[r][a:a + W]
+        want = oracle.count_string(piece, k) + oracle.count_string(strands_ref.revcomp(piece), k)
+        assert np.array_equal(counts[i], want), (i, r, a)
+
+
+def test_windows_ref_is_fast_enough_for_a_grid_pass_of_windows():
+    """About 82 000 windows of 16 bases at k = 4 (the largest case of tests/test_gpu_windows_sliding.py), a sample of the
+    rows against the oracle."""
+    from oracle import oracle
+    from tests import windows_ref
+    rng = np.random.RandomState(4)
+    seqs = ["".join(rng.choice(list("ATGC"), L)) for L in rng.randint(16, 19, 41000)]
+    owner, start, counts, sums = windows_ref.window_counts(seqs, 4, 16, 1)
+    assert 80000 < len(owner) < 84000 and (sums == 13).all()
+    for i in range(0, len(owner), 4099):
+        assert np.array_equal(counts[i], oracle.count_string(seqs[owner[i]][start[i]:start[i] + 16], 4))
