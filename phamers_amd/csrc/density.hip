@@ -8,21 +8,12 @@
 // Everything is float64: the Gram product on the fp64 matrix pipe (v_mfma_f64_16x16x4_f64), the norms, the exponent and exp.
 // No row can be skipped ("Density"): the kernel is dense.
 //
-// Shape of the work.  The rows of each class are cut into chunks of KDE_CHUNK rows (a cut that depends on the class sizes
+// Shape of the work.  The rows of each class are cut into chunks of GT_CHUNK rows (a cut that depends on the class sizes
 // only); workgroup (chunk, query block) keeps, per query, a running (max, sum) of its chunk's terms and writes it to a
 // partials array; phk_kde_merge_kernel folds a query's chunks in chunk order.  The reduction order of one query is thus
 // fixed by the model alone -- the same for any N, batch split or entry point.
-#include "phk_common.h"
+#include "gram_tile.h"
 #include "score_model.h"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-#define KDE_QT 2        // 16-query tiles per wave
-#define KDE_RT 4        // 16-row tiles per row step
-#define KDE_KC 32       // columns per K step: 8 per lane (each lane's k-slot kk covers columns kc + 8 kk + s, s < 8)
-#define KDE_WAVES 4
-#define KDE_QB (KDE_WAVES * KDE_QT * 16)   // queries per workgroup (128)
-#define KDE_CHUNK 256   // rows per workgroup (one class only)
 
 // |x|^2 of rows of X[n][D], float64, one wave per row: lanes stride the columns in order, then a fixed butterfly.  Used
 // for the model's rows and for the queries alike.
@@ -53,94 +44,46 @@ __device__ __forceinline__ void kde_merge(double &m1, double &s1, double m2, dou
     m1 = m;
 }
 
-// Loads 8 consecutive doubles of row `row` at column c0 (FULL: D % KDE_KC == 0, aligned vector loads).
-template <bool FULL>
-__device__ __forceinline__ void kde_load8(const double *__restrict__ X, uint64_t D, uint64_t row, bool ok, uint64_t c0,
-                                          double v[8]) {
-    if (FULL) {
-        if (ok) {
-            const double2 *p = (const double2 *)(X + row * D + c0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const double2 t = p[i];
-                v[2 * i] = t.x;
-                v[2 * i + 1] = t.y;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = 0.0;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (ok && c0 + i < D) ? X[row * D + c0 + i] : 0.0;
-    }
-}
-
-// grid: x = chunk (class-major: the n_cpos chunks of [0, n_pos), then those of [n_pos, M)), y = block of KDE_QB queries.
+// grid: x = chunk (class-major: the n_cpos chunks of [0, n_pos), then those of [n_pos, M)), y = block of GT_QB queries.
 // part[chunk][q] = (max term, sum of exp(term - max)) over the chunk's unmasked rows; (-inf, 0) when it has none.
 // Two workgroups per CU (two waves per SIMD, 220 registers, no spills): 64.6 ms per 2^20 queries against 93.7 ms at one wave
 // per SIMD (284 registers), same results (profiles/density/README.md).
 template <bool FULL>
-__global__ __launch_bounds__(KDE_WAVES * 64, 2) void phk_kde_partial_kernel(
+__global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_kde_partial_kernel(
     const double *__restrict__ Q, const double *__restrict__ qn, uint64_t nq, const double *__restrict__ R,
     const double *__restrict__ rn, const uint8_t *__restrict__ mask, uint64_t n_pos, uint64_t M, uint64_t D,
     uint32_t n_cpos, double inv2h2_pos, double inv2h2_neg, double2 *__restrict__ part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, kk = lane >> 4;
+    const int li = threadIdx.x & 15, wave = threadIdx.x >> 6;
     const uint32_t c = blockIdx.x;
     const bool pos = c < n_cpos;
-    const uint64_t r0 = pos ? (uint64_t)c * KDE_CHUNK : n_pos + (uint64_t)(c - n_cpos) * KDE_CHUNK;
+    const uint64_t r0 = pos ? (uint64_t)c * GT_CHUNK : n_pos + (uint64_t)(c - n_cpos) * GT_CHUNK;
     const uint64_t seg_end = pos ? n_pos : M;
-    const uint64_t r1 = r0 + KDE_CHUNK < seg_end ? r0 + KDE_CHUNK : seg_end;
+    const uint64_t r1 = r0 + GT_CHUNK < seg_end ? r0 + GT_CHUNK : seg_end;
     const double inv2h2 = pos ? inv2h2_pos : inv2h2_neg;
-    const uint64_t q0 = (uint64_t)blockIdx.y * KDE_QB + (uint64_t)wave * (KDE_QT * 16);
+    const uint64_t q0 = (uint64_t)blockIdx.y * GT_QB + (uint64_t)wave * (GT_QT * 16);
 
-    // this lane's accumulator entries: query q0 + 16 a + kk + 4 r (C/D row = (lane >> 4) + 4 reg), train row = tile + li
-    double qnorm[KDE_QT][4], mx[KDE_QT][4], sm[KDE_QT][4];
+    double qnorm[GT_QT][4], mx[GT_QT][4], sm[GT_QT][4];
 #pragma unroll
-    for (int a = 0; a < KDE_QT; ++a)
+    for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const uint64_t q = q0 + 16 * a + kk + 4 * r;
+            const uint64_t q = gram_query(q0, a, r);
             qnorm[a][r] = q < nq ? qn[q] : 0.0;
             mx[a][r] = -__builtin_inf();
             sm[a][r] = 0.0;
         }
 
-    for (uint64_t st = r0; st < r1; st += KDE_RT * 16) {
-        f64x4 acc[KDE_QT][KDE_RT];
-#pragma unroll
-        for (int a = 0; a < KDE_QT; ++a)
-#pragma unroll
-            for (int t = 0; t < KDE_RT; ++t) acc[a][t] = (f64x4){0.0, 0.0, 0.0, 0.0};
-        for (uint64_t kc = 0; kc < D; kc += KDE_KC) {
-            // A operand: lane holds A[i = li][k = kk] = Q[q0 + 16 a + li][kc + 8 kk + s] at step s; B: R[row + li][same column]
-            double qa[KDE_QT][8];
-#pragma unroll
-            for (int a = 0; a < KDE_QT; ++a) {
-                const uint64_t q = q0 + 16 * a + li;
-                kde_load8<FULL>(Q, D, q, q < nq, kc + 8 * kk, qa[a]);
-            }
-#pragma unroll
-            for (int t = 0; t < KDE_RT; ++t) {
-                const uint64_t j = st + 16 * t + li;
-                double rb[8];
-                kde_load8<FULL>(R, D, j, j < r1, kc + 8 * kk, rb);
-#pragma unroll
-                for (int s = 0; s < 8; ++s)
-#pragma unroll
-                    for (int a = 0; a < KDE_QT; ++a)
-                        acc[a][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[a][s], rb[s], acc[a][t], 0, 0, 0);
-            }
-        }
+    for (uint64_t st = r0; st < r1; st += GT_RT * 16) {
+        f64x4 acc[GT_QT][GT_RT];
+        gram_tile<FULL>(Q, nq, q0, R, r1, st, D, acc);
         // epilogue: one exp per (query, row) -- exp(-|e - m|) serves both the new term and the rescale of the old sum
 #pragma unroll
-        for (int t = 0; t < KDE_RT; ++t) {
+        for (int t = 0; t < GT_RT; ++t) {
             const uint64_t j = st + 16 * t + li;
             const bool valid = j < r1 && !(mask && mask[j]);
             const double rnj = valid ? rn[j] : 0.0;
 #pragma unroll
-            for (int a = 0; a < KDE_QT; ++a)
+            for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const double d2 = fmax(qnorm[a][r] + rnj - 2.0 * acc[a][t][r], 0.0);
@@ -155,9 +98,9 @@ __global__ __launch_bounds__(KDE_WAVES * 64, 2) void phk_kde_partial_kernel(
                 }
         }
     }
-    // the 16 lanes that share a query (same kk): fixed butterfly
+    // the 16 lanes that share a query (same k-slot): fixed butterfly
 #pragma unroll
-    for (int a = 0; a < KDE_QT; ++a)
+    for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -167,10 +110,10 @@ __global__ __launch_bounds__(KDE_WAVES * 64, 2) void phk_kde_partial_kernel(
             }
     if (li == 0) {
 #pragma unroll
-        for (int a = 0; a < KDE_QT; ++a)
+        for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const uint64_t q = q0 + 16 * a + kk + 4 * r;
+                const uint64_t q = gram_query(q0, a, r);
                 if (q < nq) part[(uint64_t)c * nq + q] = make_double2(mx[a][r], sm[a][r]);
             }
     }
@@ -210,48 +153,41 @@ static double kde_lognorm(uint64_t n, uint64_t D, double h) {
 
 static bool kde_bandwidth_ok(double h) { return h > 0.0 && h < __builtin_inf(); }   // (false for NaN)
 
+// |x|^2 of the n rows of d_X[n][D] -> d_out[n]
+int phk_launch_rownorm(phk_ctx *ctx, const double *d_X, uint64_t n, uint64_t D, double *d_out) {
+    PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
+               phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(n, 4)), dim3(256), 0, ctx->stream>>>(d_X, n, D, d_out));
+    return PHK_OK;
+}
+
 // The scoring loop shared by the model path and the standalone entry: queries d_Q[N][D] (or uint32 count rows normalised
 // into the workspace first), train rows d_R[M][D] with norms d_rn, classes [0, n_pos) and [n_pos, M).
 static int kde_run(phk_ctx *ctx, const double *d_Q, const uint32_t *d_counts, uint64_t N, const double *d_R, const double *d_rn,
                    const uint8_t *d_mask, uint64_t n_pos, uint64_t M, uint64_t D, double h_pos, double h_neg, uint64_t eff_pos,
                    uint64_t eff_neg, double *d_out, uint32_t *d_status) {
-    const uint32_t n_cpos = (uint32_t)phk_div_up(n_pos, KDE_CHUNK), n_cneg = (uint32_t)phk_div_up(M - n_pos, KDE_CHUNK);
+    const uint32_t n_cpos = (uint32_t)phk_div_up(n_pos, GT_CHUNK), n_cneg = (uint32_t)phk_div_up(M - n_pos, GT_CHUNK);
     const uint32_t S = n_cpos + n_cneg;
-    // queries per launch: partials and (count rows) normalised queries within 256 MiB each, a multiple of the query block
-    uint64_t B = (256ull << 20) / ((uint64_t)S * sizeof(double2));
-    const uint64_t Bq = (256ull << 20) / (D * sizeof(double));
-    B = B < Bq ? B : Bq;
-    B = B > (1ull << 20) ? (1ull << 20) : B;
-    B = B < KDE_QB ? KDE_QB : (B / KDE_QB) * KDE_QB;
-    if (B > N) B = N;
-    void *part, *qn, *q64 = nullptr;
-    PHK_TRY(phk_ws(ctx, WS_KDE, (uint64_t)S * B * sizeof(double2) + B * sizeof(double), &part));
-    qn = (char *)part + (uint64_t)S * B * sizeof(double2);
-    if (d_counts) PHK_TRY(phk_ws(ctx, WS_Q64, B * D * sizeof(double), &q64));
     const double lp = kde_lognorm(eff_pos ? eff_pos : 1, D, h_pos), ln = n_cneg ? kde_lognorm(eff_neg, D, h_neg) : 0.0;
     const double i2p = 1.0 / (2.0 * h_pos * h_pos), i2n = n_cneg ? 1.0 / (2.0 * h_neg * h_neg) : 0.0;
-    const bool full = D % KDE_KC == 0;
-    for (uint64_t s = 0; s < N; s += B) {
-        const uint64_t nb = N - s < B ? N - s : B;
-        const double *q = d_Q ? d_Q + s * D : (const double *)q64;
-        if (d_counts) PHK_TRY(phk_launch_normalize_u32(ctx, d_counts + s * D, nb, D, (double *)q64));
-        PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
-                   phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(nb, 4)), dim3(256), 0, ctx->stream>>>(q, nb, D, (double *)qn));
-        const dim3 grid(S, (unsigned)phk_div_up(nb, KDE_QB));
-        if (full) {
-            PHK_LAUNCH(ctx, "phk_kde_partial_kernel",
-                       phk_kde_partial_kernel<true><<<grid, dim3(KDE_WAVES * 64), 0, ctx->stream>>>(
-                           q, (const double *)qn, nb, d_R, d_rn, d_mask, n_pos, M, D, n_cpos, i2p, i2n, (double2 *)part));
-        } else {
-            PHK_LAUNCH(ctx, "phk_kde_partial_kernel",
-                       phk_kde_partial_kernel<false><<<grid, dim3(KDE_WAVES * 64), 0, ctx->stream>>>(
-                           q, (const double *)qn, nb, d_R, d_rn, d_mask, n_pos, M, D, n_cpos, i2p, i2n, (double2 *)part));
-        }
-        PHK_LAUNCH(ctx, "phk_kde_merge_kernel",
-                   phk_kde_merge_kernel<<<dim3((unsigned)phk_div_up(nb, 256)), dim3(256), 0, ctx->stream>>>(
-                       (const double2 *)part, (const double *)qn, nb, n_cpos, n_cneg, lp, ln, d_out + s, d_status));
-    }
-    return PHK_OK;
+    const bool full = D % GT_KC == 0;
+    return gram_query_batches(
+        ctx, d_Q, d_counts, N, D, S, sizeof(double2),
+        [&](const double *q, const double *qn, uint64_t nb, void *part, uint64_t s) -> int {
+            const dim3 grid(S, (unsigned)phk_div_up(nb, GT_QB));
+            if (full) {
+                PHK_LAUNCH(ctx, "phk_kde_partial_kernel",
+                           phk_kde_partial_kernel<true><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
+                               q, qn, nb, d_R, d_rn, d_mask, n_pos, M, D, n_cpos, i2p, i2n, (double2 *)part));
+            } else {
+                PHK_LAUNCH(ctx, "phk_kde_partial_kernel",
+                           phk_kde_partial_kernel<false><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
+                               q, qn, nb, d_R, d_rn, d_mask, n_pos, M, D, n_cpos, i2p, i2n, (double2 *)part));
+            }
+            PHK_LAUNCH(ctx, "phk_kde_merge_kernel",
+                       phk_kde_merge_kernel<<<dim3((unsigned)phk_div_up(nb, 256)), dim3(256), 0, ctx->stream>>>(
+                           (const double2 *)part, qn, nb, n_cpos, n_cneg, lp, ln, d_out + s, d_status));
+            return PHK_OK;
+        });
 }
 
 // ---- model side ------------------------------------------------------------------------------------------------------
@@ -261,9 +197,7 @@ int phk_model_build_density(phk_ctx *ctx, phk_model *m) {
     m->eff_pos = m->n_pos;
     m->eff_neg = m->n_neg;
     PHK_HIP(hipMalloc((void **)&m->d_rn, m->M * sizeof(double)));
-    PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
-               phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(m->M, 4)), dim3(256), 0, ctx->stream>>>(m->d_R64, m->M, m->D,
-                                                                                                         m->d_rn));
+    PHK_TRY(phk_launch_rownorm(ctx, m->d_R64, m->M, m->D, m->d_rn));
     PHK_HIP(hipStreamSynchronize(ctx->stream));
     return PHK_OK;
 }
@@ -304,9 +238,7 @@ extern "C" int phk_kde_log_density(phk_ctx *ctx, const double *Q, uint64_t N, co
     PHK_TRY(phk_copy_to_device(ctx, d_x, X, M * D * sizeof(double)));
     PHK_TRY(phk_copy_to_device(ctx, d_q, Q, N * D * sizeof(double)));
     PHK_HIP(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), ctx->stream));
-    PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
-               phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(M, 4)), dim3(256), 0, ctx->stream>>>((const double *)d_x, M, D,
-                                                                                                      d_rn));
+    PHK_TRY(phk_launch_rownorm(ctx, (const double *)d_x, M, D, d_rn));
     PHK_TRY(kde_run(ctx, (const double *)d_q, nullptr, N, (const double *)d_x, d_rn, nullptr, M, M, D, h, h, M, 0, (double *)d_o,
                     (uint32_t *)d_flags));
     uint32_t nan_rows = 0;

@@ -301,6 +301,8 @@ int phk_launch_count(phk_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_m
 int phk_launch_widen(phk_ctx *ctx, const uint32_t *d_in, uint64_t count, int64_t *d_out);
 int phk_launch_normalize_u32(phk_ctx *ctx, const uint32_t *d_counts, uint64_t n, uint64_t D,
                              double *d_out);
+// density.hip: |x|^2 of the rows of d_X[n][D], float64, profiled as phk_kde_rownorm_kernel
+int phk_launch_rownorm(phk_ctx *ctx, const double *d_X, uint64_t n, uint64_t D, double *d_out);
 int phk_launch_normalize_i64(phk_ctx *ctx, const int64_t *d_counts, uint64_t n, uint64_t D,
                              double *d_out);
 int phk_launch_normalize_f64(phk_ctx *ctx, const double *d_rows, uint64_t n, uint64_t D,

@@ -6,7 +6,7 @@
 //   * Rows are taken in libsvm's grouped order (svm_group_classes): label-0 rows first with y = +1, then label-1 rows with
 //     y = -1, each class in its original order.
 //   * Q[i][j] = (float)(y_i y_j exp(-gamma (|x_i|^2 + |x_j|^2 - 2 x_i.x_j))), n x n float32 (libsvm's Qfloat), from the
-//     fp64 MFMA Gram tile of density.hip; QD_ii = 1 exactly (libsvm's x_square[i] + x_square[i] - 2 dot(x_i, x_i) = 0).
+//     fp64 MFMA Gram tile of gram_tile.h; QD_ii = 1 exactly (libsvm's x_square[i] + x_square[i] - 2 dot(x_i, x_i) = 0).
 //   * Solver_NU runs in ONE workgroup of SVM_T threads: thread t owns rows t, t + SVM_T, ...  An iteration is
 //     (i) two block-wide (value, index) arg-max reductions with the sequential scan's last-index ties,
 //     (ii) the j choice over rows Q_ip / Q_in (min obj_diff, last index on ties) plus the two second maxima,
@@ -16,120 +16,62 @@
 //   * calculate_rho is a sequential pass (one thread, row order, as libsvm sums).
 //   All solver arithmetic is compiled without fp contraction: libsvm rounds every product.
 //
-// Decision.  dec(q) = sum_sv coef_sv exp(-gamma |q - x_sv|^2) - rho on the same MFMA Gram tile as phk_kde_partial_kernel
-// with a weighted-sum epilogue.  Support vectors are cut into chunks of SVM_CHUNK (a cut that depends on the model only),
+// Decision.  dec(q) = sum_sv coef_sv exp(-gamma |q - x_sv|^2) - rho on the same Gram tile (gram_tile.h, shared with density.hip)
+// with a weighted-sum epilogue.  Support vectors are cut into chunks of GT_CHUNK (a cut that depends on the model only),
 // a workgroup sums one chunk for a block of queries, and the merge kernel folds a query's chunks in chunk order: a query's
 // value is bit-identical for any batch split and entry point.  The method's score is 1.0 where libsvm's value is <= 0
 // (scikit-learn's predict gives classes_[1] = 1.0 there), else 0.0.
 #include <cmath>
 #include <vector>
 
-#include "phk_common.h"
+#include "gram_tile.h"
 #include "score_model.h"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-#define SVM_QT 2        // 16-query tiles per wave
-#define SVM_RT 4        // 16-row tiles per row step
-#define SVM_KC 32       // columns per K step (8 per lane)
-#define SVM_WAVES 4
-#define SVM_QB (SVM_WAVES * SVM_QT * 16)   // queries (or rows i of the Gram matrix) per workgroup (128)
-#define SVM_CHUNK 256   // support vectors (or rows j) per workgroup
 
 #define SVM_T 1024      // solver threads (one workgroup)
 #define SVM_STEPS 4096  // solver iterations per launch
 #define SVM_TAU 1e-12   // libsvm's TAU
 
-// |x|^2 of rows of X[n][D] (density.hip)
-__global__ void phk_kde_rownorm_kernel(const double *__restrict__ X, uint64_t n, uint64_t D, double *__restrict__ out);
-
-template <bool FULL>
-__device__ __forceinline__ void svm_load8(const double *__restrict__ X, uint64_t D, uint64_t row, bool ok, uint64_t c0,
-                                          double v[8]) {
-    if (FULL) {
-        if (ok) {
-            const double2 *p = (const double2 *)(X + row * D + c0);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const double2 t = p[i];
-                v[2 * i] = t.x;
-                v[2 * i + 1] = t.y;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = 0.0;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (ok && c0 + i < D) ? X[row * D + c0 + i] : 0.0;
-    }
-}
-
-// The Gram tile: grid x = chunk of SVM_CHUNK rows of R, y = block of SVM_QB rows of A.  d2 = max(|a|^2 + |r|^2 - 2 a.r, 0).
+// The Gram tile: grid x = chunk of GT_CHUNK rows of R, y = block of GT_QB rows of A.  d2 = max(|a|^2 + |r|^2 - 2 a.r, 0).
 // GRAM = true:  Qf[a][r] = (float)(y_a y_r exp(-gamma d2)) (A = R = the training rows, nq = nr = n; Qf[i][i] = 1).
 // GRAM = false: part[chunk][a] = sum over the chunk's rows r of coef[r] exp(-gamma d2), lanes folded by a fixed butterfly.
 template <bool FULL, bool GRAM>
-__global__ __launch_bounds__(SVM_WAVES * 64, 2) void phk_svm_tile_kernel(
+__global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_svm_tile_kernel(
     const double *__restrict__ A, const double *__restrict__ an, uint64_t nq, const double *__restrict__ R,
     const double *__restrict__ rn, uint64_t nr, uint64_t D, double gamma, const double *__restrict__ coef,
     const int8_t *__restrict__ y, float *__restrict__ Qf, double *__restrict__ part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, kk = lane >> 4;
-    const uint64_t r0 = (uint64_t)blockIdx.x * SVM_CHUNK;
-    const uint64_t r1 = r0 + SVM_CHUNK < nr ? r0 + SVM_CHUNK : nr;
-    const uint64_t q0 = (uint64_t)blockIdx.y * SVM_QB + (uint64_t)wave * (SVM_QT * 16);
+    const int li = threadIdx.x & 15, wave = threadIdx.x >> 6;
+    const uint64_t r0 = (uint64_t)blockIdx.x * GT_CHUNK;
+    const uint64_t r1 = r0 + GT_CHUNK < nr ? r0 + GT_CHUNK : nr;
+    const uint64_t q0 = (uint64_t)blockIdx.y * GT_QB + (uint64_t)wave * (GT_QT * 16);
 
-    // this lane's accumulator entries: query q0 + 16 a + kk + 4 r, row = tile + li
-    double qnorm[SVM_QT][4], sm[SVM_QT][4];
+    double qnorm[GT_QT][4], sm[GT_QT][4];
 #pragma unroll
-    for (int a = 0; a < SVM_QT; ++a)
+    for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const uint64_t q = q0 + 16 * a + kk + 4 * r;
+            const uint64_t q = gram_query(q0, a, r);
             qnorm[a][r] = q < nq ? an[q] : 0.0;
             sm[a][r] = 0.0;
         }
 
-    for (uint64_t st = r0; st < r1; st += SVM_RT * 16) {
-        f64x4 acc[SVM_QT][SVM_RT];
+    for (uint64_t st = r0; st < r1; st += GT_RT * 16) {
+        f64x4 acc[GT_QT][GT_RT];
+        gram_tile<FULL>(A, nq, q0, R, r1, st, D, acc);
 #pragma unroll
-        for (int a = 0; a < SVM_QT; ++a)
-#pragma unroll
-            for (int t = 0; t < SVM_RT; ++t) acc[a][t] = (f64x4){0.0, 0.0, 0.0, 0.0};
-        for (uint64_t kc = 0; kc < D; kc += SVM_KC) {
-            double qa[SVM_QT][8];
-#pragma unroll
-            for (int a = 0; a < SVM_QT; ++a) {
-                const uint64_t q = q0 + 16 * a + li;
-                svm_load8<FULL>(A, D, q, q < nq, kc + 8 * kk, qa[a]);
-            }
-#pragma unroll
-            for (int t = 0; t < SVM_RT; ++t) {
-                const uint64_t j = st + 16 * t + li;
-                double rb[8];
-                svm_load8<FULL>(R, D, j, j < r1, kc + 8 * kk, rb);
-#pragma unroll
-                for (int s = 0; s < 8; ++s)
-#pragma unroll
-                    for (int a = 0; a < SVM_QT; ++a)
-                        acc[a][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[a][s], rb[s], acc[a][t], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < SVM_RT; ++t) {
+        for (int t = 0; t < GT_RT; ++t) {
             const uint64_t j = st + 16 * t + li;
             const bool valid = j < r1;
             const double rnj = valid ? rn[j] : 0.0;
             const double cj = (!GRAM && valid) ? coef[j] : 0.0;
             const double yj = (GRAM && valid) ? (double)y[j] : 0.0;
 #pragma unroll
-            for (int a = 0; a < SVM_QT; ++a)
+            for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const double d2 = fmax(qnorm[a][r] + rnj - 2.0 * acc[a][t][r], 0.0);
                     const double k = exp(-gamma * d2);
                     if (GRAM) {
-                        const uint64_t q = q0 + 16 * a + kk + 4 * r;
+                        const uint64_t q = gram_query(q0, a, r);
                         if (valid && q < nq) Qf[q * nr + j] = q == j ? 1.0f : (float)((double)y[q] * yj * k);
                     } else if (valid) {
                         sm[a][r] += cj * k;
@@ -139,17 +81,17 @@ __global__ __launch_bounds__(SVM_WAVES * 64, 2) void phk_svm_tile_kernel(
     }
     if (GRAM) return;
 #pragma unroll
-    for (int a = 0; a < SVM_QT; ++a)
+    for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int o = 1; o < 16; o <<= 1) sm[a][r] += __shfl_xor(sm[a][r], o);
     if (li == 0) {
 #pragma unroll
-        for (int a = 0; a < SVM_QT; ++a)
+        for (int a = 0; a < GT_QT; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const uint64_t q = q0 + 16 * a + kk + 4 * r;
+                const uint64_t q = gram_query(q0, a, r);
                 if (q < nq) part[(uint64_t)blockIdx.x * nq + q] = sm[a][r];
             }
     }
@@ -489,16 +431,15 @@ static int svm_fit_grouped(phk_ctx *ctx, const double *d_Xg, uint64_t n0, uint64
     PHK_HIP(hipMemcpyAsync(dy, y.data(), n, hipMemcpyHostToDevice, ctx->stream));
     PHK_HIP(hipMemcpyAsync(alpha, a0.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PHK_HIP(hipMemcpyAsync(dctl, &c0, sizeof(SvmCtl), hipMemcpyHostToDevice, ctx->stream));
-    PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
-               phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(n, 4)), dim3(256), 0, ctx->stream>>>(d_Xg, n, D, xn));
-    const dim3 grid((unsigned)phk_div_up(n, SVM_CHUNK), (unsigned)phk_div_up(n, SVM_QB));
-    if (D % SVM_KC == 0) {
+    PHK_TRY(phk_launch_rownorm(ctx, d_Xg, n, D, xn));
+    const dim3 grid((unsigned)phk_div_up(n, GT_CHUNK), (unsigned)phk_div_up(n, GT_QB));
+    if (D % GT_KC == 0) {
         PHK_LAUNCH(ctx, "phk_svm_gram_kernel",
-                   (phk_svm_tile_kernel<true, true><<<grid, dim3(SVM_WAVES * 64), 0, ctx->stream>>>(
+                   (phk_svm_tile_kernel<true, true><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
                        d_Xg, xn, n, d_Xg, xn, n, D, gamma, nullptr, dy, Qf, nullptr)));
     } else {
         PHK_LAUNCH(ctx, "phk_svm_gram_kernel",
-                   (phk_svm_tile_kernel<false, true><<<grid, dim3(SVM_WAVES * 64), 0, ctx->stream>>>(
+                   (phk_svm_tile_kernel<false, true><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
                        d_Xg, xn, n, d_Xg, xn, n, D, gamma, nullptr, dy, Qf, nullptr)));
     }
     PHK_LAUNCH(ctx, "phk_svm_grad_init_kernel",
@@ -537,46 +478,33 @@ static int svm_fit_grouped(phk_ctx *ctx, const double *d_Xg, uint64_t n0, uint64
 static int svm_decision_run(phk_ctx *ctx, const double *d_Q, const uint32_t *d_counts, uint64_t N, const double *d_sv,
                             const double *d_svn, const double *d_coef, uint64_t n_sv, uint64_t D, double gamma, double rho,
                             bool score, double *d_out, uint32_t *d_status) {
-    const uint32_t S = (uint32_t)phk_div_up(n_sv, SVM_CHUNK);
-    uint64_t B = (256ull << 20) / ((uint64_t)S * sizeof(double));
-    const uint64_t Bq = (256ull << 20) / (D * sizeof(double));
-    B = B < Bq ? B : Bq;
-    B = B > (1ull << 20) ? (1ull << 20) : B;
-    B = B < SVM_QB ? SVM_QB : (B / SVM_QB) * SVM_QB;
-    if (B > N) B = N;
-    void *part, *qn, *q64 = nullptr;
-    PHK_TRY(phk_ws(ctx, WS_KDE, (uint64_t)S * B * sizeof(double) + B * sizeof(double), &part));
-    qn = (char *)part + (uint64_t)S * B * sizeof(double);
-    if (d_counts) PHK_TRY(phk_ws(ctx, WS_Q64, B * D * sizeof(double), &q64));
-    const bool full = D % SVM_KC == 0;
-    for (uint64_t s = 0; s < N; s += B) {
-        const uint64_t nb = N - s < B ? N - s : B;
-        const double *q = d_Q ? d_Q + s * D : (const double *)q64;
-        if (d_counts) PHK_TRY(phk_launch_normalize_u32(ctx, d_counts + s * D, nb, D, (double *)q64));
-        PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
-                   phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(nb, 4)), dim3(256), 0, ctx->stream>>>(q, nb, D, (double *)qn));
-        const dim3 grid(S, (unsigned)phk_div_up(nb, SVM_QB));
-        if (full) {
-            PHK_LAUNCH(ctx, "phk_svm_partial_kernel",
-                       (phk_svm_tile_kernel<true, false><<<grid, dim3(SVM_WAVES * 64), 0, ctx->stream>>>(
-                           q, (const double *)qn, nb, d_sv, d_svn, n_sv, D, gamma, d_coef, nullptr, nullptr, (double *)part)));
-        } else {
-            PHK_LAUNCH(ctx, "phk_svm_partial_kernel",
-                       (phk_svm_tile_kernel<false, false><<<grid, dim3(SVM_WAVES * 64), 0, ctx->stream>>>(
-                           q, (const double *)qn, nb, d_sv, d_svn, n_sv, D, gamma, d_coef, nullptr, nullptr, (double *)part)));
-        }
-        const dim3 mg((unsigned)phk_div_up(nb, 256));
-        if (score) {
-            PHK_LAUNCH(ctx, "phk_svm_merge_kernel",
-                       phk_svm_merge_kernel<true><<<mg, dim3(256), 0, ctx->stream>>>((const double *)part, (const double *)qn, nb,
-                                                                                   S, rho, d_out + s, d_status));
-        } else {
-            PHK_LAUNCH(ctx, "phk_svm_merge_kernel",
-                       phk_svm_merge_kernel<false><<<mg, dim3(256), 0, ctx->stream>>>((const double *)part, (const double *)qn, nb,
-                                                                                    S, rho, d_out + s, d_status));
-        }
-    }
-    return PHK_OK;
+    const uint32_t S = (uint32_t)phk_div_up(n_sv, GT_CHUNK);
+    const bool full = D % GT_KC == 0;
+    return gram_query_batches(
+        ctx, d_Q, d_counts, N, D, S, sizeof(double),
+        [&](const double *q, const double *qn, uint64_t nb, void *part, uint64_t s) -> int {
+            const dim3 grid(S, (unsigned)phk_div_up(nb, GT_QB));
+            if (full) {
+                PHK_LAUNCH(ctx, "phk_svm_partial_kernel",
+                           (phk_svm_tile_kernel<true, false><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
+                               q, qn, nb, d_sv, d_svn, n_sv, D, gamma, d_coef, nullptr, nullptr, (double *)part)));
+            } else {
+                PHK_LAUNCH(ctx, "phk_svm_partial_kernel",
+                           (phk_svm_tile_kernel<false, false><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
+                               q, qn, nb, d_sv, d_svn, n_sv, D, gamma, d_coef, nullptr, nullptr, (double *)part)));
+            }
+            const dim3 mg((unsigned)phk_div_up(nb, 256));
+            if (score) {
+                PHK_LAUNCH(ctx, "phk_svm_merge_kernel",
+                           phk_svm_merge_kernel<true><<<mg, dim3(256), 0, ctx->stream>>>((const double *)part, qn, nb, S, rho,
+                                                                                       d_out + s, d_status));
+            } else {
+                PHK_LAUNCH(ctx, "phk_svm_merge_kernel",
+                           phk_svm_merge_kernel<false><<<mg, dim3(256), 0, ctx->stream>>>((const double *)part, qn, nb, S, rho,
+                                                                                        d_out + s, d_status));
+            }
+            return PHK_OK;
+        });
 }
 
 // ---- standalone NuSVC ---------------------------------------------------------------------------------------------------
@@ -637,9 +565,7 @@ extern "C" int phk_nusvc_decision(phk_ctx *ctx, const double *SV, uint64_t n_sv,
     PHK_HIP(hipMemcpyAsync(d_coef, dual_coef, n_sv * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PHK_TRY(phk_copy_to_device(ctx, d_q, Q, N * D * sizeof(double)));
     PHK_HIP(hipMemsetAsync(d_flags, 0, sizeof(uint32_t), ctx->stream));
-    PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
-               phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(n_sv, 4)), dim3(256), 0, ctx->stream>>>((const double *)d_sv,
-                                                                                                         n_sv, D, d_svn));
+    PHK_TRY(phk_launch_rownorm(ctx, (const double *)d_sv, n_sv, D, d_svn));
     PHK_TRY(svm_decision_run(ctx, (const double *)d_q, nullptr, N, (const double *)d_sv, d_svn, d_coef, n_sv, D, gamma, rho,
                              false, (double *)d_o, (uint32_t *)d_flags));
     PHK_TRY(phk_copy_to_host(ctx, dec, d_o, N * sizeof(double)));
@@ -699,8 +625,7 @@ extern "C" int phk_model_fit_svm(phk_ctx *ctx, phk_model *m, double nu, double g
     PHK_LAUNCH(ctx, "phk_svm_gather_kernel",
                phk_svm_gather_kernel<<<dim3((unsigned)phk_div_up(ns * D, 256)), dim3(256), 0, ctx->stream>>>(
                    m->d_R64, D, (const uint32_t *)d_idx, ns, m->d_sv));
-    PHK_LAUNCH(ctx, "phk_kde_rownorm_kernel",
-               phk_kde_rownorm_kernel<<<dim3((unsigned)phk_div_up(ns, 4)), dim3(256), 0, ctx->stream>>>(m->d_sv, ns, D, m->d_svn));
+    PHK_TRY(phk_launch_rownorm(ctx, m->d_sv, ns, D, m->d_svn));
     PHK_HIP(hipStreamSynchronize(ctx->stream));
     m->n_sv = ns;
     m->svm_rho = rho;

@@ -7,13 +7,12 @@
 //                                          scikit-learn's _gradient_descent / TSNE._tsne around it
 // Everything is float64.  No floating-point atomics anywhere: every sum is taken in an order fixed by the shapes (n, D, k)
 // alone, so the results are bit-identical from run to run and do not depend on the number of compute units.
+#include "gram_tile.h"
 #include "pair_tile.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 #define TS_EPS 2.220446049250313e-16   // scikit-learn's MACHINE_EPSILON = np.finfo(np.double).eps
 #define TS_BYTES_256M (256ull << 20)
@@ -68,8 +67,7 @@ __global__ __launch_bounds__(256) void phk_pca_fold_kernel(const double *__restr
 }
 
 // part[chunk][a][b] = sum over the chunk's rows of (X[r][a] - mean[a]) (X[r][b] - mean[b]) on the fp64 matrix pipe
-// (v_mfma_f64_16x16x4_f64; operand layout as in density.hip: lane (li = lane & 15, kk = lane >> 4) supplies A[i = li][k = kk]
-// and B[k = kk][j = li], and holds C[i = kk + 4 reg][j = li]).  Here k runs over 4 rows of X, i and j over columns.
+// (v_mfma_f64_16x16x4_f64; operand and accumulator layout: gram_tile.h).  Here k runs over 4 rows of X, i and j over columns.
 // Workgroup = 4 waves = a 64 x 64 block of the covariance, each wave 2 x 2 tiles.  grid (D / 64, D / 64, chunks).
 __global__ __launch_bounds__(256) void phk_pca_cov_kernel(const double *__restrict__ X, const double *__restrict__ mean, uint64_t n,
                                                          uint64_t D, uint64_t rows_per_chunk, double *__restrict__ part) {
