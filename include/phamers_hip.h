@@ -391,6 +391,29 @@ int phk_nusvc_decision(phk_ctx *ctx, const double *SV, uint64_t n_sv, uint64_t D
 int phk_kde_log_density(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, double h,
                         double *out);
 
+/* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
+ * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
+ * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances
+ * takes the root of), a query's result is the first k rows in order of (d2, j): idx[N][k] int32, dist[N][k] = sqrt(d2),
+ * equal distances by index.  1 <= k <= 28 and k <= the rows left by the column mask, else PHK_ERR_ARG; a NaN query row
+ * gives PHK_ERR_NAN.  A float64 MFMA Gram-form proposal, an exact refinement of its candidates, a certificate and an exact
+ * fallback over all rows: the result does not depend on N, the batch split, the entry point or the route.
+ * phk_neighbors: host arrays; batch_rows = 0 picks the query batch, another value is rounded up to the query block of 128.
+ * phk_model_neighbors: host float64 rows against the model's train rows under its column mask; indices point into
+ * vstack(pos, neg).  phk_batch_neighbors: the rows of a resident batch, normalised on the device, nothing uploaded. */
+int phk_neighbors(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, int k, uint64_t batch_rows,
+                  int32_t *idx, double *dist);
+int phk_model_neighbors(phk_ctx *ctx, const phk_model *model, const double *Q, uint64_t N, int k, int32_t *idx, double *dist);
+int phk_batch_neighbors(phk_ctx *ctx, const phk_model *model, const phk_batch *b, int k, int32_t *idx, double *dist);
+/* out[0] = queries answered, out[1] = queries that took the fallback, since the last call; then both start from zero */
+int phk_neighbors_stats(phk_ctx *ctx, uint64_t out[2]);
+/* Diagnostics for the tests.  phk_neighbors_keep_details(ctx, 1): every later lookup on the context keeps, per query, the
+ * certificate's bound E on |Gram-form value - d2| and whether it fell back, and per returned row its Gram-form value (NaN
+ * for a row of a fallen-back query that the proposal had not kept).  phk_neighbors_details copies those of the last
+ * lookup, which must have had this N and k: E[N], approx_d2[N][k], fell_back[N] bytes. */
+int phk_neighbors_keep_details(phk_ctx *ctx, int on);
+int phk_neighbors_details(phk_ctx *ctx, uint64_t N, int k, double *E, double *approx_d2, uint8_t *fell_back);
+
 /* learning.silhouettes (scripts/learning.py:84-92, scikit-learn silhouette_samples): X[n][D] float64, labels[n] already
  * encoded 0..n_labels-1 -> out[n].  a = mean distance to the rest of the own cluster, b = smallest mean distance to another
  * cluster, s = (b - a) / max(a, b), 0 for a singleton.  Distances are float64 direct differences; every sum is taken in an

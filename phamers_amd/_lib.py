@@ -93,6 +93,12 @@ SIGNATURES = {
     "phk_model_set_column_mask": (c_int, [c_void_p, c_void_p, c_void_p]),
     "phk_model_set_bandwidths": (c_int, [c_void_p, c_void_p, c_double, c_double]),
     "phk_kde_log_density": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_double, c_void_p]),
+    "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
+    "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
+    "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "phk_neighbors_stats": (c_int, [c_void_p, c_void_p]),
+    "phk_neighbors_keep_details": (c_int, [c_void_p, c_int]),
+    "phk_neighbors_details": (c_int, [c_void_p, c_u64, c_int, c_void_p, c_void_p, c_void_p]),
     "phk_model_fit_svm": (c_int, [c_void_p, c_void_p, c_double, c_double, c_double]),
     "phk_nusvc_fit": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_double, c_double, c_double, ctypes.c_int32,
                               c_void_p, c_void_p, P(c_double), P(ctypes.c_int32), P(ctypes.c_int32)]),
@@ -282,6 +288,12 @@ class Context(object):
                  "reswept_three_digits", "swept_f16_beyond_int8")
         return {k: int(v) for k, v in zip(names, out)}
 
+    def neighbors_stats(self):
+        """(queries answered, queries that took the exact fallback) of the neighbour lookups since the last call."""
+        out = np.zeros(2, dtype=np.uint64)
+        check(self.lib.phk_neighbors_stats(self.handle, ptr(out)))
+        return int(out[0]), int(out[1])
+
     # ---- timing ----
     def profile_enable(self, on=True):
         check(self.lib.phk_profile_enable(self.handle, 1 if on else 0))
@@ -384,6 +396,16 @@ class Model(object):
         out = np.empty(Q.shape[0], dtype=np.float64)
         check(self.ctx.lib.phk_score(self.ctx.handle, self.handle, ptr(Q), Q.shape[0], METHODS[method], ptr(out)))
         return out
+
+    def neighbors(self, rows, k):
+        """(distances (N, k) float64, indices (N, k) int64 into vstack(positive, negative)) of the k nearest train rows the
+        column mask leaves in, by (distance, index) (phk_model_neighbors)."""
+        Q = np.ascontiguousarray(rows, dtype=np.float64)
+        if Q.ndim != 2 or Q.shape[1] != self.D:
+            raise ValueError("query rows must be (N, %d)" % self.D)
+        idx, dist = _neighbor_outputs(Q.shape[0], k)
+        return _neighbor_result(self.ctx.lib.phk_model_neighbors(self.ctx.handle, self.handle, ptr(Q), Q.shape[0], int(k),
+                                                                 ptr(idx), ptr(dist)), idx, dist)
 
 
 PLACEMENT_DUPLICATE, PLACEMENT_EMPTY = 1, 2
@@ -513,6 +535,67 @@ class Sweep(object):
             self.close()
         except Exception:
             pass
+
+
+NEIGHBORS_MAX_K = 28
+
+
+def _neighbor_outputs(n, k):
+    k = int(k)
+    if not 1 <= k <= NEIGHBORS_MAX_K:
+        raise ValueError("k = %d is not in 1..%d" % (k, NEIGHBORS_MAX_K))
+    return np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.float64)
+
+
+def _neighbor_result(rc, idx, dist):
+    if rc == PHK_ERR_NAN:
+        raise ValueError("Input contains NaN.")   # as scoring does
+    if rc == PHK_ERR_ARG:
+        raise ValueError(last_error())
+    check(rc)
+    return dist, idx.astype(np.int64)
+
+
+def check_neighbor_arguments(Q, X, k):
+    """The ValueErrors of a neighbour lookup that need no device: shapes, 1 <= k <= min(28, rows)."""
+    if Q.ndim != 2 or X.ndim != 2:
+        raise ValueError("query rows and data must be 2-D, got %dD and %dD" % (Q.ndim, X.ndim))
+    if Q.shape[1] != X.shape[1] or X.shape[1] == 0:
+        raise ValueError("query rows have %d columns, data %d" % (Q.shape[1], X.shape[1]))
+    k = int(k)
+    if not 1 <= k <= NEIGHBORS_MAX_K:
+        raise ValueError("k = %d is not in 1..%d" % (k, NEIGHBORS_MAX_K))
+    if k > X.shape[0]:
+        raise ValueError("Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %d" % (k, X.shape[0]))
+
+
+def neighbors(ctx, Q, X, k, batch_rows=0, details=None):
+    """The k nearest rows of X for every row of Q by (distance, index) on the device (phk_neighbors): (distances (N, k)
+    float64, indices (N, k) int64).  ``details``: a dict that receives fell_back (count), queries, E (N,), approx_d2 (N, k)
+    and fell_back_rows (N,) bool."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    check_neighbor_arguments(Q, X, k)
+    if np.isnan(X).any():
+        raise ValueError("Input contains NaN.")
+    idx, dist = _neighbor_outputs(Q.shape[0], k)
+    if details is not None:
+        ctx.neighbors_stats()
+        check(ctx.lib.phk_neighbors_keep_details(ctx.handle, 1))
+    try:
+        out = _neighbor_result(ctx.lib.phk_neighbors(ctx.handle, ptr(Q), Q.shape[0], ptr(X), X.shape[0], X.shape[1], int(k),
+                                                     int(batch_rows), ptr(idx), ptr(dist)), idx, dist)
+        if details is not None:
+            n = Q.shape[0]
+            E, a, fb = np.empty(n), np.empty((n, int(k))), np.zeros(n, dtype=np.uint8)
+            if n:
+                check(ctx.lib.phk_neighbors_details(ctx.handle, n, int(k), ptr(E), ptr(a), ptr(fb)))
+            queries, fell = ctx.neighbors_stats()
+            details.update(fell_back=fell, queries=queries, E=E, approx_d2=a, fell_back_rows=fb.astype(bool))
+    finally:
+        if details is not None:
+            ctx.lib.phk_neighbors_keep_details(ctx.handle, 0)
+    return out
 
 
 def kde_log_density(ctx, Q, X, h):
@@ -739,6 +822,13 @@ class Batch(object):
             raise ValueError("Input contains NaN.")   # what scikit-learn raises for the reference
         check(rc)
         return out
+
+    def neighbors(self, model, k):
+        """(distances (n, k), indices (n, k) int64 into the model's vstack(positive, negative)) of the k nearest train rows of
+        every resident row, normalised on the device (phk_batch_neighbors).  ValueError for a row without counts."""
+        idx, dist = _neighbor_outputs(self.n, k)
+        return _neighbor_result(self.ctx.lib.phk_batch_neighbors(self.ctx.handle, model.handle, self.handle, int(k), ptr(idx),
+                                                                 ptr(dist)), idx, dist)
 
     def close(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):

@@ -82,15 +82,16 @@ __device__ __forceinline__ void gram_tile(const double *__restrict__ Q, uint64_t
 // first, in batches of B queries against S chunks.  B: the partials (part_bytes per chunk and query) and the normalised
 // count rows within 256 MiB each, a multiple of the query block.  Per batch, score(q, qn, nb, part, s) gets the batch's nb
 // rows q with their norms qn, the partials array and the offset s of the batch's first query, and launches the caller's
-// partial and merge kernels.
+// partial and merge kernels.  force_B != 0: that many queries per batch instead (rounded to the query block; for tests).
 template <typename F>
 static int gram_query_batches(phk_ctx *ctx, const double *d_Q, const uint32_t *d_counts, uint64_t N, uint64_t D, uint32_t S,
-                              uint64_t part_bytes, F score) {
+                              uint64_t part_bytes, F score, uint64_t force_B = 0) {
     uint64_t B = (256ull << 20) / ((uint64_t)S * part_bytes);
     const uint64_t Bq = (256ull << 20) / (D * sizeof(double));
     B = B < Bq ? B : Bq;
     B = B > (1ull << 20) ? (1ull << 20) : B;
     B = B < GT_QB ? GT_QB : (B / GT_QB) * GT_QB;
+    if (force_B) B = phk_div_up(force_B, GT_QB) * GT_QB;
     if (B > N) B = N;
     void *part, *q64 = nullptr;
     PHK_TRY(phk_ws(ctx, WS_KDE, (uint64_t)S * B * part_bytes + B * sizeof(double), &part));

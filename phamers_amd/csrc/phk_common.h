@@ -80,6 +80,9 @@ enum PhkSlot {
                     // alternating blocks (PhkCountCtl), see phk_launch_count
     WS_KDE,         // density scoring: per-chunk (max, sum) partials + query norms (density.hip)
     WS_SORT,        // evaluation: the radix sort's key / index pairs and histograms, the ROC curve's points (evaluate.hip)
+    WS_NN,          // neighbour lookup: a batch's merged candidate lists and its list of uncertified queries (neighbors.hip)
+    WS_NNF,         // ... the gathered rows of the queries that fall back
+    WS_NND,         // ... the kept details of a call (phk_neighbors_keep_details)
     WS_SLOTS
 };
 
@@ -168,6 +171,12 @@ struct phk_ctx {
     // pinned staging buffers of the sequence upload (phk_batch_from_ascii), allocated at the first multi-chunk upload
     void *stage[2] = {nullptr, nullptr};
     uint64_t stage_bytes = 0;
+    // neighbour lookup (neighbors.hip): queries seen / fallen back since the last phk_neighbors_stats; whether calls keep
+    // their details in WS_NND, and the shape of the call they belong to (0 rows: none)
+    uint64_t nn_queries = 0, nn_fell_back = 0;
+    bool nn_keep = false;
+    uint64_t nn_det_n = 0;
+    int nn_det_k = 0;
 };
 
 int phk_ws(phk_ctx *ctx, int slot, uint64_t bytes, void **out);
@@ -326,6 +335,10 @@ int phk_launch_synth_ragged(phk_ctx *ctx, uint64_t seed, uint64_t first, uint64_
 int phk_silhouettes_resident(phk_ctx *ctx, const double *d_rows, uint64_t n, uint64_t D, const uint32_t *labels, uint32_t n_labels,
                              double *out);
 // score.hip
+// out[q][x] = the direct-difference fma chain |Q[q] - X[x]|^2 (phk_dist2_f64_kernel), out[nq][nx]; masked rows -> +inf
+// (phk_mask_dist_kernel)
+int phk_launch_dist2(phk_ctx *ctx, const double *d_Q, uint64_t nq, const double *d_X, uint64_t nx, uint64_t D, double *d_out);
+int phk_launch_mask_dist(phk_ctx *ctx, double *d_dist, uint64_t nq, uint64_t M, const uint8_t *d_mask);
 struct phk_model;
 int phk_score_rows(phk_ctx *ctx, const phk_model *m, const double *d_Q, const uint32_t *d_counts,
                    const uint32_t *d_rowsum, uint64_t N, int method, double *d_scores, uint32_t *d_status);

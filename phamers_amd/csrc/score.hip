@@ -86,6 +86,18 @@ __global__ __launch_bounds__(256) void phk_mask_dist_kernel(double *__restrict__
     if (mask[i % M] && dist[i] == dist[i]) dist[i] = __builtin_inf();   // (a NaN query row stays NaN)
 }
 
+int phk_launch_dist2(phk_ctx *ctx, const double *d_Q, uint64_t nq, const double *d_X, uint64_t nx, uint64_t D, double *d_out) {
+    dim3 grid((unsigned)phk_div_up(nx, DT), (unsigned)phk_div_up(nq, DT));
+    PHK_LAUNCH(ctx, "phk_dist2_f64_kernel", phk_dist2_f64_kernel<<<grid, dim3(256), 0, ctx->stream>>>(d_Q, nq, d_X, nx, D, d_out, nx));
+    return PHK_OK;
+}
+
+int phk_launch_mask_dist(phk_ctx *ctx, double *d_dist, uint64_t nq, uint64_t M, const uint8_t *d_mask) {
+    PHK_LAUNCH(ctx, "phk_mask_dist_kernel",
+               phk_mask_dist_kernel<<<dim3((unsigned)phk_div_up(nq * M, 256)), dim3(256), 0, ctx->stream>>>(d_dist, nq, M, d_mask));
+    return PHK_OK;
+}
+
 __global__ __launch_bounds__(256) void phk_knn_vote_kernel(const double *__restrict__ dist, uint64_t nq,
                                                            uint64_t M, uint64_t ld,
                                                            const uint8_t *__restrict__ labels, int kn,

@@ -186,6 +186,48 @@ def save_phamer_scores(ids, scores, file_name, args=None):
                                         _lib.ptr(scores), scores.shape[0]))
 
 
+NEIGHBORS_COLUMNS = ("contig_id", "rank", "reference_id", "class", "distance")
+
+
+def save_phamer_neighbors(file_name, contig_ids, reference_ids, reference_is_positive, distances, args=None, slice_rows=65536):
+    """phamer_output/phamer_neighbors.csv: the '# ' header block, the column line, then one 'contig_id,rank,reference_id,
+    class,distance' line per (contig, neighbour): rank from 1, class 'positive' / 'negative', the distance as
+    ``repr(float)``.  Fields are quoted as the csv module does (an id may hold a comma).  ``reference_ids`` /
+    ``reference_is_positive`` / ``distances`` are (n, k); written ``slice_rows`` contigs at a time."""
+    import csv
+    header = "PhaMers nearest reference file"
+    if args is not None:
+        header = generate_summary(args, header=header)
+    distances = np.asarray(distances, dtype=np.float64)
+    n, k = distances.shape
+    if len(contig_ids) != n or np.shape(reference_ids) != (n, k) or np.shape(reference_is_positive) != (n, k):
+        raise ValueError("%d contig ids, reference ids %s and classes %s for %s distances"
+                         % (len(contig_ids), np.shape(reference_ids), np.shape(reference_is_positive), (n, k)))
+    names = ("negative", "positive")
+    with open(file_name, 'w', newline='') as f:
+        f.write(_comment_block(header).decode('latin-1'))
+        w = csv.writer(f, lineterminator='\n')
+        w.writerow(NEIGHBORS_COLUMNS)
+        for s in range(0, n, slice_rows):
+            e = min(n, s + slice_rows)
+            cids = [str(c) for c in np.asarray(contig_ids[s:e]).tolist()]
+            rids = np.asarray(reference_ids[s:e]).tolist()
+            cls = np.asarray(reference_is_positive[s:e]).tolist()
+            dist = distances[s:e].tolist()
+            w.writerows((cids[i], r + 1, str(rids[i][r]), names[1 if cls[i][r] else 0], repr(dist[i][r]))
+                        for i in range(e - s) for r in range(k))
+
+
+def read_phamer_neighbors(filename):
+    """The rows of a nearest reference file as (contig_id, rank, reference_id, class, distance) tuples."""
+    import csv
+    with open(filename, 'r', newline='') as f:
+        rows = csv.reader(line for line in f if not line.startswith('#'))
+        if tuple(next(rows)) != NEIGHBORS_COLUMNS:
+            raise ValueError("%s is not a nearest reference file" % filename)
+        return [(c, int(r), i, kind, float(d)) for c, r, i, kind, d in rows]
+
+
 def read_phamer_output(filename):
     """{contig id: score} of a PhaMers score file."""
     with open(filename, 'r') as f:

@@ -75,6 +75,22 @@ def distances(vector, data):
     return out[0]
 
 
+def kneighbors(queries, data, k=5, _batch_rows=0, _details=None):
+    """The k nearest rows of ``data`` (M, D) for every row of ``queries`` (N, D): ``(distances, indices)`` as scikit-learn's
+    NearestNeighbors(n_neighbors=k, algorithm='brute').fit(data).kneighbors(queries) orders them, (N, k) float64 and (N, k)
+    int64.  The distances are the numbers ``distances`` returns (sqrt of the direct-difference sums accumulated in column
+    order); equal distances are ordered by index.  1 <= k <= 28.  Computed on the device (phk_neighbors): a float64 MFMA
+    proposal, an exact refinement, a certificate and an exact fallback -- the result does not depend on the route.
+    ``_batch_rows`` / ``_details`` are for the tests: queries per batch, and a dict that receives ``fell_back``, ``queries``,
+    the per-query bound ``E`` and the Gram-form ``approx_d2`` of the returned neighbours."""
+    queries = np.asarray(queries, dtype=np.float64)
+    data = np.asarray(data, dtype=np.float64)
+    _lib.check_neighbor_arguments(queries, data, k)
+    if np.isnan(queries).any() or np.isnan(data).any():
+        raise ValueError("Input contains NaN.")
+    return _lib.neighbors(_lib.get_context(), queries, data, k, _batch_rows, _details)
+
+
 def closest_to(point, picks):
     """The row of ``picks`` closest to ``point`` (scripts/learning.py:59-66): first index wins ties, as np.argmin."""
     picks = np.asarray(picks)

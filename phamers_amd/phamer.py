@@ -289,6 +289,9 @@ class phamer_scorer(object):
     def get_phamer_output_filename(self):
         return os.path.join(self.output_directory, "phamer_scores.csv")
 
+    def get_neighbors_output_filename(self):
+        return os.path.join(self.output_directory, "phamer_neighbors.csv")
+
     def get_tsne_output_filename(self):
         """scripts/phamer.py:443-445."""
         return os.path.join(self.output_directory, "tsne_coordinates.csv")
@@ -318,6 +321,42 @@ class phamer_scorer(object):
         """phamer_scores.csv (scripts/phamer.py:316-323)."""
         self.phamer_output_filename = self.get_phamer_output_filename()
         fileIO.save_phamer_scores(self.data_ids, self.scores, self.phamer_output_filename, args=args)
+
+    # ---- nearest references -------------------------------------------------------------------------------
+    def find_nearest_references(self, k=5):
+        """The k nearest reference rows of every contig among vstack(positive_data, negative_data), by (distance, index):
+        sets ``neighbor_distances`` (n, k), ``neighbor_indices`` (n, k) into that stack and ``neighbor_ids`` (n, k) from
+        ``positive_ids`` + ``negative_ids`` (None without them).  On the resident counts when there are any; ValueError
+        for a contig without counts, as scoring raises."""
+        model = _lib.Model(_lib.get_context(), self.positive_data, self.negative_data,
+                           k_neighbors=min(self.k_neighbors, self.positive_data.shape[0] + self.negative_data.shape[0]))
+        try:
+            if self._batch is not None:
+                dist, idx = self._batch.neighbors(model, k)
+            else:
+                q = np.asarray(self._rows, dtype=np.float64)
+                if np.isnan(q).any():
+                    raise ValueError("Input contains NaN.")
+                dist, idx = model.neighbors(q, k)
+        finally:
+            model.close()
+        self.neighbor_distances, self.neighbor_indices = dist, idx
+        self.neighbor_ids = None
+        if self.positive_ids is not None and self.negative_ids is not None:
+            ids = np.concatenate((np.asarray(self.positive_ids, dtype=object), np.asarray(self.negative_ids, dtype=object)))
+            self.neighbor_ids = ids[idx]
+        return dist, idx
+
+    def make_neighbors_file(self, args=None):
+        """phamer_neighbors.csv beside phamer_scores.csv: one line per (contig, rank), see fileIO.save_phamer_neighbors."""
+        idx = self.neighbor_indices
+        ids = self.neighbor_ids
+        if ids is None:
+            n_pos = self.positive_data.shape[0]
+            ids = np.where(idx < n_pos, "positive_", "negative_").astype(object) + np.where(idx < n_pos, idx, idx - n_pos).astype(str).astype(object)
+        self.neighbors_output_filename = self.get_neighbors_output_filename()
+        fileIO.save_phamer_neighbors(self.neighbors_output_filename, self.data_ids, ids, idx < self.positive_data.shape[0],
+                                     self.neighbor_distances, args=args)
 
     # ---- scoring ------------------------------------------------------------------------------------------
     def equalize_reference_data(self):
@@ -563,6 +602,11 @@ def main(argv=None):
     if args.do_tsne or args.plot_tsne:
         raise NotImplementedError("t-SNE / plots (-do_tsne, -plot) are outside the accelerated path (SURVEY.md section 8)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if hasattr(args, "neighbors"):
+        if not 1 <= args.neighbors <= _lib.NEIGHBORS_MAX_K:
+            ap.error("--neighbors must be in 1..%d (got %d)" % (_lib.NEIGHBORS_MAX_K, args.neighbors))
+        if (args.gpus and args.gpus > 1) or world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1":
+            ap.error("--neighbors is not sharded: run it on one GPU (without --gpus)")
     if world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1":   # one rank of a sharded run (started below, or by
                                                                         # torch.distributed.run; forced: a 1-rank group, tests)
         return _run_rank(ap, args)
@@ -594,6 +638,11 @@ def _parser():
             (('--gpus',), dict(type=int, default=1, help='GPUs of this node to shard the contigs over (one process per GPU)')),
             (('--both_strands',), dict(action='store_true', help='Fold every count row with its reverse complement: a contig '
                                                                  'scores the same on either strand')),
+            # (no default: without the flag the attribute is absent, and the argument summary stamped into the output
+            # files is what it was)
+            (('--neighbors',), dict(type=int, default=argparse.SUPPRESS, metavar='K',
+                                    help='Also write phamer_neighbors.csv: the K nearest reference rows of every contig '
+                                         '(1..28; one GPU only)')),
             (('-v', '--verbose'), dict(action='store_true')),
             (('--debug',), dict(action='store_true')),
             # the rest of the reference's command line (scripts/phamer.py:515-553), so that its launch scripts
@@ -648,8 +697,16 @@ def _run(ap, args):
         os.makedirs(scorer.output_directory, exist_ok=True)
         scorer.score_points()
         lap("scored")
+        neighbors = getattr(args, "neighbors", None)
+        if neighbors is not None:      # the scores file is stamped as a run without the flag stamps it
+            args = argparse.Namespace(**{k: v for k, v in vars(args).items() if k != "neighbors"})
         scorer.make_summary_file(args=args)
         lap("scores written")
+        if neighbors is not None:
+            scorer.find_nearest_references(neighbors)
+            lap("nearest references found")
+            scorer.make_neighbors_file(args=argparse.Namespace(neighbors=neighbors, **vars(args)))
+            lap("nearest references written")
     finally:
         scorer.finish_io()
         lap("features cache complete")
