@@ -172,7 +172,7 @@ def test_batch_invariance_and_rerun(probe, placed):
     finally:
         pl.close()
         pl.close()                                                       # twice is harmless
-    assert launches["pl_init_kernel"] == 3 and launches["pl_seed_dist_kernel"] == 3 * k
+    assert launches["pl_dup_kernel"] == 3 and launches["pl_seed_dist_kernel"] == 3 * k
     assert len(set(whole["n_iter"].tolist())) > 1
     for key in whole:
         m = whole["n_members"]

@@ -21,7 +21,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from phamers_amd import _lib, kmer, learning  # noqa: E402
 
-STAGES = {"seed": ("pl_seed_dist_kernel", "pl_seed_choose_kernel", "pl_init_kernel", "pl_dup_kernel"),
+STAGES = {"seed": ("pl_seed_dist_kernel", "pl_seed_choose_kernel", "pl_dup_kernel"),
           "lloyd": ("pl_assign_kernel", "pl_update_kernel", "pl_stop_kernel"),
           "silhouettes": ("pl_members_kernel", "pl_silhouette_kernel")}
 
