@@ -34,7 +34,7 @@ __global__ __launch_bounds__(CL_THREADS) void phk_cl_silhouette_sums_kernel(
     for (uint32_t k = gbeg[g]; k < gbeg[g + 1]; ++k) {
         const uint32_t cs = cstart[k], cl = clen[k];
         double s[4][4];
-        cl_tile(X, D, nullptr, q0 + nq, qbase, perm, (uint64_t)cs + cl, cs, Qs, Cs, s);
+        cl_tile({X, nullptr, q0 + nq, qbase}, {X, perm, (uint64_t)cs + cl, cs}, D, Qs, Cs, s);
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if ((uint32_t)(tx + 16 * c) < cl) {
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(CL_THREADS) void phk_cl_count_kernel(const double *
     uint32_t c4[4] = {0, 0, 0, 0};
     for (uint64_t J = j0; J < j1; ++J) {
         double s[4][4];
-        cl_tile(X, D, nullptr, n, qbase, nullptr, n, J * CL_T, Qs, Cs, s);
+        cl_tile({X, nullptr, n, qbase}, {X, nullptr, n, J * CL_T}, D, Qs, Cs, s);
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if (J * CL_T + tx + 16 * c < n) {
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(CL_THREADS) void phk_cl_union_kernel(const double *
     const bool diag = I == J;
     if (threadIdx.x < 2 * CL_T) lp[threadIdx.x] = threadIdx.x;
     double s[4][4];
-    cl_tile(X, D, core, nc, I * CL_T, core, nc, J * CL_T, Qs, Cs, s);   // (its barriers order the lp init)
+    cl_tile({X, core, nc, I * CL_T}, {X, core, nc, J * CL_T}, D, Qs, Cs, s);   // (its barriers order the lp init)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(CL_THREADS) void phk_cl_border_kernel(const double 
     int32_t m4[4] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};
     for (uint64_t J = j0; J < j1; ++J) {
         double s[4][4];
-        cl_tile(X, D, nonc, nn, qbase, core, nc, J * CL_T, Qs, Cs, s);
+        cl_tile({X, nonc, nn, qbase}, {X, core, nc, J * CL_T}, D, Qs, Cs, s);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const uint64_t m = J * CL_T + tx + 16 * c;

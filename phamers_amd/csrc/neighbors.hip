@@ -2,7 +2,7 @@
 // what scikit-learn's NearestNeighbors(algorithm='brute').kneighbors returns over learning.distances
 // (scripts/learning.py:47-66) and what learning.knn (scripts/learning.py:118-128) folds into a vote.
 //
-// Contract: d2(q, j) = the fma chain of phk_dist2_f64_kernel (direct differences, column order); the
+// Contract: d2(q, j) = the fma chain of pair_tile.h (direct differences, column order); the
 // result of a query is the first k rows in order of (d2, j), distances sqrt(d2) -- bit for bit, whatever N, the batch
 // split, the entry point or the route.
 //
@@ -12,9 +12,10 @@
 // candidates with the exact chain and orders them by (d2, j).  (3) Certificate: with E >= |a~ - d^2| for every row of the
 // query and eps the chain's relative error, a row that was not kept has a~ >= a~_(KC), hence a chain value of at least
 // (a~_(KC) - E)(1 - eps); the query is certified when d2_(k) + E_exact < a~_(KC) - E with E_exact = 2 eps max(d2_(k),
-// a~_(KC) - E), or when every unmasked row was kept.  (4) Fallback: the other queries are gathered, run through
-// phk_dist2_f64_kernel against all rows and selected by a radix select on (d2, j) (phk_nn_select_kernel).
+// a~_(KC) - E), or when every unmasked row was kept.  (4) Fallback: the other queries are gathered, run through the pair
+// tile against all rows (phk_launch_dist2) and selected in order of (d2, j) by row_select.h (phk_nn_select_kernel).
 #include "gram_tile.h"
+#include "row_select.h"
 #include "score_model.h"
 
 #define NN_KMAX 28
@@ -188,7 +189,7 @@ __device__ __forceinline__ double nn_bound(uint64_t D, double qn, double rnmax) 
 }
 __device__ __forceinline__ double nn_eps(uint64_t D) { return 0x1p-53 * (double)(D + 4); }
 
-// KC threads per query: thread (query, c) recomputes d2 of candidate c with the chain of phk_dist2_f64_kernel, the KC pairs
+// KC threads per query: thread (query, c) recomputes d2 of candidate c with the chain of pair_tile.h, the KC pairs
 // are ordered by (d2, j) by rank, the first k go to the output (out_* at the call's query s + q) and thread 0 decides the
 // certificate; an uncertified query is appended to flist.  A NaN query row is counted in *nan_rows and left alone.
 // det_*: optional details of the call (the bound, the fallback flag, the Gram-form values of the k returned rows).
@@ -261,10 +262,8 @@ __global__ __launch_bounds__(256) void phk_nn_gather_kernel(const double *__rest
     rows[i] = Q[(uint64_t)flist[i / D] * D + i % D];
 }
 
-// One workgroup per fallen-back query: the k smallest of its M squared distances by (d2, j) -- the scheme of
-// phk_ts_select_kernel (tsne.hip): non-negative doubles order like their bit patterns, a radix select (8 passes of 8 bits)
-// finds the k-th smallest key T, entries below T are collected in any order, ties at T in index order until k are taken, a
-// bitonic sort of the 32 (key, index) slots puts them in order.  Masked rows are +inf and k <= the unmasked rows.
+// One workgroup per fallen-back query: the k smallest of its M squared distances by (d2, j) (row_select.h, 32 slots), as
+// indices, distances and the kept Gram-form values.  Masked rows are +inf and k <= the unmasked rows.
 __global__ __launch_bounds__(256) void phk_nn_select_kernel(const double *__restrict__ D2, uint64_t M, uint32_t k,
                                                             const uint32_t *__restrict__ flist, uint64_t s,
                                                             int32_t *__restrict__ out_idx, double *__restrict__ out_dist,
@@ -272,92 +271,9 @@ __global__ __launch_bounds__(256) void phk_nn_select_kernel(const double *__rest
                                                             double *__restrict__ det_a) {
     __shared__ uint64_t skey[32];
     __shared__ int32_t sidx[32];
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t wsum[4];
-    __shared__ uint64_t sh_prefix;
-    __shared__ uint32_t sh_need, sh_cnt, sh_eq;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint64_t *row = (const uint64_t *)(D2 + (uint64_t)blockIdx.x * M);
-    uint64_t prefix = 0;
-    uint32_t need = k;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        hist[t] = 0;
-        __syncthreads();
-        const uint64_t hi = shift == 56 ? 0ull : (~0ull << (shift + 8));
-        for (uint64_t j = t; j < M; j += 256) {
-            const uint64_t key = row[j];
-            if ((key & hi) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
-        }
-        __syncthreads();
-        if (t == 0) {
-            uint32_t cum = 0;
-            int b = 0;
-            for (; b < 255; ++b) {
-                if (cum + hist[b] >= need) break;
-                cum += hist[b];
-            }
-            sh_prefix = prefix | ((uint64_t)b << shift);
-            sh_need = need - cum;
-        }
-        __syncthreads();
-        prefix = sh_prefix;
-        need = sh_need;
-        __syncthreads();
-    }
-    const uint64_t T = prefix;          // the k-th smallest key; `need` of the entries equal to it are taken
-    const uint32_t nless = k - need;
-    if (t == 0) {
-        sh_cnt = 0;
-        sh_eq = 0;
-    }
-    if (t >= (int)k && t < 32) {        // padding of the sort: after every real entry
-        skey[t] = ~0ull;
-        sidx[t] = INT32_MAX;
-    }
-    __syncthreads();
-    for (uint64_t base = 0; base < M; base += 256) {
-        const uint64_t j = base + t;
-        const uint64_t key = j < M ? row[j] : ~0ull;
-        if (key < T) {
-            const uint32_t slot = atomicAdd(&sh_cnt, 1u);
-            if (slot < nless) {
-                skey[slot] = key;
-                sidx[slot] = (int32_t)j;
-            }
-        }
-        const bool eq = key == T;
-        const unsigned long long bal = __ballot(eq);
-        if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t rank = sh_eq + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) rank += wsum[w];
-        if (eq && rank < need) {
-            skey[nless + rank] = key;
-            sidx[nless + rank] = (int32_t)j;
-        }
-        __syncthreads();
-        if (t == 0) sh_eq += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
-    for (uint32_t size = 2; size <= 32; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            if (t < 32) {
-                const uint32_t e = t, o = e ^ stride;
-                if (o > e) {
-                    const uint64_t ka = skey[e], kb = skey[o];
-                    const int32_t ia = sidx[e], ib = sidx[o];
-                    const bool gt = ka > kb || (ka == kb && ia > ib);
-                    if (gt == ((e & size) == 0)) {
-                        skey[e] = kb;
-                        skey[o] = ka;
-                        sidx[e] = ib;
-                        sidx[o] = ia;
-                    }
-                }
-            }
-        }
-    __syncthreads();
+    __shared__ RsScratch sc;
+    const int t = threadIdx.x;
+    rs_select_sorted((const uint64_t *)(D2 + (uint64_t)blockIdx.x * M), M, k, 32, skey, sidx, sc);
     const uint64_t ql = flist[blockIdx.x], q = s + ql;
     if (t < (int)k) {
         out_idx[q * k + t] = sidx[t];

@@ -335,7 +335,7 @@ int phk_launch_synth_ragged(phk_ctx *ctx, uint64_t seed, uint64_t first, uint64_
 int phk_silhouettes_resident(phk_ctx *ctx, const double *d_rows, uint64_t n, uint64_t D, const uint32_t *labels, uint32_t n_labels,
                              double *out);
 // score.hip
-// out[q][x] = the direct-difference fma chain |Q[q] - X[x]|^2 (phk_dist2_f64_kernel), out[nq][nx]; masked rows -> +inf
+// out[q][x] = the direct-difference fma chain |Q[q] - X[x]|^2 (pair_tile.h; profiled as phk_dist2_f64_kernel), out[nq][nx]; masked rows -> +inf
 // (phk_mask_dist_kernel)
 int phk_launch_dist2(phk_ctx *ctx, const double *d_Q, uint64_t nq, const double *d_X, uint64_t nx, uint64_t D, double *d_out);
 int phk_launch_mask_dist(phk_ctx *ctx, double *d_dist, uint64_t nq, uint64_t M, const uint8_t *d_mask);

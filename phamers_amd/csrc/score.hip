@@ -7,72 +7,23 @@
 // combo_score_points (scripts/phamer.py:303-313).
 //
 // This file holds the EXACT float64 path: direct-difference squared distances
-// (scripts/learning.py:56 form) tiled through LDS, then per-query selection.  It serves any
-// D / M / kn and is the fall-back of the MFMA path (score_mfma.hip) for queries whose
-// candidate margin cannot be certified.
+// (scripts/learning.py:56 form) by the pair tile of pair_tile.h, then per-query selection.
+// It serves any D / M / kn and is the fall-back of the MFMA path (score_mfma.hip) for
+// queries whose candidate margin cannot be certified.
 #include <stdlib.h>
 
-#include "phk_common.h"
+#include "pair_tile.h"
 #include "score_model.h"
 
 // ------------------------------------------------------------------------------------
-// squared distances, float64, direct differences:  out[q][x] = sum_d (Q[q][d]-X[x][d])^2
-// block = 256 threads, tile = 64 queries x 64 rows, 4x4 per thread, K chunk = 16
+// squared distances, float64, direct differences:  out[q][x] = sum_d (Q[q][d]-X[x][d])^2,
+// out[nq][nx]: pair_tile.h's tile written out as it is
 // ------------------------------------------------------------------------------------
-#define DT 64
-#define DK 16
-__global__ __launch_bounds__(256) void phk_dist2_f64_kernel(const double *__restrict__ Q, uint64_t nq,
-                                                            const double *__restrict__ X, uint64_t nx,
-                                                            uint64_t D, double *__restrict__ out,
-                                                            uint64_t ld_out) {
-    __shared__ double Qs[DK][DT + 2];
-    __shared__ double Xs[DK][DT + 2];
-    const int t = threadIdx.x;
-    const int tq = t >> 4, tx = t & 15;  // 16 x 16 threads, each 4 q x 4 x
-    const uint64_t q0 = (uint64_t)blockIdx.y * DT, x0 = (uint64_t)blockIdx.x * DT;
-    double acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-
-    const int lr = t >> 2, lk = (t & 3) * 4;  // loader: row lr, 4 consecutive k at lk
-    for (uint64_t k0 = 0; k0 < D; k0 += DK) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t k = k0 + lk + j;
-            const uint64_t qr = q0 + lr, xr = x0 + lr;
-            Qs[lk + j][lr] = (qr < nq && k < D) ? Q[qr * D + k] : 0.0;
-            Xs[lk + j][lr] = (xr < nx && k < D) ? X[xr * D + k] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < DK; ++kk) {
-            double qv[4], xv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) qv[i] = Qs[kk][tq * 4 + i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xv[j] = Xs[kk][tx * 4 + j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const double d = qv[i] - xv[j];
-                    acc[i][j] = fma(d, d, acc[i][j]);
-                }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint64_t q = q0 + tq * 4 + i;
-        if (q >= nq) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t x = x0 + tx * 4 + j;
-            if (x < nx) out[q * ld_out + x] = acc[i][j];
-        }
-    }
+int phk_launch_dist2(phk_ctx *ctx, const double *d_Q, uint64_t nq, const double *d_X, uint64_t nx, uint64_t D, double *d_out) {
+    dim3 grid((unsigned)phk_div_up(nx, CL_T), (unsigned)phk_div_up(nq, CL_T));
+    PHK_LAUNCH(ctx, "phk_dist2_f64_kernel",
+               cl_matrix_kernel<ClStoreValue><<<grid, dim3(CL_THREADS), 0, ctx->stream>>>(d_Q, nq, 0, d_X, nx, D, d_out, nullptr));
+    return PHK_OK;
 }
 
 // ------------------------------------------------------------------------------------
@@ -84,12 +35,6 @@ __global__ __launch_bounds__(256) void phk_mask_dist_kernel(double *__restrict__
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nq * M) return;
     if (mask[i % M] && dist[i] == dist[i]) dist[i] = __builtin_inf();   // (a NaN query row stays NaN)
-}
-
-int phk_launch_dist2(phk_ctx *ctx, const double *d_Q, uint64_t nq, const double *d_X, uint64_t nx, uint64_t D, double *d_out) {
-    dim3 grid((unsigned)phk_div_up(nx, DT), (unsigned)phk_div_up(nq, DT));
-    PHK_LAUNCH(ctx, "phk_dist2_f64_kernel", phk_dist2_f64_kernel<<<grid, dim3(256), 0, ctx->stream>>>(d_Q, nq, d_X, nx, D, d_out, nx));
-    return PHK_OK;
 }
 
 int phk_launch_mask_dist(phk_ctx *ctx, double *d_dist, uint64_t nq, uint64_t M, const uint8_t *d_mask) {
@@ -255,14 +200,9 @@ int phk_score_exact_batch(phk_ctx *ctx, const phk_model *m, const double *d_Q, u
     if (want_knn) {
         void *dist;
         PHK_TRY(phk_ws(ctx, WS_DIST, nq * m->M * sizeof(double), &dist));
-        dim3 grid((unsigned)phk_div_up(m->M, DT), (unsigned)phk_div_up(nq, DT));
-        PHK_LAUNCH(ctx, "phk_dist2_f64_kernel",
-                   phk_dist2_f64_kernel<<<grid, dim3(256), 0, ctx->stream>>>(d_Q, nq, m->d_R64, m->M, D,
-                                                                            (double *)dist, m->M));
+        PHK_TRY(phk_launch_dist2(ctx, d_Q, nq, m->d_R64, m->M, D, (double *)dist));
         if (m->has_mask) {   // cross-validation fold: excluded train rows are infinitely far
-            PHK_LAUNCH(ctx, "phk_mask_dist_kernel",
-                       phk_mask_dist_kernel<<<dim3((unsigned)phk_div_up(nq * m->M, 256)), dim3(256), 0, ctx->stream>>>(
-                           (double *)dist, nq, m->M, m->d_col_mask));
+            PHK_TRY(phk_launch_mask_dist(ctx, (double *)dist, nq, m->M, m->d_col_mask));
         }
         PHK_LAUNCH(ctx, "phk_knn_vote_kernel",
                    phk_knn_vote_kernel<<<dim3((unsigned)phk_div_up(nq, 4)), dim3(256), 0, ctx->stream>>>(
@@ -272,10 +212,7 @@ int phk_score_exact_batch(phk_ctx *ctx, const phk_model *m, const double *d_Q, u
         const uint64_t nc = m->n_cpos + m->n_cneg;
         void *dist;
         PHK_TRY(phk_ws(ctx, WS_DIST, nq * (want_knn ? (m->M > nc ? m->M : nc) : nc) * sizeof(double), &dist));
-        dim3 grid((unsigned)phk_div_up(nc, DT), (unsigned)phk_div_up(nq, DT));
-        PHK_LAUNCH(ctx, "phk_dist2_f64_kernel",
-                   phk_dist2_f64_kernel<<<grid, dim3(256), 0, ctx->stream>>>(d_Q, nq, m->d_C64, nc, D,
-                                                                            (double *)dist, nc));
+        PHK_TRY(phk_launch_dist2(ctx, d_Q, nq, m->d_C64, nc, D, (double *)dist));
         PHK_LAUNCH(ctx, "phk_centroid_metric_kernel",
                    phk_centroid_metric_kernel<<<dim3((unsigned)phk_div_up(nq, 256)), dim3(256), 0, ctx->stream>>>(
                        (const double *)dist, nq, m->n_cpos, m->n_cneg, nc, d_cen, d_status, want_knn ? 0 : 1));
@@ -305,9 +242,7 @@ extern "C" int phk_distances(phk_ctx *ctx, const double *Q, uint64_t N, const do
     for (uint64_t s = 0; s < N; s += rows) {
         const uint64_t nb = N - s < rows ? N - s : rows;
         PHK_HIP(hipMemcpyAsync(d_q, Q + s * D, nb * D * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        dim3 grid((unsigned)phk_div_up(M, DT), (unsigned)phk_div_up(nb, DT));
-        PHK_LAUNCH(ctx, "phk_dist2_f64_kernel",
-                   phk_dist2_f64_kernel<<<grid, dim3(256), 0, ctx->stream>>>((const double *)d_q, nb, (const double *)d_x, M, D, (double *)d_o, M));
+        PHK_TRY(phk_launch_dist2(ctx, (const double *)d_q, nb, (const double *)d_x, M, D, (double *)d_o));
         PHK_LAUNCH(ctx, "phk_sqrt_kernel", phk_sqrt_kernel<<<dim3((unsigned)phk_div_up(nb * M, 256)), dim3(256), 0, ctx->stream>>>((double *)d_o, nb * M));
         PHK_HIP(hipMemcpyAsync(out + s * M, d_o, nb * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         PHK_HIP(hipStreamSynchronize(ctx->stream));

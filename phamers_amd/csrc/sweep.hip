@@ -32,26 +32,11 @@ struct phk_sweep {
 };
 
 // ---- silhouettes ----------------------------------------------------------------------------------------------------
-// d[q][j] = sqrt(sum_k (x_qk - x_jk)^2) for all pairs of the raw rows: pair_tile.h's tile, one workgroup per 64 x 64 tile
-// (tile row = blockIdx.y + y0).  The same bits for (q, j) and (j, q).
-__global__ __launch_bounds__(CL_THREADS) void sw_pair_kernel(const double *__restrict__ X, uint64_t n, uint64_t D, uint64_t y0,
-                                                            double *__restrict__ dist) {
-    __shared__ double Qs[CL_KC][CL_T + CL_PAD], Cs[CL_KC][CL_T + CL_PAD];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const uint64_t qbase = (y0 + blockIdx.y) * CL_T, cbase = (uint64_t)blockIdx.x * CL_T;
-    double s[4][4];
-    cl_tile(X, D, nullptr, n, qbase, nullptr, n, cbase, Qs, Cs, s);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const uint64_t q = qbase + ty + 16 * r;
-        if (q >= n) continue;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint64_t j = cbase + tx + 16 * c;
-            if (j < n) dist[q * n + j] = sqrt(s[r][c]);
-        }
-    }
-}
+// d[q][j] = sqrt(sum_k (x_qk - x_jk)^2) for all pairs of the raw rows: pair_tile.h's tile with the square root as its
+// stored value.  The same bits for (q, j) and (j, q).
+struct SwStoreSqrt {
+    __device__ double operator()(uint64_t, uint64_t, double s) const { return sqrt(s); }
+};
 
 // One thread per (row q, problem).  perm = the problem's rows sorted by label (stable); cluster c = perm[first[c] ..
 // first[c + 1]).  phk_cl_silhouette_sums_kernel gives the 16 threads of a query the columns tx, tx + 16, tx + 32, tx + 48
@@ -250,8 +235,9 @@ extern "C" int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint
                 const uint64_t step = std::max<uint64_t>(1, std::min<uint64_t>(65535, CL_MAX_BLOCKS / tiles));
                 for (uint64_t y0 = 0; y0 < tiles; y0 += step)
                     PHK_LAUNCH(ctx, "sw_pair_kernel",
-                               sw_pair_kernel<<<dim3((unsigned)tiles, (unsigned)std::min(step, tiles - y0)), dim3(CL_THREADS), 0,
-                                                ctx->stream>>>(sw->d_x, n, D, y0, sw->d_pair));
+                               cl_matrix_kernel<SwStoreSqrt>
+                               <<<dim3((unsigned)tiles, (unsigned)std::min(step, tiles - y0)), dim3(CL_THREADS), 0, ctx->stream>>>(
+                                   sw->d_x, n, y0, sw->d_x, n, D, sw->d_pair + y0 * CL_T * n, nullptr));
             }
         }
     }

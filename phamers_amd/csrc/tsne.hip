@@ -9,6 +9,7 @@
 // alone, so the results are bit-identical from run to run and do not depend on the number of compute units.
 #include "gram_tile.h"
 #include "pair_tile.h"
+#include "row_select.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -118,54 +119,6 @@ __global__ __launch_bounds__(256) void phk_pca_cov_kernel(const double *__restri
             }
 }
 
-// out[i][c] = sum_d (X[i][d] - mean[d]) V[c][d], in column order: the pair tile with a product in place of the squared
-// difference.  grid (component tiles, row tiles).
-__global__ __launch_bounds__(CL_THREADS) void phk_pca_project_kernel(const double *__restrict__ X, const double *__restrict__ mean,
-                                                                     uint64_t n, uint64_t D, const double *__restrict__ V,
-                                                                     uint64_t nc, double *__restrict__ out) {
-    __shared__ double Qs[CL_KC][CL_T + CL_PAD], Cs[CL_KC][CL_T + CL_PAD];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const uint64_t qbase = (uint64_t)blockIdx.y * CL_T, cbase = (uint64_t)blockIdx.x * CL_T;
-    double s[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s[r][c] = 0.0;
-    for (uint64_t k0 = 0; k0 < D; k0 += CL_KC) {
-        __syncthreads();
-        {
-            const int t = threadIdx.x, r = t >> 2, kq = (t & 3) * 4;
-            const uint64_t g = qbase + r;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint64_t k = k0 + kq + i;
-                Qs[kq + i][r] = (g < n && k < D) ? X[g * D + k] - mean[k] : 0.0;
-            }
-        }
-        cl_stage(V, D, nullptr, nc, cbase, k0, Cs);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < CL_KC; ++k) {
-            double q[4], x[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) q[r] = Qs[k][ty + 16 * r];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) x[c] = Cs[k][tx + 16 * c];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) s[r][c] = fma(q[r], x[c], s[r][c]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint64_t i = qbase + ty + 16 * r, j = cbase + tx + 16 * c;
-            if (i < n && j < nc) out[i * nc + j] = s[r][c];
-        }
-}
-
 // rows per chunk of the PCA sums: at least 1024, and few enough chunks that their D x D partials fit 256 MiB
 static uint64_t pca_chunk_rows(uint64_t n, uint64_t D) {
     const uint64_t cap = std::min<uint64_t>(65535, std::max<uint64_t>(1, TS_BYTES_256M / (D * D * sizeof(double))));   // (grid z)
@@ -217,12 +170,15 @@ extern "C" int phk_pca_project(phk_ctx *ctx, const double *X, uint64_t n, uint64
     PHK_TRY(phk_copy_to_device(ctx, d_x, X, n * D * 8));
     PHK_TRY(phk_copy_to_device(ctx, d_mean, mean, D * 8));
     PHK_TRY(phk_copy_to_device(ctx, d_v, V, nc * D * 8));
+    // out[i][c] = sum_d (X[i][d] - mean[d]) V[c][d], in column order: the pair tile with a product in place of the squared
+    // difference and the mean taken off the query side
     const uint64_t rt = phk_div_up(n, CL_T);
     for (uint64_t b0 = 0; b0 < rt; b0 += 32768) {   // (grid y < 65536)
         const uint64_t nb = std::min<uint64_t>(32768, rt - b0), rows = std::min<uint64_t>(n - b0 * CL_T, nb * CL_T);
         PHK_LAUNCH(ctx, "phk_pca_project_kernel",
-                   phk_pca_project_kernel<<<dim3((unsigned)phk_div_up(nc, CL_T), (unsigned)nb), dim3(CL_THREADS), 0, ctx->stream>>>(
-                       d_x + b0 * CL_T * D, d_mean, rows, D, d_v, nc, d_out + b0 * CL_T * nc));
+                   cl_matrix_kernel<ClStoreValue, CL_PRODUCT, true>
+                   <<<dim3((unsigned)phk_div_up(nc, CL_T), (unsigned)nb), dim3(CL_THREADS), 0, ctx->stream>>>(
+                       d_x + b0 * CL_T * D, rows, 0, d_v, nc, D, d_out + b0 * CL_T * nc, d_mean));
     }
     return phk_copy_to_host(ctx, out, d_out, n * nc * 8);
 }
@@ -230,120 +186,21 @@ extern "C" int phk_pca_project(phk_ctx *ctx, const double *X, uint64_t n, uint64
 // ---- neighbour graph ---------------------------------------------------------------------------------------------------
 #define TS_KMAX 4096   // neighbours per row the selection sorts in LDS (perplexity <= 1365)
 
-// D2[q - q0][j] = s_qj for the query rows [q0, q0 + nq) of the batch and every row j; +inf for j = q (a row is not its own
-// neighbour).  grid (column tiles, query tiles of the batch); q0 is a multiple of the tile side.
-__global__ __launch_bounds__(CL_THREADS) void phk_ts_dist_kernel(const double *__restrict__ Z, uint64_t n, uint64_t d, uint64_t q0,
-                                                                 uint64_t nq, double *__restrict__ D2) {
-    __shared__ double Qs[CL_KC][CL_T + CL_PAD], Cs[CL_KC][CL_T + CL_PAD];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const uint64_t qbase = q0 + (uint64_t)blockIdx.y * CL_T, cbase = (uint64_t)blockIdx.x * CL_T;
-    double s[4][4];
-    cl_tile(Z, d, nullptr, q0 + nq, qbase, nullptr, n, cbase, Qs, Cs, s);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint64_t q = qbase + ty + 16 * r, j = cbase + tx + 16 * c;
-            if (q < q0 + nq && j < n) D2[(q - q0) * n + j] = j == q ? __builtin_inf() : s[r][c];
-        }
-}
+// the neighbour graph's distance rows: +inf for j = q (a row is not its own neighbour)
+struct TsStoreOffDiagonal {
+    __device__ double operator()(uint64_t q, uint64_t j, double s) const { return j == q ? __builtin_inf() : s; }
+};
 
-// One workgroup per query row of the batch: the k smallest of its n distances, ordered by (distance, index).
-// Non-negative doubles order like their bit patterns, so the k-th smallest value T is found by a radix select on the 64-bit
-// keys (8 passes of 8 bits, integer histogram in LDS); entries below T are collected in any order, ties at T in index order
-// (an ordered scan) until k are taken; a bitonic sort of the k (key, index) pairs -- all distinct -- puts them in order.
+// One workgroup per query row of the batch: the k smallest of its n distances, ordered by (distance, index) (row_select.h),
+// as indices and squared distances.
 __global__ __launch_bounds__(256) void phk_ts_select_kernel(const double *__restrict__ D2, uint64_t n, uint32_t k, uint32_t kp,
                                                            uint64_t q0, int32_t *__restrict__ idx_out, double *__restrict__ d2_out) {
     __shared__ uint64_t skey[TS_KMAX];
     __shared__ int32_t sidx[TS_KMAX];
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t wsum[4];
-    __shared__ uint64_t sh_prefix;
-    __shared__ uint32_t sh_need, sh_cnt, sh_eq;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint64_t *row = (const uint64_t *)(D2 + (uint64_t)blockIdx.x * n);
-    uint64_t prefix = 0;
-    uint32_t need = k;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        hist[t] = 0;
-        __syncthreads();
-        const uint64_t hi = shift == 56 ? 0ull : (~0ull << (shift + 8));
-        for (uint64_t j = t; j < n; j += 256) {
-            const uint64_t key = row[j];
-            if ((key & hi) == prefix) atomicAdd(&hist[(key >> shift) & 255], 1u);
-        }
-        __syncthreads();
-        if (t == 0) {
-            uint32_t cum = 0;
-            int b = 0;
-            for (; b < 255; ++b) {
-                if (cum + hist[b] >= need) break;
-                cum += hist[b];
-            }
-            sh_prefix = prefix | ((uint64_t)b << shift);
-            sh_need = need - cum;
-        }
-        __syncthreads();
-        prefix = sh_prefix;
-        need = sh_need;
-        __syncthreads();
-    }
-    const uint64_t T = prefix;          // the k-th smallest key; `need` of the entries equal to it are taken
-    const uint32_t nless = k - need;
-    if (t == 0) {
-        sh_cnt = 0;
-        sh_eq = 0;
-    }
-    for (uint32_t e = k + t; e < kp; e += 256) {   // padding of the sort: after every real entry
-        skey[e] = ~0ull;
-        sidx[e] = INT32_MAX;
-    }
-    __syncthreads();
-    for (uint64_t base = 0; base < n; base += 256) {
-        const uint64_t j = base + t;
-        const uint64_t key = j < n ? row[j] : ~0ull;
-        if (key < T) {
-            const uint32_t slot = atomicAdd(&sh_cnt, 1u);
-            if (slot < nless) {
-                skey[slot] = key;
-                sidx[slot] = (int32_t)j;
-            }
-        }
-        const bool eq = key == T;
-        const unsigned long long bal = __ballot(eq);
-        if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t rank = sh_eq + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) rank += wsum[w];
-        if (eq && rank < need) {
-            skey[nless + rank] = key;
-            sidx[nless + rank] = (int32_t)j;
-        }
-        __syncthreads();
-        if (t == 0) sh_eq += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
-    for (uint32_t size = 2; size <= kp; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (uint32_t e = t; e < kp; e += 256) {
-                const uint32_t o = e ^ stride;
-                if (o > e) {
-                    const uint64_t ka = skey[e], kb = skey[o];
-                    const int32_t ia = sidx[e], ib = sidx[o];
-                    const bool gt = ka > kb || (ka == kb && ia > ib);
-                    if (gt == ((e & size) == 0)) {
-                        skey[e] = kb;
-                        skey[o] = ka;
-                        sidx[e] = ib;
-                        sidx[o] = ia;
-                    }
-                }
-            }
-        }
-    __syncthreads();
+    __shared__ RsScratch sc;
+    rs_select_sorted((const uint64_t *)(D2 + (uint64_t)blockIdx.x * n), n, k, kp, skey, sidx, sc);
     const uint64_t q = q0 + blockIdx.x;
-    for (uint32_t e = t; e < k; e += 256) {
+    for (uint32_t e = threadIdx.x; e < k; e += 256) {
         idx_out[q * k + e] = sidx[e];
         d2_out[q * k + e] = __longlong_as_double((long long)skey[e]);
     }
@@ -370,9 +227,11 @@ extern "C" int phk_tsne_neighbors(phk_ctx *ctx, const double *Z, uint64_t n, uin
     PHK_TRY(phk_copy_to_device(ctx, d_z, Z, n * d * 8));
     for (uint64_t q0 = 0; q0 < n; q0 += B) {
         const uint64_t nq = std::min(B, n - q0);
+        // d_rows[q - q0][j] = s_qj for the query rows [q0, q0 + nq) of the batch (q0 is a multiple of the tile side) and every row j
         PHK_LAUNCH(ctx, "phk_ts_dist_kernel",
-                   phk_ts_dist_kernel<<<dim3((unsigned)phk_div_up(n, CL_T), (unsigned)phk_div_up(nq, CL_T)), dim3(CL_THREADS), 0,
-                                        ctx->stream>>>(d_z, n, d, q0, nq, d_rows));
+                   cl_matrix_kernel<TsStoreOffDiagonal>
+                   <<<dim3((unsigned)phk_div_up(n, CL_T), (unsigned)phk_div_up(nq, CL_T)), dim3(CL_THREADS), 0, ctx->stream>>>(
+                       d_z, q0 + nq, q0 / CL_T, d_z, n, d, d_rows, nullptr));
         PHK_LAUNCH(ctx, "phk_ts_select_kernel",
                    phk_ts_select_kernel<<<dim3((unsigned)nq), dim3(256), 0, ctx->stream>>>(d_rows, n, (uint32_t)k, kp, q0, d_idx,
                                                                                           d_d2));
