@@ -1208,12 +1208,7 @@ int phk_count_init_device(phk_ctx *ctx) {
 // the loads); 0 = T / n
 int phk_launch_count(phk_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t T,
                      const uint64_t *d_offsets, uint64_t n, int k, uint32_t *d_counts,
-                     uint32_t *d_nwin, uint64_t mean_bases) {
-    // phk_count_score_dev may have armed the int8 operand hand-over (PhkPrep8): it stays armed for the scorer ONLY if the one
-    // kernel that writes the fragments is launched below -- every other way out of this function (tiny batches, empty batches,
-    // knobs, the wave-per-contig kernel) leaves it disarmed, and the scorer prepares its operand itself
-    const bool prep8_asked = ctx->prep8.armed;
-    ctx->prep8.armed = false;
+                     uint32_t *d_nwin, uint64_t mean_bases, PhkStepLink *link) {
     PHK_REQUIRE(k >= 1, "phk_count: k must be >= 1 (got %d)", k);
     if (k > PHK_MAX_K) {
         phk_set_error("phk_count: k=%d is above PHK_MAX_K=%d (4^k bins no longer fit LDS)", k, PHK_MAX_K);
@@ -1267,11 +1262,10 @@ int phk_launch_count(phk_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_m
             PHK_LAUNCH(ctx, "phk_count_plan_kernel",
                        phk_count_plan_kernel<<<dim3((unsigned)pb), dim3(256), 0, ctx->stream>>>(
                            d_offsets, forced ? 0 : n, k, slots, long_thr, piece_w, sorted ? 1 : 0, d_long_count, d_ctl_next,
-                           ctx->plan_zero[0], ctx->plan_zero_words[0], ctx->plan_zero[1], ctx->plan_zero_words[1]));
+                           link ? link->zero[0] : nullptr, link ? link->zero_words[0] : 0u, link ? link->zero[1] : nullptr,
+                           link ? link->zero_words[1] : 0u));
             ctx->ctl_epoch += 1;
-            ctx->plan_zero_taken = ctx->plan_zero[0] != nullptr || ctx->plan_zero[1] != nullptr;
-            ctx->plan_zero[0] = ctx->plan_zero[1] = nullptr;
-            ctx->plan_zero_words[0] = ctx->plan_zero_words[1] = 0;
+            if (link) link->planned = true;   // (the words a caller's next stage wanted zeroed, see PhkStepLink)
         }
         if (sorted) {   // returns at once on the device unless the statistics call the batch ragged
             const unsigned long long *st = (const unsigned long long *)(d_long_count + CTL_STATS);
@@ -1307,13 +1301,14 @@ int phk_launch_count(phk_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_m
         }
         // The unstaged slot kernel (phk_count_direct_kernel) for everything else the slot kernel used to count: masked batches,
         // the sorted walk of ragged batches, k = 3 and k = 5.
-        // At k = 5 without a mask it also writes the scorer's int8 operand when phk_count_score_dev armed it for this matrix.
+        // At k = 5 without a mask it also writes the scorer's int8 operand when phk_count_score_dev offered it for this matrix
+        // (PhkPrep8): `written` is set here and nowhere else -- this is the one kernel that writes the fragments.
         {
-            PhkPrep8 &pp = ctx->prep8;
-            const bool prep = k == 5 && !d_mask && prep8_asked && pp.counts == d_counts && pp.n == n && pp.D == 1024;
-            uint4 *frag8 = prep ? (uint4 *)pp.frag : nullptr;
-            uint32_t *big8 = prep ? pp.big : nullptr;
-            pp.armed = prep;   // (stays armed only if the kernel that prepares it is launched)
+            const bool prep = k == 5 && !d_mask && link && link->prep8.offered && link->prep8.counts == d_counts && link->prep8.n == n &&
+                              link->prep8.D == 1024;
+            uint4 *frag8 = prep ? (uint4 *)link->prep8.frag : nullptr;
+            uint32_t *big8 = prep ? link->prep8.big : nullptr;
+            if (link) link->prep8.written = prep;
             const size_t dlds = (size_t)phk_pow4(k) * slots * 4 + 2 * slots * 4;
             const unsigned dfit = (unsigned)((160u * 1024u - 1024u) / dlds);
             // shapes, measured (1M contigs, ms): k = 3 unmasked 0.70 (slot kernel 0.79); k = 4 masked 1.00 with 512 threads, 1.22 with 1024

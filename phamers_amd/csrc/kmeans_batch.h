@@ -357,16 +357,6 @@ static __global__ __launch_bounds__(256) void kb_stop_kernel(KbView v, uint32_t 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// workspace layout: every array starts on a 256-byte boundary
-struct KbLayout {
-    uint64_t bytes = 0;
-    uint64_t take(uint64_t b) {
-        const uint64_t o = bytes;
-        bytes += (b + 255) & ~255ull;
-        return o;
-    }
-};
-
 // grow a handle's workspace to `need` bytes (the stream is drained first: the old block may be in use)
 static inline int kb_grow(phk_ctx *ctx, void **ws, uint64_t *ws_bytes, uint64_t need, const char *fname, uint64_t problems) {
     if (*ws_bytes >= need) return PHK_OK;

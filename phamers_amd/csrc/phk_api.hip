@@ -30,12 +30,22 @@ extern "C" int phk_device_count(int *count) {
     return PHK_OK;
 }
 
+// the "proposal" option: a flavour is named by the first characters of the value; anything else is accepted and means the default
+static PhkProposal parse_proposal(const char *v) {
+    if (!v[0]) return PHK_PROP_DEFAULT;
+    if (!strncmp(v, "f1", 2)) return PHK_PROP_F16;
+    if (!strncmp(v, "hi", 2)) return PHK_PROP_HI;
+    if (!strncmp(v, "cxf", 3)) return PHK_PROP_CXF;
+    if (!strncmp(v, "i83", 3)) return PHK_PROP_I83;
+    return PHK_PROP_OTHER;
+}
+
 // one knob by name (the part after PHK_ of its environment variable, lower case)
 static int set_knob(PhkKnobs &k, const char *key, const char *value) {
     const char *v = value ? value : "";
     if (!strcmp(key, "count_lanes")) k.count_lanes = v[0];
     else if (!strcmp(key, "force_exact")) k.force_exact = v[0] == '1';
-    else if (!strcmp(key, "proposal")) snprintf(k.proposal, sizeof(k.proposal), "%s", v);
+    else if (!strcmp(key, "proposal")) k.proposal = parse_proposal(v);
     else if (!strcmp(key, "cx_cfg")) snprintf(k.cx_cfg, sizeof(k.cx_cfg), "%s", v);
     else if (!strcmp(key, "rerank")) k.rerank = v[0];
     else if (!strcmp(key, "count_sort")) k.count_sort = v[0] != '0';
@@ -552,38 +562,30 @@ extern "C" int phk_count_score_dev(phk_ctx *ctx, const phk_model *model, const u
     // one.  It lost at every chunk count, 5.32 ms unchunked against 5.71 / 6.39 / 7.94 with 2 / 4 / 8 chunks: every chunk paid
     // the latency-bound tail of the scoring chain again.  Removed in round 5; what does overlap is a batch's tail with the
     // next batch's sweep inside phk_score_fast.)
-    // k = 5: the count kernel's flush also writes the int8 operand of the scorer's sweep (PhkPrep8, phk_common.h)
-    ctx->prep8.armed = false;
+    // what the two stages of this call tell each other (PhkStepLink, phk_common.h); it ends with the call
+    PhkStepLink link;
+    // k = 5: the count kernel's flush also writes the int8 operand of the scorer's sweep (PhkPrep8)
     if (k == 5 && method != PHK_METHOD_DENSITY && method != PHK_METHOD_SVM && !d_mask && n > 0 && phk_model_has_fast(model) && model->d_A8 && !model->bf_stale && !ctx->knobs.force_exact &&
-        !ctx->knobs.proposal[0] && !ctx->knobs.count_lanes) {
+        ctx->knobs.proposal == PHK_PROP_DEFAULT && !ctx->knobs.count_lanes) {
         const uint64_t D = model->D;
         void *frag, *big;
         PHK_TRY(phk_ws(ctx, WS_FRAG8, phk_div_up(n, 32) * 32 * D, &frag));
         PHK_TRY(phk_ws(ctx, WS_BIG8, (n + 1) * sizeof(uint32_t), &big));
         PHK_HIP(hipMemsetAsync(big, 0, (n + 1) * sizeof(uint32_t), ctx->stream));
-        ctx->prep8.counts = d_counts; ctx->prep8.n = n; ctx->prep8.D = D;
-        ctx->prep8.frag = frag; ctx->prep8.big = (uint32_t *)big;
-        ctx->prep8.armed = true;
+        link.prep8.counts = d_counts; link.prep8.n = n; link.prep8.D = D;
+        link.prep8.frag = frag; link.prep8.big = (uint32_t *)big;
+        link.prep8.offered = true;
     }
     // the scorer's NaN counter and the call totals of its statistics are zeroed by the count planner's kernel where there is
-    // one (no memset in front of either stage); phk_score_rows does it itself otherwise
-    ctx->plan_zero[0] = d_status;
-    ctx->plan_zero_words[0] = d_status ? 1u : 0u;
+    // one (no memset in front of either stage); the scorer does it itself otherwise
+    link.zero[0] = d_status;
+    link.zero_words[0] = d_status ? 1u : 0u;
     const bool totals_ready = phk_model_has_fast(model) && !ctx->knobs.force_exact && ctx->ws[WS_SCTL].ptr && !ctx->score_ctl_dirty &&
                               ctx->score_ctl_gen == ctx->ws[WS_SCTL].gen;
-    ctx->plan_zero[1] = totals_ready ? (uint32_t *)ctx->ws[WS_SCTL].ptr : nullptr;
-    ctx->plan_zero_words[1] = totals_ready ? 32u : 0u;
-    ctx->plan_zero_taken = false;
-    int rc = phk_launch_count(ctx, d_packed, d_mask, total_bases, d_offsets, n, k, d_counts, nwin);
-    ctx->plan_zero[0] = ctx->plan_zero[1] = nullptr;
-    ctx->plan_zero_words[0] = ctx->plan_zero_words[1] = 0;
-    ctx->score_totals_zeroed = ctx->plan_zero_taken;   // (consumed by phk_score_rows)
-    ctx->score_totals_only_status = ctx->plan_zero_taken && !totals_ready;
-    ctx->plan_zero_taken = false;
-    if (rc == PHK_OK) rc = phk_score_rows(ctx, model, nullptr, d_counts, nwin, n, method, d_scores, d_status);
-    ctx->prep8.armed = false;
-    ctx->score_totals_zeroed = ctx->score_totals_only_status = false;
-    return rc;
+    link.zero[1] = totals_ready ? (uint32_t *)ctx->ws[WS_SCTL].ptr : nullptr;
+    link.zero_words[1] = totals_ready ? 32u : 0u;
+    PHK_TRY(phk_launch_count(ctx, d_packed, d_mask, total_bases, d_offsets, n, k, d_counts, nwin, 0, &link));
+    return phk_score_rows(ctx, model, nullptr, d_counts, nwin, n, method, d_scores, d_status, &link);
 }
 
 extern "C" int phk_check_counts_dev(phk_ctx *ctx, const uint32_t *d_counts, const uint32_t *d_other, uint64_t n, uint64_t D,

@@ -99,13 +99,30 @@ struct PhkTimed {
     uint64_t launches = 0;
 };
 
+// workspace layout: hands out consecutive pieces of one allocation, every piece starting on a multiple of `align` bytes
+struct PhkLayout {
+    uint64_t bytes = 0;
+    uint64_t align = 256;
+    uint64_t take(uint64_t b) {
+        const uint64_t o = bytes;
+        bytes += (b + align - 1) / align * align;
+        return o;
+    }
+};
+
+// the "proposal" option (phk_set_option / PHK_PROPOSAL) as set_knob parses it.  A value that names no flavour is accepted
+// and scores as the default does (PHK_PROP_OTHER); like every set value it keeps phk_count_score_dev from offering the int8
+// operand hand-over.
+enum PhkProposal { PHK_PROP_DEFAULT = 0, PHK_PROP_OTHER, PHK_PROP_F16, PHK_PROP_HI, PHK_PROP_CXF, PHK_PROP_I83 };
+
 // Tuning / diagnostic knobs.  Read ONCE from the environment when the context is created (PHK_<NAME>), changed
 // afterwards only through phk_set_option(): no launch path calls getenv.
 struct PhkKnobs {
-    char count_lanes = 0;      // '0' wave-per-contig kernel only, '1' slot kernel by the batch statistics, '2' slot kernel whatever the
-                               // batch looks like, 'p' / 'P' (forced: 'q' / 'Q') two-windows-per-add kernel with 512 / 1024 threads (k = 4, no mask)
+    char count_lanes = 0;      // which count kernel (phk_launch_count): '0' the wave-per-contig kernel only; 'f' the unstaged slot kernel whatever
+                               // the batch looks like; 'p' / 'P' the two-windows-per-add kernel with 512 / 1024 threads where the batch
+                               // statistics allow (k = 4, no mask), 'q' / 'Q' the same, forced; 'd' / 'D' the slot kernel with 512 / 1024 threads; 0 = default
     bool force_exact = false;  // every model through the float64 path
-    char proposal[8] = "";     // "f32" fp32 MFMA, "f16" split-query f16, "cx2" count-exact with 2 MFMAs per k-step
+    PhkProposal proposal = PHK_PROP_DEFAULT;   // first pass of the fast scorer, parsed once by set_knob (see the table at ScoreRoute, score_mfma.hip)
     char cx_cfg[8] = "";       // "<tiles per wave><waves per workgroup>": 14, 24, 28
     char rerank = 0;           // 'w' wave per query, 'g' 16 lanes per query for all
     bool count_sort = true;    // length-bucketed contig order for the slot count kernel on ragged batches
@@ -128,16 +145,32 @@ struct PhkKnobs {
 #define PHK_PREP8_MISSING 0x40000000u
 #define PHK_I8_L1_MAX 65000u   // |c - c0|_1 of a row the sweep epilogue's 32-bit fold is exact for: (256 * 127 + 128) * 65000 < 2^31
 struct PhkPrep8 {
-    bool armed = false;
+    bool offered = false;               // phk_count_score_dev: the buffers below exist and belong to `counts`
+    bool written = false;               // phk_launch_count: the one kernel that writes the fragments was launched for this matrix --
+                                        // every other way through it (tiny or empty batches, knobs, the wave-per-contig kernel)
+                                        // leaves it false, and the scorer prepares its operand itself
     const uint32_t *counts = nullptr;   // the count matrix the fragments belong to
     uint64_t n = 0, D = 0;
     void *frag = nullptr;               // [ceil(n / 32)][D / 32][64 lanes] x 16 bytes
     uint32_t *big = nullptr;            // [n + 1]
 };
 
+// What the count stage and the score stage of ONE phk_count_score_dev call tell each other.  It lives on that call's stack
+// and is passed down as an optional trailing pointer (phk_launch_count, phk_score_rows, phk_score_fast,
+// phk_launch_proposal_i8_general); every other caller passes none: the scorer then zeroes its own words with a memset and
+// prepares its own operand.  Nothing of it is kept in the context, so a call that fails half way leaves nothing behind.
+struct PhkStepLink {
+    PhkPrep8 prep8;
+    // words the count planner's kernel is asked to zero beside its own -- [0] the scorer's NaN counter, [1] the call totals of
+    // its statistics (WS_SCTL) -- so that no memset stands in front of either stage; `planned` = that kernel was launched
+    uint32_t *zero[2] = {nullptr, nullptr};
+    uint32_t zero_words[2] = {0, 0};
+    bool planned = false;
+    bool zeroed(const uint32_t *p) const { return planned && p && (p == zero[0] || p == zero[1]); }
+};
+
 struct phk_ctx {
     int device = 0;
-    PhkPrep8 prep8;
     PhkKnobs knobs;
     bool slots_lds0 = true;        // the slot count kernel's dynamic LDS starts at address 0 (checked at creation)
     hipStream_t stream = nullptr;
@@ -155,13 +188,6 @@ struct phk_ctx {
     // the scorer's control words (phk_score_fast, WS_SCTL): zeroed by the kernels that read them last; see there
     uint64_t score_ctl_gen = 0;
     bool score_ctl_dirty = true;
-    bool score_totals_zeroed = false;   // this call's NaN counter (and totals) were zeroed by the count planner's kernel ...
-    bool score_totals_only_status = false;   // ... the NaN counter only (the totals' workspace did not exist yet)
-    // words another entry point wants zeroed by the planning kernel (phk_count_score_dev: the scorer's NaN counter and call
-    // totals), consumed by the next phk_launch_count that launches a planning kernel; `taken` says it did
-    uint32_t *plan_zero[2] = {nullptr, nullptr};
-    uint32_t plan_zero_words[2] = {0, 0};
-    bool plan_zero_taken = false;
     int num_cus = 256;
     PhkBuf ws[WS_SLOTS];
     bool profile = false;
@@ -306,7 +332,7 @@ int phk_launch_deline_pack(phk_ctx *ctx, const uint8_t *d_raw, const uint8_t *d_
                            uint32_t *d_mask, uint32_t *d_any_invalid);
 int phk_launch_count(phk_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t T,
                      const uint64_t *d_offsets, uint64_t n, int k, uint32_t *d_counts,
-                     uint32_t *d_nwin, uint64_t mean_bases = 0);
+                     uint32_t *d_nwin, uint64_t mean_bases = 0, PhkStepLink *link = nullptr);
 int phk_launch_widen(phk_ctx *ctx, const uint32_t *d_in, uint64_t count, int64_t *d_out);
 int phk_launch_normalize_u32(phk_ctx *ctx, const uint32_t *d_counts, uint64_t n, uint64_t D,
                              double *d_out);
@@ -341,4 +367,5 @@ int phk_launch_dist2(phk_ctx *ctx, const double *d_Q, uint64_t nq, const double 
 int phk_launch_mask_dist(phk_ctx *ctx, double *d_dist, uint64_t nq, uint64_t M, const uint8_t *d_mask);
 struct phk_model;
 int phk_score_rows(phk_ctx *ctx, const phk_model *m, const double *d_Q, const uint32_t *d_counts,
-                   const uint32_t *d_rowsum, uint64_t N, int method, double *d_scores, uint32_t *d_status);
+                   const uint32_t *d_rowsum, uint64_t N, int method, double *d_scores, uint32_t *d_status,
+                   const PhkStepLink *link = nullptr);

@@ -199,7 +199,7 @@ extern "C" int phk_placement_run(phk_ctx *ctx, phk_placement *pl, const double *
         }
     const uint64_t Bc = std::min<uint64_t>(B, chunk ? chunk : PL_DEFAULT_CHUNK);
     // the chunk's workspace
-    KbLayout ws;
+    PhkLayout ws;
     const uint64_t o_z = ws.take(Bc * D * 8), o_mean = ws.take(Bc * D * 8), o_cen = ws.take(Bc * 2 * k * D * 8),
                    o_lab = ws.take(Bc * n1 * 4), o_clo = ws.take(Bc * n1 * 8), o_td = ws.take(Bc * T * n1 * 8),
                    o_cand = ws.take(Bc * KB_MAX_TRIALS * 4), o_seed = ws.take(Bc * k * 4), o_size = ws.take(Bc * k * 4),

@@ -60,7 +60,7 @@ struct RerankParams {
     // candidate lists sit at the dense positions 0 .. min(*map_count, N) of a second list set of capacity N
     const uint32_t *map = nullptr;
     const uint32_t *map_count = nullptr;
-    uint32_t *counters = nullptr;           // the batch's counter words (see phk_score_fast)
+    uint32_t *counters = nullptr;           // the batch's counter words (see ScoreSet, score_mfma.hip)
     // Statistics that most waves of a large grid increment -- decisions by exact distances, the reasons a query is handed on --
     // are counted in PHK_STRIPES copies of the counter words, each in a cache line of its own, chosen by the workgroup number,
     // and summed by phk_fallback_merge_kernel.  As atomics on the batch's ONE line of counters they were a serial resource the

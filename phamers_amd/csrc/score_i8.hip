@@ -697,14 +697,15 @@ __global__ void phk_merge_list_sets_kernel(float *__restrict__ cv, uint32_t *__r
 // proposal pass for uint32 counts at D = 512 .. 4096: row sums (if needed) -> int8 query fragments -> sweep (-> merge)
 int phk_launch_proposal_i8_general(phk_ctx *ctx, const phk_model *m, const uint32_t *d_counts, const uint32_t *d_rowsum, uint64_t nb,
                                    uint32_t nref, uint32_t npos, uint32_t nneg, float *cv, uint32_t *ci, float *cu, uint32_t groups,
-                                   uint64_t set_bytes, bool two_parts) {
+                                   uint64_t set_bytes, bool two_parts, const PhkStepLink *link) {
     const uint64_t D = m->D, nchunk = D / (32 * I8_KS), nchunk256 = D / 256;
     const uint64_t nqb = phk_div_up(nb, 32);
     void *bq, *rs = nullptr, *bg;
     // the operand the count kernel prepared (phk_count_score_dev), when this batch is a whole-block range of its matrix
-    const PhkPrep8 &pp = ctx->prep8;
-    const uint64_t r0 = pp.armed && d_counts >= pp.counts ? (uint64_t)(d_counts - pp.counts) / D : 0;
-    const bool prepared = pp.armed && pp.D == D && d_counts >= pp.counts && (uint64_t)(d_counts - pp.counts) % D == 0 && r0 % 32 == 0 &&
+    const PhkPrep8 none;   // (no link: nothing prepared)
+    const PhkPrep8 &pp = link ? link->prep8 : none;
+    const uint64_t r0 = pp.written && d_counts >= pp.counts ? (uint64_t)(d_counts - pp.counts) / D : 0;
+    const bool prepared = pp.written && pp.D == D && d_counts >= pp.counts && (uint64_t)(d_counts - pp.counts) % D == 0 && r0 % 32 == 0 &&
                           r0 + nb <= pp.n && (nb % 32 == 0 || r0 + nb == pp.n);
     if (prepared) {
         bq = (char *)pp.frag + (r0 / 32) * (D / 32) * 1024;

@@ -242,7 +242,7 @@ extern "C" int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint
         }
     }
     // the chunk's workspace
-    KbLayout ws;
+    PhkLayout ws;
     const uint64_t o_cen = ws.take(2 * ksum_max * D * 8), o_lab = ws.take(Sc * n * 4), o_clo = ws.take(Sc * n * 8),
                    o_td = ws.take(Sc * KB_MAX_TRIALS * n * 8), o_cand = ws.take(Sc * KB_MAX_TRIALS * 4),
                    o_seed = ws.take(ksum_max * 4), o_size = ws.take(ksum_max * 4), o_st = ws.take(Sc * sizeof(KbState)),
