@@ -430,6 +430,22 @@ int phk_silhouettes(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const
 int phk_dbscan(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, double eps, uint64_t min_samples, int64_t *labels,
                uint8_t *core, uint64_t *n_clusters);
 
+/* ---- the DBSCAN eps x min_samples sweep (the parameters of learning.dbscan, scripts/learning.py:149-163).
+ * The rows X[n][D] stay on the device (phk_dbscan_sweep_create; host pointer, float64; PHK_ERR_NAN for NaN rows).
+ * phk_dbscan_sweep solves the C cells (eps[c], min_samples[c]), 1 <= C <= 64, in one call: every pair distance is computed
+ * once per pass and serves all cells.  Per cell the result is phk_dbscan's for that cell alone:
+ *   labels[C][n] int32 (-1 = noise), n_clusters[C] (may be NULL);
+ *   coremask[n] (may be NULL): bit c = row i is a core sample of cell c.
+ * tiles_per_launch: at most that many 64 x 64 pair tiles per launch of the count, union and border passes (0 = the
+ * default); launches[3] (may be NULL) = the launches each of the three took.  A cell's results do not depend on C, on its
+ * place in the list, on the other cells or on tiles_per_launch.  PHK_ERR_ARG for eps not finite and > 0, min_samples < 1
+ * or C outside 1..64. */
+typedef struct phk_dbscan_rows phk_dbscan_rows;
+int phk_dbscan_sweep_create(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, phk_dbscan_rows **out);
+int phk_dbscan_sweep_destroy(phk_ctx *ctx, phk_dbscan_rows *rows);
+int phk_dbscan_sweep(phk_ctx *ctx, phk_dbscan_rows *rows, uint32_t C, const double *eps, const uint64_t *min_samples,
+                     uint64_t tiles_per_launch, int32_t *labels, uint64_t *coremask, uint64_t *n_clusters, uint32_t *launches);
+
 /* ---- batched per-contig placement (results_analyzer.get_taxonomy_prediction_dict, scripts/analysis.py:754-792; DESIGN.md
  * 4.9).  The reference rows X[n][D] stay on the device; phk_placement_run solves, for each of the B rows of Z[B][D], the
  * problem "k-means of X with the row appended (row n), then the silhouettes of the members of that row's cluster", the

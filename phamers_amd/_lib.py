@@ -108,6 +108,9 @@ SIGNATURES = {
     "phk_distances": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_silhouettes": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_void_p]),
     "phk_dbscan": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_double, c_u64, c_void_p, c_void_p, P(c_u64)]),
+    "phk_dbscan_sweep_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, P(c_void_p)]),
+    "phk_dbscan_sweep_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_dbscan_sweep": (c_int, [c_void_p, c_void_p, c_u32, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_placement_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, P(c_void_p)]),
     "phk_placement_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_placement_run": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u32, c_u32, c_void_p, c_double, c_int, c_u32, c_void_p,
@@ -640,6 +643,37 @@ def dbscan(ctx, X, eps, min_samples):
     check(ctx.lib.phk_dbscan(ctx.handle, ptr(X), X.shape[0], X.shape[1], float(eps), int(min_samples), ptr(labels), ptr(core),
                              ctypes.byref(k)))
     return labels, core.astype(bool), int(k.value)
+
+
+class DbscanRows(object):
+    """Rows resident on the device for the DBSCAN parameter sweep (phk_dbscan_sweep_create); ``run`` solves up to 64 cells."""
+
+    def __init__(self, ctx, X):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("X must be 2-D")
+        self.ctx, self.n = ctx, X.shape[0]
+        h = ctypes.c_void_p()
+        check(ctx.lib.phk_dbscan_sweep_create(ctx.handle, ptr(X), X.shape[0], X.shape[1], ctypes.byref(h)))
+        self.handle = h
+
+    def run(self, eps, min_samples, tiles_per_launch=0):
+        """The cells (eps[c], min_samples[c]): {labels (C, n) int32, coremask (n,) uint64, n_clusters (C,), launches (3,)}."""
+        eps = np.ascontiguousarray(eps, dtype=np.float64)
+        ms = np.ascontiguousarray(min_samples, dtype=np.uint64)
+        C = eps.shape[0]
+        if eps.ndim != 1 or ms.shape != eps.shape:
+            raise ValueError("one eps and one min_samples per cell")
+        out = {"labels": np.empty((C, self.n), dtype=np.int32), "coremask": np.empty(self.n, dtype=np.uint64),
+               "n_clusters": np.empty(C, dtype=np.uint64), "launches": np.zeros(3, dtype=np.uint32)}
+        check(self.ctx.lib.phk_dbscan_sweep(self.ctx.handle, self.handle, C, ptr(eps), ptr(ms), int(tiles_per_launch),
+                                            ptr(out["labels"]), ptr(out["coremask"]), ptr(out["n_clusters"]), ptr(out["launches"])))
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.phk_dbscan_sweep_destroy(self.ctx.handle, self.handle)
+            self.handle = None
 
 
 def svm_gamma(X, gamma):

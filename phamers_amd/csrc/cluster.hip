@@ -1,6 +1,7 @@
 // cluster.hip -- the clustering analysis of PhaMers' scripts/learning.py on the device (gfx950):
 //   phk_silhouettes : learning.silhouettes (:84-92, scikit-learn silhouette_samples)
 //   phk_dbscan      : learning.dbscan (:149-163, scikit-learn DBSCAN(eps, min_samples).fit(X).labels_)
+// (phk_dbscan_sweep, the same for a whole eps x min_samples grid in one pass over the pairs: dbscan_sweep.hip)
 //
 // Both are all-pairs passes over X[n][D] float64.  Every pass is built on one pair tile: 64 query rows x 64 column rows,
 // 256 threads, each thread a 4 x 4 block of pairs (queries ty + 16 r, columns tx + 16 c); KC columns of both row sets are
@@ -10,6 +11,7 @@
 //
 // DBSCAN's neighbour test d_ij <= eps is decided as s_ij <= t, t = the largest double whose correctly rounded square root
 // is <= eps (computed on the host): exactly the float64 decision sqrt(s_ij) <= eps.
+#include "cluster_shared.h"
 #include "pair_tile.h"
 
 #include <algorithm>
@@ -105,65 +107,7 @@ __global__ __launch_bounds__(CL_THREADS) void phk_cl_count_kernel(const double *
     }
 }
 
-// Union-find on the parent array of the core points (compact indices: core point m is row core[m] of X; compact order is
-// row order).  The larger root is hooked under the smaller, so a component's root is its smallest member.  The array is
-// written by workgroups on all XCDs at once and the XCD L2s are not coherent: every access here is an agent-scope atomic.
-__device__ __forceinline__ int32_t uf_load(int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int32_t uf_find(int32_t *parent, int32_t x) {
-    for (;;) {
-        const int32_t p = uf_load(parent + x);
-        if (p == x) return x;
-        const int32_t gp = uf_load(parent + p);
-        if (gp != p) {   // path halving: parent[x] moves to an ancestor only
-            int32_t e = p;
-            __hip_atomic_compare_exchange_strong(parent + x, &e, gp, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        x = gp;
-    }
-}
-
-__device__ __forceinline__ void uf_union(int32_t *parent, int32_t a, int32_t b) {
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a > b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        int32_t e = b;   // b is (was) a root: hook it under the smaller root a
-        if (__hip_atomic_compare_exchange_strong(parent + b, &e, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return;
-    }
-}
-
-// the same on the tile's 128 slots in LDS (one workgroup: workgroup-scope atomics)
-__device__ __forceinline__ int lf_find(int *lp, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(lp + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-__device__ __forceinline__ void lf_union(int *lp, int a, int b) {
-    for (;;) {
-        a = lf_find(lp, a);
-        b = lf_find(lp, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        int e = b;
-        if (__hip_atomic_compare_exchange_strong(lp + b, &e, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-            return;
-    }
-}
-
+// (The union-find on the parent array and on the LDS slots -- uf_union, lf_union -- is in cluster_shared.h.)
 // Pass 2: joins every core-core neighbour pair.  Tile (I, J) of the core points with I <= J (symmetry: d_ij = d_ji bit for
 // bit); its edges are first joined on 128 slots in LDS (slot r: core point 64 I + r, slot 64 + c: core point 64 J + c; the
 // diagonal tile uses slots 0..63 for both), then each slot is joined to its LDS root in the global parent array: at most
@@ -259,18 +203,15 @@ __global__ __launch_bounds__(256) void phk_cl_fill_kernel(int32_t *__restrict__ 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-// X to the device (WS_WIDE) and the NaN check.  Returns the device copy.
-static int cl_upload(phk_ctx *ctx, const char *fname, const double *X, uint64_t n, uint64_t D, uint64_t extra_bytes,
-                     double **d_x, void **d_extra) {
-    void *p, *flags;
-    const uint64_t xb = (n * D * sizeof(double) + 255) & ~255ull;
-    PHK_TRY(phk_ws(ctx, WS_WIDE, xb + extra_bytes, &p));
+// PHK_ERR_NAN when any of the `count` doubles at d_p (device) is NaN; returns with the stream idle (dbscan_sweep.hip calls it too)
+int cl_refuse_nan(phk_ctx *ctx, const char *fname, const double *d_p, uint64_t count) {
+    void *flags;
     PHK_TRY(phk_ws(ctx, WS_FLAGS, 64, &flags));
-    PHK_TRY(phk_copy_to_device(ctx, p, X, n * D * sizeof(double)));
     PHK_HIP(hipMemsetAsync(flags, 0, sizeof(uint32_t), ctx->stream));
-    const uint64_t blocks = std::min<uint64_t>(phk_div_up(n * D, 256), 4096);
-    PHK_LAUNCH(ctx, "phk_cl_nan_kernel",
-               phk_cl_nan_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>((const double *)p, n * D, (uint32_t *)flags));
+    const uint64_t blocks = std::min<uint64_t>(phk_div_up(count, 256), 4096);
+    if (blocks)
+        PHK_LAUNCH(ctx, "phk_cl_nan_kernel",
+                   phk_cl_nan_kernel<<<dim3((unsigned)blocks), dim3(256), 0, ctx->stream>>>(d_p, count, (uint32_t *)flags));
     uint32_t bad = 0;
     PHK_HIP(hipMemcpyAsync(&bad, flags, 4, hipMemcpyDeviceToHost, ctx->stream));
     PHK_HIP(hipStreamSynchronize(ctx->stream));
@@ -278,13 +219,24 @@ static int cl_upload(phk_ctx *ctx, const char *fname, const double *X, uint64_t 
         phk_set_error("%s: the data contain NaN", fname);
         return PHK_ERR_NAN;
     }
+    return PHK_OK;
+}
+
+// X to the device (WS_WIDE) and the NaN check.  Returns the device copy.
+static int cl_upload(phk_ctx *ctx, const char *fname, const double *X, uint64_t n, uint64_t D, uint64_t extra_bytes,
+                     double **d_x, void **d_extra) {
+    void *p;
+    const uint64_t xb = (n * D * sizeof(double) + 255) & ~255ull;
+    PHK_TRY(phk_ws(ctx, WS_WIDE, xb + extra_bytes, &p));
+    PHK_TRY(phk_copy_to_device(ctx, p, X, n * D * sizeof(double)));
+    PHK_TRY(cl_refuse_nan(ctx, fname, (const double *)p, n * D));
     *d_x = (double *)p;
     *d_extra = (char *)p + xb;
     return PHK_OK;
 }
 
 // workgroups per query block so that a launch fills the chip (~8 workgroups per CU), at most `tiles`
-static uint32_t cl_groups(phk_ctx *ctx, uint64_t qblocks, uint64_t tiles) {
+uint32_t cl_groups(phk_ctx *ctx, uint64_t qblocks, uint64_t tiles) {
     const uint64_t want = (uint64_t)ctx->num_cus * 8;
     uint64_t g = qblocks >= want ? 1 : phk_div_up(want, qblocks);
     if (g > tiles) g = tiles;
@@ -388,7 +340,7 @@ int phk_silhouettes_resident(phk_ctx *ctx, const double *d_rows, uint64_t n, uin
 }
 
 // the largest double t with sqrt(t) <= eps (sqrt correctly rounded and monotone): s <= t  <=>  sqrt(s) <= eps
-static double cl_eps_threshold(double eps) {
+double cl_eps_threshold(double eps) {
     double t = eps * eps;
     while (std::sqrt(t) > eps) t = std::nextafter(t, 0.0);
     for (;;) {

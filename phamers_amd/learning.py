@@ -8,6 +8,8 @@ learning.py -- drop-in for the hot-path helpers of PhaMers' scripts/learning.py.
     get_centroids(data, assignment)               scripts/learning.py:69-81     -> NumPy (86 means)
     get_density(point, data, bandwidth=0.1)       scripts/learning.py:107-115   -> GPU (float64 Gaussian KDE, log_density batched)
     dbscan(data, eps, min_samples, ...)           scripts/learning.py:149-163   -> GPU (neighbour counts + lock-free union-find)
+    dbscan_sweep(data, eps_values, min_samples_values)   (the choice of dbscan's parameters) -> GPU, every cell of the grid in one pass over the pairs (phk_dbscan_sweep)
+    kdistances(data, k)                           (the k-distance curve)        -> GPU kneighbors, sorted k-th distances
     silhouettes(data, assignment)                 scripts/learning.py:84-92     -> GPU (float64 cluster distance sums)
     cluster_silhouettes(data, assignment, c)      scripts/learning.py:95-104    -> GPU silhouettes of one cluster's members
     place_contigs(reference, contigs, k)          scripts/analysis.py:771-776   -> GPU, all contigs as one batch (phk_placement_run)
@@ -432,17 +434,94 @@ def dbscan(data, eps, min_samples, sort_by_size=False):
 
 def dbscan_fit(data, eps, min_samples):
     """(labels_, core_sample_indices_) of ``DBSCAN(eps=eps, min_samples=min_samples).fit(data)``."""
+    eps, min_samples = _check_dbscan_parameters(eps, min_samples)
+    X = _check_rows(data)
+    if X.shape[0] == 0:
+        raise ValueError("Found array with 0 sample(s) (shape=%s) while a minimum of 1 is required." % (X.shape,))
+    labels, core, _ = _lib.dbscan(_lib.get_context(), X, eps, int(min_samples))
+    return labels, np.flatnonzero(core)
+
+
+def _check_dbscan_parameters(eps, min_samples):
+    """dbscan_fit's ValueErrors for one eps / one min_samples; returns them as (float, int)."""
     eps = float(eps)
     if not (np.isfinite(eps) and eps > 0.0):
         raise ValueError("The 'eps' parameter of DBSCAN must be a float in the range (0.0, inf). Got %r instead." % (eps,))
     if isinstance(min_samples, (bool, np.bool_)) or not isinstance(min_samples, (int, np.integer)) or min_samples < 1:
         raise ValueError("The 'min_samples' parameter of DBSCAN must be an int in the range [1, inf). Got %r instead."
                          % (min_samples,))
+    return eps, int(min_samples)
+
+
+DBSCAN_SWEEP_MAX_CELLS = 64   # cells of one device pass (one bit each of a row's core mask)
+
+
+def dbscan_sweep(data, eps_values, min_samples_values, silhouettes=False, _cells_per_pass=DBSCAN_SWEEP_MAX_CELLS,
+                 _tiles_per_launch=0, _details=None):
+    """DBSCAN for every cell of the grid ``eps_values`` x ``min_samples_values`` on the same rows -- what a loop of
+    ``dbscan_fit`` per cell returns -- with the rows uploaded once and ONE pass over the pairs per stage for up to 64 cells
+    (phk_dbscan_sweep; more cells run as several passes over the same resident rows).  Returns one dict per cell in the
+    order ``for eps in eps_values: for m in min_samples_values`` (the values as given, duplicates kept): ``eps``,
+    ``min_samples``, ``labels`` (n,) int64 (-1 = noise) and ``core_sample_indices`` as ``dbscan_fit`` returns them,
+    ``n_clusters``, ``n_core``, ``n_border``, ``n_noise``, ``largest`` (the size of the largest cluster, 0 without one) and
+    ``route`` ('device').  The ValueErrors are ``dbscan_fit``'s, raised for every value before any device work; empty value
+    lists return [].  With ``silhouettes`` a record also has ``silhouette``: ``silhouette_score`` of the rows with a label
+    >= 0, NaN unless 2 <= n_clusters <= (number of such rows) - 1.  That is the existing single-problem pass, once per
+    cell: the sweep does not fuse it.  ``_cells_per_pass`` / ``_tiles_per_launch`` / ``_details`` are for the tests: cells
+    per device pass, pair tiles per launch, and a dict that receives ``passes`` and per pass the ``launches`` of the count,
+    union and border stages."""
+    eps_list = [e for e in np.asarray(eps_values, dtype=object).ravel().tolist()]
+    ms_list = [m for m in np.asarray(min_samples_values, dtype=object).ravel().tolist()]
+    eps_list = [_check_dbscan_parameters(e, 1)[0] for e in eps_list]
+    ms_list = [_check_dbscan_parameters(1.0, m)[1] for m in ms_list]
+    per_pass = int(_cells_per_pass)
+    if not 1 <= per_pass <= DBSCAN_SWEEP_MAX_CELLS:
+        raise ValueError("_cells_per_pass = %d is not in 1..%d" % (per_pass, DBSCAN_SWEEP_MAX_CELLS))
     X = _check_rows(data)
     if X.shape[0] == 0:
         raise ValueError("Found array with 0 sample(s) (shape=%s) while a minimum of 1 is required." % (X.shape,))
-    labels, core, _ = _lib.dbscan(_lib.get_context(), X, eps, int(min_samples))
-    return labels, np.flatnonzero(core)
+    cells = [(e, m) for e in eps_list for m in ms_list]
+    if not cells:
+        return []
+    n = X.shape[0]
+    records, launches = [], []
+    rows = _lib.DbscanRows(_lib.get_context(), X)
+    try:
+        for c0 in range(0, len(cells), per_pass):
+            part = cells[c0:c0 + per_pass]
+            out = rows.run([e for e, _ in part], [m for _, m in part], _tiles_per_launch)
+            launches.append(out["launches"].tolist())
+            for c, (e, m) in enumerate(part):
+                labels = out["labels"][c].astype(np.int64)
+                core = (out["coremask"] >> np.uint64(c)) & np.uint64(1) != 0
+                sizes = np.bincount(labels[labels >= 0], minlength=1)
+                n_noise = int(np.count_nonzero(labels < 0))
+                n_core = int(np.count_nonzero(core))
+                records.append({"eps": e, "min_samples": m, "labels": labels, "core_sample_indices": np.flatnonzero(core),
+                                "n_clusters": int(out["n_clusters"][c]), "n_core": n_core, "n_border": n - n_core - n_noise,
+                                "n_noise": n_noise, "largest": int(sizes.max()), "route": "device"})
+    finally:
+        rows.close()
+    if _details is not None:
+        _details["passes"] = len(launches)
+        _details["launches"] = launches
+    if silhouettes:
+        for record in records:
+            clustered = record["labels"] >= 0
+            m = int(np.count_nonzero(clustered))
+            record["silhouette"] = silhouette_score(X[clustered], record["labels"][clustered]) \
+                if 2 <= record["n_clusters"] <= m - 1 else float("nan")
+    return records
+
+
+def kdistances(data, k):
+    """The distance from every row of ``data`` to its k-th nearest row, the row itself counting as the first, sorted
+    ascending: the usual curve for choosing DBSCAN's eps by eye.  From ``kneighbors(data, data, k)``, so 1 <= k <= 28 and the
+    distances are the direct-difference ones ``dbscan`` and ``dbscan_sweep`` decide on: a row is a core sample at
+    (eps, min_samples) exactly when its min_samples-th distance is <= eps."""
+    data = np.asarray(data, dtype=np.float64)
+    d, _ = kneighbors(data, data, k)
+    return np.sort(d[:, int(k) - 1])
 
 
 def silhouettes(data, assignment):
