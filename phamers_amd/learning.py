@@ -177,7 +177,7 @@ def kmeans_reference_on_device(data, k, seed=kmeans_seed, max_iter=300, tol=1e-4
     ``RandomState(seed)`` -- what ``KMeans.fit`` does before its first sweep, n_init = 1) and its Lloyd iteration,
     stopping rule included, on the device (phk_kmeans_lloyd).  Returns (labels, sweeps), or None when a cluster ran
     empty (scikit-learn relocates it) or when some point came within KMEANS_MIN_GAP (relative) of a tie between its two
-    nearest centres in some sweep: the caller then takes the host fit.
+    nearest centres in some sweep, or when the rows hold a NaN or an infinity: the caller then takes the host fit.
 
     Parity: the device forms distances by float64 direct differences, scikit-learn by chunked matrix products; the labels
     are EQUAL to scikit-learn 1.7.2's on the reference's matrices (pinned: tests/golden centroids) and on every fold
@@ -187,11 +187,16 @@ def kmeans_reference_on_device(data, k, seed=kmeans_seed, max_iter=300, tol=1e-4
     import ctypes
     X = np.array(data, dtype=np.float64, order="C")          # (a copy: centred in place, as KMeans.fit does)
     n, D = X.shape
-    X -= X.mean(axis=0)
+    with np.errstate(invalid="ignore"):
+        X -= X.mean(axis=0)
+        tol_abs = float(np.mean(np.var(X, axis=0)) * tol)
+    if not np.isfinite(tol_abs):
+        # a NaN or an infinity among the rows (it reaches every entry of its centred column, and so the tolerance, which
+        # phk_kmeans_lloyd would refuse as an argument): the host fit refuses such rows with scikit-learn's ValueError
+        return None
     with _one_blas_thread():
         init, _ = kmeans_plusplus_seeds(X, int(k), np.random.RandomState(seed))
     init = np.ascontiguousarray(init, dtype=np.float64)
-    tol_abs = float(np.mean(np.var(X, axis=0)) * tol)
     labels = np.empty(n, dtype=np.uint32)
     n_iter, n_empty, min_gap = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
     ctx = ctx or _lib.get_context()
