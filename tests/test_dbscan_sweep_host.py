@@ -229,3 +229,113 @@ def test_grid_csv_round_trip(tmp_path, monkeypatch):
         for name in dbscan_grid.COLUMNS:
             assert back[name].dtype == table[name].dtype
             assert np.array_equal(back[name], table[name], equal_nan=True), name      # repr round-trips every float
+
+
+# ---- the inputs of tests/test_gpu_dbscan_sweep_shapes.py: what that file assumes of them, asserted without a device --------
+def test_groups_restates_cl_groups():
+    g = dbscan_sweep_ref.groups
+    assert g(256, 45, 45) == 45 and g(256, 46, 46) == 45 and g(256, 90, 90) == 23          # T^2 <= 8 cus: one tile per group
+    assert g(256, 2048, 7) == 1 and g(256, 5000, 7) == 1 and g(256, 1, 3) == 3 and g(256, 3, 4000) == 683
+    assert max(n for n in range(1, 4000) if g(256, -(-n // 64), -(-n // 64)) == -(-n // 64)) == 2880
+    assert dbscan_sweep_ref.group_tiles(90, 23).count(4) == 21 and sum(dbscan_sweep_ref.group_tiles(90, 23)) == 90
+
+
+@pytest.mark.parametrize("cus", [32, 256, 304])
+def test_scattered_lattice_meets_the_conditions_of_its_cases(cus):
+    """Cases 1 and 2 of the shapes file at three sizes of device: groups of several tiles (unevenly many from 256 compute
+    units on), hundreds of pairs exactly at every eps, and with min_samples 6 and 12 both row-index sides proper subsets
+    spanning more tiles than one group walks.  The eight cells of case 2 have 8 distinct cluster counts on the 256 compute
+    units of an MI355X, which is what the device test asserts; 7 on 32 units and 6 on 304."""
+    R = dbscan_sweep_ref
+    T, n = R.lattice_tiles(cus), R.lattice_rows(cus)
+    assert (T, n) == {32: (32, 2025), 256: (90, 5737), 304: (98, 6249)}[cus]
+    X = R.scattered_lattice(n, 41)
+    assert X.shape == (n, 2) and np.array_equal(X, R.scattered_lattice(n, 41))
+    G = R.groups(cus, T, T)
+    assert 1 < G < T and min(R.group_tiles(T, G)) >= 2
+    if cus >= 256:
+        assert len(set(R.group_tiles(T, G))) > 1
+    assert min(R.pairs_exactly_at(X, R.LATTICE_EPS)) >= 900
+    records = R.sweep_cells(X, [(e, m) for e in R.LATTICE_EPS for m in (6, 12)])
+    nu, nb = R.core_somewhere(records, n)
+    assert 20 * R.TILE < nu < n and 20 * R.TILE < nb < n
+    Tq, Tu = -(-nb // R.TILE), -(-nu // R.TILE)
+    assert Tq * Tu > 8 * cus and R.groups(cus, Tq, Tu) < Tu
+    assert len({r["n_clusters"] for r in records}) >= {32: 7, 256: 8, 304: 6}[cus]
+    assert max(R.borders_between_clusters(X, r) for r in records) >= 1
+    if cus == 256:
+        assert (nu, nb, R.groups(cus, Tq, Tu), Tu) == (4948, 3012, 43, 78)
+    # with min_samples = 1 and n + 1 beside them every row is on both sides
+    assert R.core_somewhere(R.sweep_cells(X, [(0.5, 1), (0.5, n + 1)]), n) == (n, n)
+
+
+def test_pairs_exactly_at_counts_like_the_distance_matrix():
+    X = dbscan_sweep_ref.scattered_lattice(700, 3)
+    d = cluster_ref.pair_distances(X, X)[np.triu_indices(700, 1)]
+    eps_values = dbscan_sweep_ref.LATTICE_EPS + (1.25,)                 # 1.25: (3, 4) and (5, 0) offsets
+    assert dbscan_sweep_ref.pairs_exactly_at(X, eps_values) == [int(np.count_nonzero(d == e)) for e in eps_values]
+
+
+def test_dbscan_cells_equals_dbscan_on_the_lattice():
+    """The reference of the large cases against the plain one, with pairs exactly at eps and border ties."""
+    X = dbscan_sweep_ref.scattered_lattice(900, 5)
+    cells = [(e, m) for e in dbscan_sweep_ref.LATTICE_EPS for m in (1, 6, 901, 12)]
+    want = dbscan_sweep_ref.dbscan_sweep(X, dbscan_sweep_ref.LATTICE_EPS, (1, 6, 901, 12))
+    dbscan_sweep_ref.same_records(dbscan_sweep_ref.sweep_cells(X, cells), want)
+    assert max(dbscan_sweep_ref.borders_between_clusters(X, r) for r in want) >= 1
+
+
+def test_clump_cells_fill_every_bin_at_every_number_of_thresholds():
+    R = dbscan_sweep_ref
+    X = R.clumps()
+    cells = R.clump_cells(X)
+    assert X.shape == (150, 3) and len(cells) == 64 and len({e for e, _ in cells}) == 64
+    eps = np.array([e for e, _ in cells])
+    assert (np.diff(eps) < 0).any() and (np.diff(eps) > 0).any()                      # not sorted
+    assert sum(1 for e in eps if 16 * e * e != round(16 * e * e)) >= 16               # square roots that were rounded
+    assert {m for _, m in cells} == {1, 2, 3, 4, 6, 9, 151, 2 ** 40}
+    for E in range(1, 65):
+        counts = R.bin_counts(X, eps[:E])
+        assert len(counts) == E + 1 and counts[:E].min() >= 1 and counts[E] >= 1, E
+    records = R.sweep_cells(X, cells)
+    R.same_records(records, [R.dbscan_sweep(X, [e], [m])[0] for e, m in cells])
+    assert len({tuple(r[k] for k in R.SUMMARY) for r in records}) >= 20
+    assert all(r["n_core"] == 0 for r in records if r["min_samples"] > 150)
+    assert any(r["n_border"] for r in records)
+    for thresholds in (32, 2):                                                        # 64 cells on fewer thresholds
+        some = R.cells_64(cells, thresholds)
+        assert len(some) == 64 and len({e for e, _ in some}) == thresholds
+        records = R.sweep_cells(X, some)
+        assert len({tuple(r[k] for k in R.SUMMARY) for r in records}) >= 20 and sum(1 for r in records if r["n_border"]) >= 20
+
+
+@pytest.mark.parametrize("D", [33, 100])
+def test_general_rows_keep_their_margin_in_extended_precision(D):
+    R = dbscan_sweep_ref
+    X = R.blobs(130, D, D)
+    d = R.extended_distances(X)
+    assert d.dtype == np.longdouble and np.array_equal(d, d.T) and (np.diag(d) == 0).all()
+    eps_values = R.midpoint_eps(d)
+    assert len(set(eps_values)) == 4 and R.relative_margin(d, eps_values) >= R.MARGIN
+    assert (D + 3) * 2.0 ** -53 * 64 <= R.MARGIN
+    records = R.cells_of_distances(d, [(e, m) for e in eps_values for m in (1, 3, 5, 9)])
+    R.same_records(records, R.dbscan_sweep(X, eps_values, (1, 3, 5, 9)))              # float64 decides the same: the margin
+    assert len({r["n_clusters"] for r in records}) >= 4 and any(r["n_border"] for r in records)
+
+
+def test_rows_with_infinities_are_nobodys_neighbours():
+    R = dbscan_sweep_ref
+    X, where = R.rows_with_infinities()
+    assert X.shape == (107, 4) and not np.isnan(X).any() and np.array_equal(np.flatnonzero(~np.isfinite(X).all(axis=1)), where)
+    with np.errstate(invalid="ignore"):
+        d = cluster_ref.pair_distances(X, X)
+        records = R.dbscan_sweep(X, [0.4, 0.8], [1, 4])
+    assert np.isnan(d[where, where]).all() and np.isnan(d[where[0], where[1]]) and np.isinf(d[where[0], where[2]])
+    assert not (d[where] <= 1e300).any()
+    for r in records:
+        assert (r["labels"][where] == -1).all() and not set(where) & set(r["core_sample_indices"])
+    finite = np.delete(np.arange(107), where)
+    for r, (e, m) in zip(records, [(e, m) for e in (0.4, 0.8) for m in (1, 4)]):      # the other rows: as without them
+        labels, core = cluster_ref.dbscan(X[finite], e, m)
+        assert np.array_equal(r["labels"][finite], labels) and np.array_equal(r["core_sample_indices"], finite[core])
+    assert records[0]["n_core"] == 100 and records[0]["n_noise"] == 7 and 0 < records[1]["n_core"] < 100
