@@ -391,6 +391,17 @@ int phk_nusvc_decision(phk_ctx *ctx, const double *SV, uint64_t n_sv, uint64_t D
 int phk_kde_log_density(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, double h,
                         double *out);
 
+/* phk_kde_log_density at B bandwidths from one pass over the pairs: out[b][q] (out[B][N]) is bit for bit what
+ * phk_kde_log_density(..., h[b], ...) writes to out[q].  Q and X go up once; a pass of the device carries up to
+ * PHK_KDE_SWEEP_PER_PASS bandwidths through one Gram tile, more bandwidths run as further passes over the resident rows.
+ * exclude_self != 0: N == M, query q is taken to be row q of X and the pair (q, q) is left out -- by index, an equal row
+ * elsewhere still counts -- and the normaliser is log(M - 1): the leave-one-out density.  M == 1 is then PHK_ERR_ARG.
+ * batch_rows: queries per device batch, 0 = the default (for tests; the result does not depend on it).  Host pointers.
+ * Every h[b] must be finite and > 0 and B >= 1 (else PHK_ERR_ARG); a NaN query row gives PHK_ERR_NAN; N == 0 is PHK_OK. */
+#define PHK_KDE_SWEEP_PER_PASS 8
+int phk_kde_sweep(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, const double *h,
+                  uint32_t B, int exclude_self, uint64_t batch_rows, double *out);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -93,6 +93,7 @@ SIGNATURES = {
     "phk_model_set_column_mask": (c_int, [c_void_p, c_void_p, c_void_p]),
     "phk_model_set_bandwidths": (c_int, [c_void_p, c_void_p, c_double, c_double]),
     "phk_kde_log_density": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_double, c_void_p]),
+    "phk_kde_sweep": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_int, c_u64, c_void_p]),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -617,6 +618,45 @@ def kde_log_density(ctx, Q, X, h):
         raise ValueError("Input contains NaN.")
     out = np.empty(Q.shape[0], dtype=np.float64)
     check(ctx.lib.phk_kde_log_density(ctx.handle, ptr(Q), Q.shape[0], ptr(X), X.shape[0], X.shape[1], h, ptr(out)))
+    return out
+
+
+KDE_SWEEP_PER_PASS = 8   # PHK_KDE_SWEEP_PER_PASS: bandwidths one device pass of phk_kde_sweep carries
+
+
+def check_kde_sweep_arguments(Q, X, bandwidths, exclude_self):
+    """(Q, X, h) as float64 C-contiguous arrays, or the ValueError of learning.density_sweep -- no library needed."""
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if Q.ndim != 2 or X.ndim != 2 or Q.shape[1] != X.shape[1]:
+        raise ValueError("query rows and data must be 2-D with the same number of columns")
+    if X.shape[0] == 0:
+        raise ValueError("Found array with 0 sample(s) (shape=%s) while a minimum of 1 is required." % (X.shape,))
+    h = np.ascontiguousarray(np.asarray(bandwidths, dtype=np.float64).ravel())
+    if h.size == 0:
+        raise ValueError("no bandwidths given")
+    if not (np.isfinite(h) & (h > 0)).all():
+        raise ValueError("bandwidth must be finite and > 0, got %r" % (h.tolist(),))
+    if exclude_self:
+        if Q.shape != X.shape:
+            raise ValueError("exclude_self needs the data rows as queries: shapes %s and %s" % (Q.shape, X.shape))
+        if X.shape[0] == 1:
+            raise ValueError("exclude_self leaves no row of a one-row data set")
+    if np.isnan(Q).any() or np.isnan(X).any():
+        raise ValueError("Input contains NaN.")
+    return Q, X, h
+
+
+def kde_sweep(ctx, Q, X, h, exclude_self=False, per_pass=None, batch_rows=0):
+    """kde_log_density at every bandwidth of ``h`` from one upload and one pass over the pairs per KDE_SWEEP_PER_PASS
+    bandwidths (phk_kde_sweep): (B, N) float64, row b bit for bit kde_log_density(ctx, Q, X, h[b]).  ``Q``, ``X``, ``h`` as
+    check_kde_sweep_arguments returns them.  ``per_pass`` (tests): at most that many bandwidths per call of the library."""
+    per = len(h) if per_pass is None else int(per_pass)   # (None: one call, the library runs its passes on resident rows)
+    out = np.empty((len(h), Q.shape[0]), dtype=np.float64)
+    for b0 in range(0, len(h), per):
+        hs, part = np.ascontiguousarray(h[b0:b0 + per]), out[b0:b0 + per]
+        check(ctx.lib.phk_kde_sweep(ctx.handle, ptr(Q), Q.shape[0], ptr(X), X.shape[0], X.shape[1], ptr(hs), len(hs),
+                                    1 if exclude_self else 0, int(batch_rows), ptr(part)))
     return out
 
 

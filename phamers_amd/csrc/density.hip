@@ -12,6 +12,7 @@
 // only); workgroup (chunk, query block) keeps, per query, a running (max, sum) of its chunk's terms and writes it to a
 // partials array; phk_kde_merge_kernel folds a query's chunks in chunk order.  The reduction order of one query is thus
 // fixed by the model alone -- the same for any N, batch split or entry point.
+#include "density_shared.h"
 #include "gram_tile.h"
 #include "score_model.h"
 
@@ -28,20 +29,6 @@ __global__ __launch_bounds__(256) void phk_kde_rownorm_kernel(const double *__re
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
     if (lane == 0) out[r] = s;
-}
-
-// (m1, s1) <- the log-sum-exp pair of the union of two sets: m = max term, s = sum of exp(term - m).  s == 0 = empty set.
-// Symmetric in its operands (so the two lanes of a butterfly step hold the same result).
-__device__ __forceinline__ void kde_merge(double &m1, double &s1, double m2, double s2) {
-    if (s2 == 0.0) return;
-    if (s1 == 0.0) {
-        m1 = m2;
-        s1 = s2;
-        return;
-    }
-    const double m = fmax(m1, m2);
-    s1 = s1 * exp(m1 - m) + s2 * exp(m2 - m);
-    m1 = m;
 }
 
 // grid: x = chunk (class-major: the n_cpos chunks of [0, n_pos), then those of [n_pos, M)), y = block of GT_QB queries.
@@ -144,14 +131,6 @@ __global__ __launch_bounds__(256) void phk_kde_merge_kernel(const double2 *__res
     const double lp = mp + log(sp) - lognorm_pos;
     out[q] = n_cneg ? lp - (mn + log(sn) - lognorm_neg) : lp;
 }
-
-// log(n) + (D/2) log(2 pi) + D log(h): what score_samples subtracts from the log-sum-exp (sklearn/neighbors/_kde.py:
-// log_density -= log(N); _binary_tree.pxi _log_kernel_norm for the Gaussian kernel)
-static double kde_lognorm(uint64_t n, uint64_t D, double h) {
-    return std::log((double)n) + 0.5 * (double)D * std::log(2.0 * M_PI) + (double)D * std::log(h);
-}
-
-static bool kde_bandwidth_ok(double h) { return h > 0.0 && h < __builtin_inf(); }   // (false for NaN)
 
 // |x|^2 of the n rows of d_X[n][D] -> d_out[n]
 int phk_launch_rownorm(phk_ctx *ctx, const double *d_X, uint64_t n, uint64_t D, double *d_out) {

@@ -48,19 +48,20 @@ __device__ __forceinline__ uint64_t gram_query(uint64_t q0, int a, int r) {
 }
 
 // acc[a][t] = Q[q0 + 16 a ..][:] . R[st + 16 t ..][:] over all D columns, in column-step order (queries at or past nq and
-// rows at or past r1 enter as zeros).
-template <bool FULL>
+// rows at or past r1 enter as zeros).  QT: the 16-query tiles the wave holds (GT_QT unless a kernel narrows its tile; a tile's
+// products do not depend on it).
+template <bool FULL, int QT = GT_QT>
 __device__ __forceinline__ void gram_tile(const double *__restrict__ Q, uint64_t nq, uint64_t q0, const double *__restrict__ R,
-                                          uint64_t r1, uint64_t st, uint64_t D, f64x4 acc[GT_QT][GT_RT]) {
+                                          uint64_t r1, uint64_t st, uint64_t D, f64x4 acc[QT][GT_RT]) {
     const int li = threadIdx.x & 15, kk = (threadIdx.x & 63) >> 4;
 #pragma unroll
-    for (int a = 0; a < GT_QT; ++a)
+    for (int a = 0; a < QT; ++a)
 #pragma unroll
         for (int t = 0; t < GT_RT; ++t) acc[a][t] = (f64x4){0.0, 0.0, 0.0, 0.0};
     for (uint64_t kc = 0; kc < D; kc += GT_KC) {
-        double qa[GT_QT][8];
+        double qa[QT][8];
 #pragma unroll
-        for (int a = 0; a < GT_QT; ++a) {
+        for (int a = 0; a < QT; ++a) {
             const uint64_t q = q0 + 16 * a + li;
             gram_load8<FULL>(Q, D, q, q < nq, kc + 8 * kk, qa[a]);
         }
@@ -72,7 +73,7 @@ __device__ __forceinline__ void gram_tile(const double *__restrict__ Q, uint64_t
 #pragma unroll
             for (int s = 0; s < 8; ++s)
 #pragma unroll
-                for (int a = 0; a < GT_QT; ++a)
+                for (int a = 0; a < QT; ++a)
                     acc[a][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[a][s], rb[s], acc[a][t], 0, 0, 0);
         }
     }

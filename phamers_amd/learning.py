@@ -7,6 +7,7 @@ learning.py -- drop-in for the hot-path helpers of PhaMers' scripts/learning.py.
     kmeans(data, k, ...)                          scripts/learning.py:131-146   -> scikit-learn's seeding on the host + its Lloyd sweeps on the GPU
     get_centroids(data, assignment)               scripts/learning.py:69-81     -> NumPy (86 means)
     get_density(point, data, bandwidth=0.1)       scripts/learning.py:107-115   -> GPU (float64 Gaussian KDE, log_density batched)
+    density_sweep(queries, data, bandwidths)      (the choice of the density bandwidths) -> GPU, every bandwidth from one pass over the pairs (phk_kde_sweep)
     dbscan(data, eps, min_samples, ...)           scripts/learning.py:149-163   -> GPU (neighbour counts + lock-free union-find)
     dbscan_sweep(data, eps_values, min_samples_values)   (the choice of dbscan's parameters) -> GPU, every cell of the grid in one pass over the pairs (phk_dbscan_sweep)
     kdistances(data, k)                           (the k-distance curve)        -> GPU kneighbors, sorted k-th distances
@@ -404,6 +405,28 @@ def log_density(queries, data, bandwidth=0.1):
     if queries.ndim == 1:
         queries = queries[None, :]
     return _lib.kde_log_density(_lib.get_context(), queries, np.asarray(data, dtype=np.float64), bandwidth)
+
+
+DENSITY_SWEEP_PER_PASS = _lib.KDE_SWEEP_PER_PASS   # bandwidths one device pass carries through one Gram tile
+
+
+def density_sweep(queries, data, bandwidths, exclude_self=False, _per_pass=None, _batch_rows=0):
+    """``log_density(queries, data, h)`` for every h of ``bandwidths`` -- (B, N) float64, row b for ``bandwidths[b]`` (the
+    order as given, duplicates kept), each row bit for bit what ``log_density`` returns -- with the rows uploaded once and
+    ONE pass over the pairs per DENSITY_SWEEP_PER_PASS bandwidths (phk_kde_sweep): the pair distances do not depend on
+    the bandwidth.  With ``exclude_self`` the queries are the data rows themselves (same shape) and query i is scored
+    under the data without row i -- left out by index: an equal row elsewhere still counts -- normalised by M - 1 rows:
+    the leave-one-out log-density.  ValueError, before any device work, for NaN input, an empty bandwidth list, a
+    bandwidth that is not finite and > 0, ``exclude_self`` with differing shapes or a one-row ``data``.  ``_per_pass``
+    (at most DENSITY_SWEEP_PER_PASS) and ``_batch_rows`` are for the tests: bandwidths per device pass and queries per
+    device batch; no result depends on either."""
+    queries = np.asarray(queries, dtype=np.float64)
+    if queries.ndim == 1:
+        queries = queries[None, :]
+    Q, X, h = _lib.check_kde_sweep_arguments(queries, data, bandwidths, exclude_self)
+    if _per_pass is not None and not 1 <= int(_per_pass) <= DENSITY_SWEEP_PER_PASS:
+        raise ValueError("_per_pass = %d is not in 1..%d" % (int(_per_pass), DENSITY_SWEEP_PER_PASS))
+    return _lib.kde_sweep(_lib.get_context(), Q, X, h, exclude_self=exclude_self, per_pass=_per_pass, batch_rows=_batch_rows)
 
 
 def get_density(point, data, bandwidth=0.1):
