@@ -43,7 +43,7 @@ static PhkProposal parse_proposal(const char *v) {
 // one knob by name (the part after PHK_ of its environment variable, lower case)
 static int set_knob(PhkKnobs &k, const char *key, const char *value) {
     const char *v = value ? value : "";
-    if (!strcmp(key, "count_lanes")) k.count_lanes = v[0];
+    if (!strcmp(key, "count_lanes")) k.count_lanes = phk_count_lanes_of(v[0]);
     else if (!strcmp(key, "force_exact")) k.force_exact = v[0] == '1';
     else if (!strcmp(key, "proposal")) k.proposal = parse_proposal(v);
     else if (!strcmp(key, "cx_cfg")) snprintf(k.cx_cfg, sizeof(k.cx_cfg), "%s", v);
@@ -566,7 +566,7 @@ extern "C" int phk_count_score_dev(phk_ctx *ctx, const phk_model *model, const u
     PhkStepLink link;
     // k = 5: the count kernel's flush also writes the int8 operand of the scorer's sweep (PhkPrep8)
     if (k == 5 && method != PHK_METHOD_DENSITY && method != PHK_METHOD_SVM && !d_mask && n > 0 && phk_model_has_fast(model) && model->d_A8 && !model->bf_stale && !ctx->knobs.force_exact &&
-        ctx->knobs.proposal == PHK_PROP_DEFAULT && !ctx->knobs.count_lanes) {
+        ctx->knobs.proposal == PHK_PROP_DEFAULT && !ctx->knobs.count_lanes.set) {
         const uint64_t D = model->D;
         void *frag, *big;
         PHK_TRY(phk_ws(ctx, WS_FRAG8, phk_div_up(n, 32) * 32 * D, &frag));

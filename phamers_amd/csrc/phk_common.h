@@ -115,12 +115,41 @@ struct PhkLayout {
 // operand hand-over.
 enum PhkProposal { PHK_PROP_DEFAULT = 0, PHK_PROP_OTHER, PHK_PROP_F16, PHK_PROP_HI, PHK_PROP_CXF, PHK_PROP_I83 };
 
+// The "count_lanes" option (phk_set_option / PHK_COUNT_LANES) as set_knob decodes its first character; nothing else looks at
+// the character.  `slot path`: whether the slot kernels count a batch they are eligible for (count_route); `pairs`: threads
+// of the two-windows-per-add kernel at k = 4 without a mask; `direct`: threads of the slot kernel, - = by k (512 at k = 3, 4).
+//   value   slot path                pairs   direct   int8 operand offered (phk_count_score_dev)
+//   unset   by the statistics        1024    -        yes
+//   0       never (wave-per-contig)  .       .        no
+//   f       whatever the batch       none    -        no
+//   p       by the statistics        512     512      no
+//   P       by the statistics        1024    -        no
+//   q       whatever the batch       512     512      no
+//   Q       whatever the batch       1024    -        no
+//   d       by the statistics        none    512      no
+//   D       by the statistics        none    1024     no     (k = 3 stays at 512)
+//   other   by the statistics        none    -        no
+struct PhkCountLanes {
+    bool set = false;         // the option holds a value
+    bool wave_only = false;   // '0'
+    bool forced = false;      // f q Q: no stand-down by the batch statistics, no sorted walk
+    uint16_t pairs = 1024;    // threads of phk_count_pairs_kernel, 0 = not launched
+    uint16_t direct = 0;      // threads of phk_count_direct_kernel, 0 = no preference
+};
+static inline PhkCountLanes phk_count_lanes_of(char c) {   // set_knob's decoder: the table above, column by column
+    PhkCountLanes l;
+    l.set = c != 0;
+    l.wave_only = c == '0';
+    l.forced = c == 'f' || c == 'q' || c == 'Q';
+    l.pairs = (c == 0 || c == 'P' || c == 'Q') ? 1024 : ((c == 'p' || c == 'q') ? 512 : 0);
+    l.direct = (c == 'd' || c == 'p' || c == 'q') ? 512 : (c == 'D' ? 1024 : 0);
+    return l;
+}
+
 // Tuning / diagnostic knobs.  Read ONCE from the environment when the context is created (PHK_<NAME>), changed
 // afterwards only through phk_set_option(): no launch path calls getenv.
 struct PhkKnobs {
-    char count_lanes = 0;      // which count kernel (phk_launch_count): '0' the wave-per-contig kernel only; 'f' the unstaged slot kernel whatever
-                               // the batch looks like; 'p' / 'P' the two-windows-per-add kernel with 512 / 1024 threads where the batch
-                               // statistics allow (k = 4, no mask), 'q' / 'Q' the same, forced; 'd' / 'D' the slot kernel with 512 / 1024 threads; 0 = default
+    PhkCountLanes count_lanes; // which count kernels (count_route, count_shared.h), decoded once by set_knob: the table above
     bool force_exact = false;  // every model through the float64 path
     PhkProposal proposal = PHK_PROP_DEFAULT;   // first pass of the fast scorer, parsed once by set_knob (see the table at ScoreRoute, score_mfma.hip)
     char cx_cfg[8] = "";       // "<tiles per wave><waves per workgroup>": 14, 24, 28
@@ -234,7 +263,7 @@ int phk_batch_build(phk_ctx *ctx, const char *bases, const std::function<void(ui
                     const uint64_t *offsets, uint64_t n, int k, const char *symbols4, phk_batch **out,
                     const PhkWindowSpec *windows = nullptr);
 // (batch.hip) the same from the RAW bytes of a FASTA file (title lines, line ends and all) + one layout entry per record:
-// the bytes go up as they are and the device drops what is not sequence (phk_deline_pack_kernel, count.hip).
+// the bytes go up as they are and the device drops what is not sequence (phk_deline_pack_kernel, ingest.hip).
 // phk_raw_to_device puts the file's bytes into the context's WS_ASCII workspace (staged copies; it may run on a thread of its
 // own beside the host's index scan -- nothing else uses the context meanwhile); phk_batch_build_raw then takes the record
 // layout and the side buffer of the irregular records (rbegin[r] indexes the raw bytes, or `side` where rlw[r] = 2^32 - 1).
@@ -321,18 +350,20 @@ static inline uint64_t phk_div_up(uint64_t a, uint64_t b) { return (a + b - 1) /
 
 // ---- internal entry points implemented across translation units ----
 // per-device kernel attributes (dynamic LDS above 64 KiB), set for the context's device at phk_create
-int phk_count_init_device(phk_ctx *ctx);       // count.hip
+int phk_count_init_device(phk_ctx *ctx);       // count_slots.hip
 int phk_score_f16_init_device(phk_ctx *ctx);   // score_f16.hip
 int phk_score_mfma_init_device(phk_ctx *ctx);  // score_mfma.hip
-// count.hip
+// ingest.hip
 int phk_launch_pack(phk_ctx *ctx, const char *d_bases, uint64_t T, const char *symbols4,
                     uint32_t *d_packed, uint32_t *d_mask, uint32_t *d_any_invalid);
 int phk_launch_deline_pack(phk_ctx *ctx, const uint8_t *d_raw, const uint8_t *d_side, const uint64_t *d_offsets, uint64_t n, const uint64_t *d_rbegin,
                            const uint32_t *d_rlw, const uint32_t *d_rtl, uint64_t T, const char *symbols4, uint32_t *d_packed,
                            uint32_t *d_mask, uint32_t *d_any_invalid);
+// count.hip (the driver; its stages and the kernels' launchers: count_shared.h)
 int phk_launch_count(phk_ctx *ctx, const uint32_t *d_packed, const uint32_t *d_mask, uint64_t T,
                      const uint64_t *d_offsets, uint64_t n, int k, uint32_t *d_counts,
                      uint32_t *d_nwin, uint64_t mean_bases = 0, PhkStepLink *link = nullptr);
+// rows.hip
 int phk_launch_widen(phk_ctx *ctx, const uint32_t *d_in, uint64_t count, int64_t *d_out);
 int phk_launch_normalize_u32(phk_ctx *ctx, const uint32_t *d_counts, uint64_t n, uint64_t D,
                              double *d_out);

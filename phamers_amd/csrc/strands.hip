@@ -1,6 +1,6 @@
 // strands.hip -- strand-symmetric counts: a count row added to its reverse-complement permutation.
 //
-// An assembler emits a contig on an arbitrary strand, and the count kernels (count.hip, windows.hip) restate the
+// An assembler emits a contig on an arbitrary strand, and the count kernels (count_wave.hip, count_slots.hip, windows.hip) restate the
 // reference's single-strand window loop (scripts/kmer.py:32-79).  The fold F[c] = C[c] + C[rc(c)], rc(c) = the column of
 // the reverse-complement k-mer, is what counting the sequence AND its reverse complement gives -- for every string,
 // invalid characters included, because a window holds an invalid character exactly when its mirror image does -- so

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void sw_silhouette_kernel(const double *__rest
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// np.add.reduce of a contiguous float64 vector: pairwise, in pieces of 8192 (count.hip's phk_np_pairwise_sum on the host)
+// np.add.reduce of a contiguous float64 vector: pairwise, in pieces of 8192 (rows.hip's phk_np_pairwise_sum on the host)
 static double sw_np_pairwise(const double *a, uint64_t n) {
     if (n < 8) {
         double r = 0.0;

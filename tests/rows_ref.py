@@ -1,5 +1,5 @@
 """NumPy's summation order for a contiguous float64 row, in plain Python floats: the reference statement of what
-phk_normalize_f64_kernel (phamers_amd/csrc/count.hip) has to reproduce.  Test-only code.
+phk_normalize_f64_kernel (phamers_amd/csrc/rows.hip) has to reproduce.  Test-only code.
 
 np.sum hands its reduction loop at most np.getbufsize() = 8 192 elements at a time.  Each piece is summed pairwise:
 blocks of at most 128 elements with eight running partial sums, larger pieces halved with the split rounded down to a
