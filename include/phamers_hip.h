@@ -385,6 +385,33 @@ int phk_nusvc_fit(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const d
 int phk_nusvc_decision(phk_ctx *ctx, const double *SV, uint64_t n_sv, uint64_t D, const double *dual_coef, double rho,
                        double gamma, const double *Q, uint64_t N, double *dec);
 
+/* phk_nusvc_fit over a grid gamma x nu x row subset, and phk_nusvc_decision of every fold's held-out rows: the fits behind a
+ * choice of the svm method's nu and gamma.  Subset 0 is all rows; subset f + 1 (f < F) the rows whose fold_of is not f.
+ * Problem (g, v, s) has index (g V + v)(F + 1) + s; it is solved in a workgroup of its own from one kernel matrix per gamma,
+ * bit for bit as phk_nusvc_fit solves the rows of the subset (in their order) at gammas[g], nus[v], tol, max_iter.
+ * X[n][D], labels[n] in {0, 1}, gammas[Gm], nus[V] host arrays; fold_of[n] int32 in [0, F), or F = 0 (fold_of and held_dec
+ * may be NULL) for full fits only.  Out (host), per problem q: status[q] -- PHK_SVM_OK; PHK_SVM_INFEASIBLE: a class of the
+ * subset has no rows or nu (n0 + n1) / 2 > min(n0, n1) on it, decided before any launch; PHK_SVM_NOT_FINITE: coefficients
+ * or rho that are not finite (r = 0), where phk_nusvc_fit returns PHK_ERR_ARG -- n_iter[q], and for PHK_SVM_OK n_sv[q],
+ * rho[q] (libsvm's; NaN otherwise) and coef[q][n]: libsvm's coefficients alpha_i y_i / r in the caller's row order, 0 off the
+ * support (all 0 otherwise).  Per cell c = g V + v: held_dec[c][i] = libsvm's decision value of row i under the fit of
+ * subset fold_of[i] + 1 of that cell, the bits phk_nusvc_decision gives for that model and row; NaN where that fit has
+ * another status.  Private arguments (tests; no result depends on them): lds_rows -- the solver keeps alpha, G and y in LDS
+ * when n is at most min(lds_rows, phk_nusvc_sweep_lds_rows()), in global memory otherwise; -1 = the device's capacity, 0 =
+ * never; gammas_per_pass -- kernel matrices resident at a time, 0 = as many as 4 GiB hold; threads -- the solver's workgroup
+ * size, a multiple of 64 up to 1024, 0 = chosen from n.  PHK_ERR_ARG for an empty axis, nu outside (0, 1], a gamma or tol
+ * that is not finite and > 0, fold ids outside [0, F), labels outside {0, 1}, more than 65536 rows; PHK_ERR_NAN for NaN
+ * rows.  No infeasible or non-finite problem is an error, and none disturbs another problem. */
+#define PHK_SVM_OK 0
+#define PHK_SVM_INFEASIBLE 1
+#define PHK_SVM_NOT_FINITE 2
+int phk_nusvc_sweep(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, const double *labels, const double *gammas,
+                    uint32_t Gm, const double *nus, uint32_t V, const int32_t *fold_of, uint32_t F, double tol,
+                    int32_t max_iter, int64_t lds_rows, uint32_t gammas_per_pass, uint32_t threads, int32_t *status,
+                    int32_t *n_iter, int32_t *n_sv, double *rho, double *coef, double *held_dec);
+/* rows whose solver state (17 bytes each) fits the LDS a workgroup of phk_nusvc_sweep may declare */
+uint32_t phk_nusvc_sweep_lds_rows(void);
+
 /* KernelDensity(kernel='gaussian', bandwidth=h).fit(X).score_samples(Q) (learning.get_density, scripts/learning.py:107-115):
  * out[q] = logsumexp_j(-|Q[q] - X[j]|^2 / (2 h^2)) - log(M) - (D/2) log(2 pi) - D log(h), float64, the density method's
  * kernel over one data set.  Host pointers.  h must be finite and > 0 (else PHK_ERR_ARG); a NaN query row gives PHK_ERR_NAN. */

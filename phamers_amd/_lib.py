@@ -105,6 +105,10 @@ SIGNATURES = {
                               c_void_p, c_void_p, P(c_double), P(ctypes.c_int32), P(ctypes.c_int32)]),
     "phk_nusvc_decision": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_double, c_double, c_void_p, c_u64,
                                    c_void_p]),
+    "phk_nusvc_sweep": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u32, c_void_p, c_u32, c_void_p, c_u32,
+                                c_double, ctypes.c_int32, ctypes.c_int64, c_u32, c_u32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "phk_nusvc_sweep_lds_rows": (c_u32, []),
     "phk_score": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p]),
     "phk_distances": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p]),
     "phk_silhouettes": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_void_p]),
@@ -758,6 +762,67 @@ def nusvc_decision(ctx, SV, coef, rho, gamma, Q):
     out = np.empty(Q.shape[0], dtype=np.float64)
     check(ctx.lib.phk_nusvc_decision(ctx.handle, ptr(SV), SV.shape[0], SV.shape[1], ptr(coef), float(rho), float(gamma),
                                      ptr(Q), Q.shape[0], ptr(out)))
+    return out
+
+
+SVM_OK, SVM_INFEASIBLE, SVM_NOT_FINITE = 0, 1, 2   # PHK_SVM_*: a sweep problem's status
+
+
+def nusvc_sweep_lds_rows():
+    """Rows whose solver state fits the LDS of one workgroup of phk_nusvc_sweep (no device needed)."""
+    return int(load().phk_nusvc_sweep_lds_rows())
+
+
+def check_nusvc_sweep_arguments(X, labels, nus, gammas, fold_of, folds, tol, max_iter):
+    """(X, labels, nus, gammas, fold_of) as C-contiguous arrays of the library's types, or the ValueError of
+    svm.nusvc_sweep -- no library needed.  ``gammas`` are numbers here; ``fold_of`` is None with ``folds`` = 0."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    y = np.ascontiguousarray(labels, dtype=np.float64)
+    if X.ndim != 2 or y.ndim != 1 or len(y) != len(X) or X.shape[0] == 0 or X.shape[1] == 0:
+        raise ValueError("X must be 2-D and y 1-D with one label per row")
+    if not np.isin(y, (0.0, 1.0)).all():
+        raise ValueError("labels must be 0 or 1")
+    nus = np.ascontiguousarray(np.asarray(nus, dtype=np.float64).ravel())
+    gammas = np.ascontiguousarray(np.asarray(gammas, dtype=np.float64).ravel())
+    if nus.size == 0 or gammas.size == 0:
+        raise ValueError("an empty axis of the grid: %d nu value(s), %d gamma value(s)" % (nus.size, gammas.size))
+    if not ((nus > 0) & (nus <= 1)).all():
+        raise ValueError("nu <= 0 or nu > 1")
+    if not (np.isfinite(gammas) & (gammas > 0)).all():
+        raise ValueError("gamma must be finite and > 0, got %r" % (gammas.tolist(),))
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError("tol must be finite and > 0, got %r" % (tol,))
+    if not (max_iter == -1 or max_iter > 0):
+        raise ValueError("max_iter must be -1 or > 0, got %r" % (max_iter,))
+    folds = int(folds)
+    if folds:
+        fold_of = np.ascontiguousarray(fold_of, dtype=np.int32)
+        if fold_of.shape != y.shape or ((fold_of < 0) | (fold_of >= folds)).any():
+            raise ValueError("one fold id in [0, %d) per row" % folds)
+    else:
+        fold_of = None
+    if np.isnan(X).any():
+        raise ValueError("Input contains NaN.")
+    return X, y, nus, gammas, fold_of
+
+
+def nusvc_sweep(ctx, X, labels, nus, gammas, fold_of=None, folds=0, tol=1e-3, max_iter=-1, lds_rows=-1, gammas_per_pass=0,
+                threads=0):
+    """phk_nusvc_sweep on arguments as check_nusvc_sweep_arguments returns them: {status, n_iter, n_sv (Gm, V, folds + 1)
+    int32, rho (Gm, V, folds + 1), coef (Gm, V, folds + 1, n): libsvm's values, subset 0 = the full fit; held_dec (Gm, V, n)
+    or None without folds}."""
+    n, Gm, V, S = X.shape[0], len(gammas), len(nus), folds + 1
+    out = {"status": np.empty((Gm, V, S), dtype=np.int32), "n_iter": np.empty((Gm, V, S), dtype=np.int32),
+           "n_sv": np.empty((Gm, V, S), dtype=np.int32), "rho": np.empty((Gm, V, S), dtype=np.float64),
+           "coef": np.empty((Gm, V, S, n), dtype=np.float64),
+           "held_dec": np.empty((Gm, V, n), dtype=np.float64) if folds else None}
+    rc = ctx.lib.phk_nusvc_sweep(ctx.handle, ptr(X), n, X.shape[1], ptr(labels), ptr(gammas), Gm, ptr(nus), V, ptr(fold_of),
+                                 folds, float(tol), int(max_iter), int(lds_rows), int(gammas_per_pass), int(threads),
+                                 ptr(out["status"]), ptr(out["n_iter"]), ptr(out["n_sv"]), ptr(out["rho"]), ptr(out["coef"]),
+                                 ptr(out["held_dec"]))
+    if rc == PHK_ERR_ARG:
+        raise ValueError(last_error())
+    check(rc)
     return out
 
 

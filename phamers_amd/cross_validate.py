@@ -72,7 +72,9 @@ class cross_validator(object):
         self.k_neighbors = 3                         # scripts/phamer.py:79
         self.positive_bandwidth = 0.005              # scripts/phamer.py:82-83 (method 'density')
         self.negative_bandwidth = 0.01
-        self.score_threshold = 0                     # scripts/cross_validate.py:53
+        self.svm_nu = 0.5                            # NuSVC()'s defaults (method 'svm'); svm_grid.py tables other values
+        self.svm_gamma = 'scale'
+        self.score_threshold = 0                    # scripts/cross_validate.py:53
         self.output_directory = "cross_validation"   # scripts/cross_validate.py:55
         self.methods = list(ALL_METHODS)             # what cross_validate_all_algorithms runs (scripts/cross_validate.py:304)
 
@@ -138,7 +140,8 @@ class cross_validator(object):
                     model.set_centroids(*cents)
                 model.set_column_mask(np.concatenate((out_p, out_n)))
                 if method == 'svm':
-                    model.fit_svm()    # on the fold's train rows (the mask's complement), gamma over those rows
+                    # on the fold's train rows (the mask's complement); 'scale' / 'auto' are taken over those rows
+                    model.fit_svm(self.svm_nu, self.svm_gamma)
                 scores = model.score(np.vstack((P[out_p], Nm[out_n])), method)
                 n_p = int(out_p.sum())
                 pos_scores[out_p], neg_scores[out_n] = scores[:n_p], scores[n_p:]

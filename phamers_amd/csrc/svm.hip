@@ -26,10 +26,7 @@
 
 #include "gram_tile.h"
 #include "score_model.h"
-
-#define SVM_T 1024      // solver threads (one workgroup)
-#define SVM_STEPS 4096  // solver iterations per launch
-#define SVM_TAU 1e-12   // libsvm's TAU
+#include "svm_shared.h"
 
 // The Gram tile: grid x = chunk of GT_CHUNK rows of R, y = block of GT_QB rows of A.  d2 = max(|a|^2 + |r|^2 - 2 a.r, 0).
 // GRAM = true:  Qf[a][r] = (float)(y_a y_r exp(-gamma d2)) (A = R = the training rows, nq = nr = n; Qf[i][i] = 1).
@@ -117,12 +114,6 @@ __global__ __launch_bounds__(256) void phk_svm_merge_kernel(const double *__rest
 }
 
 // ---- solver ------------------------------------------------------------------------------------------------------------
-struct SvmCtl {
-    int32_t iter;   // iterations done
-    int32_t done;   // the stop test held
-    double rho, r;  // calculate_rho (before the 1/r scaling)
-};
-
 // Solver::Solve's gradient start: G[j] = sum over rows i with alpha_i > 0, in row order, of alpha_i Q[i][j]
 __global__ __launch_bounds__(256) void phk_svm_grad_init_kernel(const float *__restrict__ Qf, const double *__restrict__ alpha,
                                                                 uint64_t n, double *__restrict__ G) {
@@ -137,219 +128,26 @@ __global__ __launch_bounds__(256) void phk_svm_grad_init_kernel(const float *__r
     G[j] = g;
 }
 
-// (value, index) pairs ordered by value, then by index: the larger pair wins a max, the (smaller value, larger index) pair
-// a min -- what the sequential scans with ">=" / "<=" keep (the last of equal values).
-__device__ __forceinline__ void svm_argmax(double &v, int &i, double v2, int i2) {
-    if (v2 > v || (v2 == v && i2 > i)) {
-        v = v2;
-        i = i2;
-    }
-}
-__device__ __forceinline__ void svm_argmin(double &v, int &i, double v2, int i2) {
-    if (v2 < v || (v2 == v && i2 > i)) {
-        v = v2;
-        i = i2;
-    }
-}
-
-// block-wide reduction of two (value, index) pairs: RED0 / RED1 = true for max, false for min.  The result is in every
-// thread.  (Commutative and associative: the order of the folds does not matter.)
-template <bool MAX0, bool MAX1>
-__device__ void svm_reduce2(double &v0, int &i0, double &v1, int &i1, double *s_v, int *s_i) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double a = __shfl_xor(v0, o), b = __shfl_xor(v1, o);
-        const int ia = __shfl_xor(i0, o), ib = __shfl_xor(i1, o);
-        if (MAX0) svm_argmax(v0, i0, a, ia); else svm_argmin(v0, i0, a, ia);
-        if (MAX1) svm_argmax(v1, i1, b, ib); else svm_argmin(v1, i1, b, ib);
-    }
-    if (lane == 0) {
-        s_v[2 * wave] = v0;
-        s_i[2 * wave] = i0;
-        s_v[2 * wave + 1] = v1;
-        s_i[2 * wave + 1] = i1;
-    }
-    __syncthreads();
-    for (int w = 0; w < SVM_T / 64; ++w) {
-        if (MAX0) svm_argmax(v0, i0, s_v[2 * w], s_i[2 * w]); else svm_argmin(v0, i0, s_v[2 * w], s_i[2 * w]);
-        if (MAX1) svm_argmax(v1, i1, s_v[2 * w + 1], s_i[2 * w + 1]); else svm_argmin(v1, i1, s_v[2 * w + 1], s_i[2 * w + 1]);
-    }
-    __syncthreads();   // (s_v / s_i are reused by the next reduction)
-}
-
-// Solver_NU, no shrinking, C_i = 1 (scikit-learn passes unit sample weights): at most max_steps iterations from the state
-// in (alpha, G, ctl).  y in the grouped order.  alpha_i >= 1: upper bound, alpha_i <= 0: lower bound (update_alpha_status).
+// Solver_NU (svm_solve_steps, svm_shared.h): at most max_steps iterations from the state in (alpha, G, ctl).
 __global__ __launch_bounds__(SVM_T) void phk_svm_solve_kernel(const float *__restrict__ Qf, const int8_t *__restrict__ y,
                                                               uint64_t n, double eps, int32_t max_iter, int32_t max_steps,
                                                               double *__restrict__ alpha, double *__restrict__ G,
                                                               SvmCtl *__restrict__ ctl) {
-#pragma clang fp contract(off)
-    __shared__ double s_v[2 * (SVM_T / 64)];
-    __shared__ int s_i[2 * (SVM_T / 64)];
-    __shared__ int s_ij[2];
-    __shared__ double s_d[2];
-    __shared__ int s_stop;
-    const int tid = threadIdx.x;
-    const int ni = (int)n;
-    const double INF = __builtin_inf();
-    int iter = ctl->iter;
+    __shared__ SvmShared sh;
     if (ctl->done) return;
-    for (int step = 0; step < max_steps; ++step) {
-        if (max_iter != -1 && iter >= max_iter) {
-            if (tid == 0) ctl->done = 1;
-            break;
-        }
-        // (i) i candidates: -G[t] over y = +1 rows below the upper bound, G[t] over y = -1 rows above the lower bound
-        double gp = -INF, gn = -INF;
-        int ip = -1, in = -1;
-        for (int t = tid; t < ni; t += SVM_T) {
-            const double a = alpha[t], g = G[t];
-            if (y[t] == 1) {
-                if (!(a >= 1.0) && -g >= gp) {
-                    gp = -g;
-                    ip = t;
-                }
-            } else if (!(a <= 0.0) && g >= gn) {
-                gn = g;
-                in = t;
-            }
-        }
-        svm_reduce2<true, true>(gp, ip, gn, in, s_v, s_i);
-        // (ii) j: min obj_diff (last index on ties) + the second maxima Gmaxp2 / Gmaxn2
-        double gp2 = -INF, gn2 = -INF, od_min = INF;
-        int jmin = -1, dummy0 = -1, dummy1 = -1;
-        const float *Qp = ip >= 0 ? Qf + (uint64_t)ip * n : nullptr;
-        const float *Qn = in >= 0 ? Qf + (uint64_t)in * n : nullptr;
-        for (int t = tid; t < ni; t += SVM_T) {
-            const double a = alpha[t], g = G[t];
-            if (y[t] == 1) {
-                if (!(a <= 0.0)) {
-                    const double gd = gp + g;
-                    if (g >= gp2) gp2 = g;
-                    if (gd > 0.0) {
-                        const double qc = 2.0 - (double)(2.0f * Qp[t]);
-                        const double od = -(gd * gd) / (qc > 0.0 ? qc : SVM_TAU);
-                        if (od <= od_min) {
-                            od_min = od;
-                            jmin = t;
-                        }
-                    }
-                }
-            } else if (!(a >= 1.0)) {
-                const double gd = gn - g;
-                if (-g >= gn2) gn2 = -g;
-                if (gd > 0.0) {
-                    const double qc = 2.0 - (double)(2.0f * Qn[t]);
-                    const double od = -(gd * gd) / (qc > 0.0 ? qc : SVM_TAU);
-                    if (od <= od_min) {
-                        od_min = od;
-                        jmin = t;
-                    }
-                }
-            }
-        }
-        svm_reduce2<true, true>(gp2, dummy0, gn2, dummy1, s_v, s_i);
-        double od2 = 0.0;
-        int dummy2 = -1;
-        svm_reduce2<false, true>(od_min, jmin, od2, dummy2, s_v, s_i);
-        // (iii) stop test and the two-variable update (thread 0)
-        if (tid == 0) {
-            const double m1 = gp + gp2, m2 = gn + gn2;
-            if ((m1 > m2 ? m1 : m2) < eps || jmin == -1) {
-                s_stop = 1;
-            } else {
-                s_stop = 0;
-                const int j = jmin, i = y[j] == 1 ? ip : in;
-                const double Qij = (double)Qf[(uint64_t)i * n + j];
-                double ai = alpha[i], aj = alpha[j];
-                const double oi = ai, oj = aj;
-                const double Gi = G[i], Gj = G[j];
-                if (y[i] != y[j]) {
-                    double qc = 2.0 + (double)(2.0f * (float)Qij);
-                    if (qc <= 0.0) qc = SVM_TAU;
-                    const double delta = (-Gi - Gj) / qc;
-                    const double diff = ai - aj;
-                    ai += delta;
-                    aj += delta;
-                    if (diff > 0.0) {
-                        if (aj < 0.0) { aj = 0.0; ai = diff; }
-                    } else {
-                        if (ai < 0.0) { ai = 0.0; aj = -diff; }
-                    }
-                    if (diff > 0.0) {   // (C_i - C_j = 0)
-                        if (ai > 1.0) { ai = 1.0; aj = 1.0 - diff; }
-                    } else {
-                        if (aj > 1.0) { aj = 1.0; ai = 1.0 + diff; }
-                    }
-                } else {
-                    double qc = 2.0 - (double)(2.0f * (float)Qij);
-                    if (qc <= 0.0) qc = SVM_TAU;
-                    const double delta = (Gi - Gj) / qc;
-                    const double sum = ai + aj;
-                    ai -= delta;
-                    aj += delta;
-                    if (sum > 1.0) {
-                        if (ai > 1.0) { ai = 1.0; aj = sum - 1.0; }
-                    } else {
-                        if (aj < 0.0) { aj = 0.0; ai = sum; }
-                    }
-                    if (sum > 1.0) {
-                        if (aj > 1.0) { aj = 1.0; ai = sum - 1.0; }
-                    } else {
-                        if (ai < 0.0) { ai = 0.0; aj = sum; }
-                    }
-                }
-                alpha[i] = ai;
-                alpha[j] = aj;
-                s_ij[0] = i;
-                s_ij[1] = j;
-                s_d[0] = ai - oi;
-                s_d[1] = aj - oj;
-            }
-        }
-        __syncthreads();
-        if (s_stop) {
-            if (tid == 0) ctl->done = 1;
-            break;
-        }
-        ++iter;
-        // (iv) G += Q_i d_i + Q_j d_j
-        {
-            const float *Qi = Qf + (uint64_t)s_ij[0] * n, *Qj = Qf + (uint64_t)s_ij[1] * n;
-            const double di = s_d[0], dj = s_d[1];
-            for (int t = tid; t < ni; t += SVM_T) G[t] = G[t] + ((double)Qi[t] * di + (double)Qj[t] * dj);
-        }
-        __syncthreads();
+    int iter = ctl->iter;
+    const bool finished = svm_solve_steps<SVM_T>(Qf, y, n, eps, max_iter, max_steps, alpha, G, iter, sh);
+    if (threadIdx.x == 0) {
+        if (finished) ctl->done = 1;
+        ctl->iter = iter;
     }
-    if (tid == 0) ctl->iter = iter;
 }
 
 // Solver_NU::calculate_rho, one thread, row order
 __global__ __launch_bounds__(64) void phk_svm_rho_kernel(const int8_t *__restrict__ y, uint64_t n,
                                                          const double *__restrict__ alpha, const double *__restrict__ G,
                                                          SvmCtl *__restrict__ ctl) {
-#pragma clang fp contract(off)
-    if (threadIdx.x != 0) return;
-    const double INF = __builtin_inf();
-    int nf1 = 0, nf2 = 0;
-    double ub1 = INF, ub2 = INF, lb1 = -INF, lb2 = -INF, sf1 = 0.0, sf2 = 0.0;
-    for (uint64_t i = 0; i < n; ++i) {
-        const double a = alpha[i], g = G[i];
-        if (y[i] == 1) {
-            if (a >= 1.0) lb1 = fmax(lb1, g);
-            else if (a <= 0.0) ub1 = fmin(ub1, g);
-            else { ++nf1; sf1 += g; }
-        } else {
-            if (a >= 1.0) lb2 = fmax(lb2, g);
-            else if (a <= 0.0) ub2 = fmin(ub2, g);
-            else { ++nf2; sf2 += g; }
-        }
-    }
-    const double r1 = nf1 > 0 ? sf1 / nf1 : (ub1 + lb1) / 2;
-    const double r2 = nf2 > 0 ? sf2 / nf2 : (ub2 + lb2) / 2;
-    ctl->r = (r1 + r2) / 2;
-    ctl->rho = (r1 - r2) / 2;
+    if (threadIdx.x == 0) svm_calculate_rho(y, n, alpha, G, ctl);
 }
 
 // rows idx[0..n) of X[][D] -> out[n][D]
@@ -378,8 +176,27 @@ bool svm_gamma_ok(double g) { return g > 0.0 && g < __builtin_inf(); }
 
 }   // namespace
 
-// libsvm's largest problem here: Q is n x n float32
-#define SVM_MAX_ROWS 65536u
+int svm_launch_gram(phk_ctx *ctx, const double *d_Xg, const double *xn, uint64_t n, uint64_t D, double gamma, const int8_t *dy,
+                    float *Qf) {
+    const dim3 grid((unsigned)phk_div_up(n, GT_CHUNK), (unsigned)phk_div_up(n, GT_QB));
+    if (D % GT_KC == 0) {
+        PHK_LAUNCH(ctx, "phk_svm_gram_kernel",
+                   (phk_svm_tile_kernel<true, true><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
+                       d_Xg, xn, n, d_Xg, xn, n, D, gamma, nullptr, dy, Qf, nullptr)));
+    } else {
+        PHK_LAUNCH(ctx, "phk_svm_gram_kernel",
+                   (phk_svm_tile_kernel<false, true><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
+                       d_Xg, xn, n, d_Xg, xn, n, D, gamma, nullptr, dy, Qf, nullptr)));
+    }
+    return PHK_OK;
+}
+
+int svm_launch_gather(phk_ctx *ctx, const double *d_X, uint64_t D, const uint32_t *d_idx, uint64_t n, double *d_out) {
+    PHK_LAUNCH(ctx, "phk_svm_gather_kernel",
+               phk_svm_gather_kernel<<<dim3((unsigned)phk_div_up(n * D, 256)), dim3(256), 0, ctx->stream>>>(d_X, D, d_idx, n,
+                                                                                                            d_out));
+    return PHK_OK;
+}
 
 // svm_check_parameter (svm.cpp:3129) for nu-SVC with two classes of n0 / n1 rows, and the other arguments
 static int svm_check(uint64_t n0, uint64_t n1, double nu, double gamma, double tol) {
@@ -432,16 +249,7 @@ static int svm_fit_grouped(phk_ctx *ctx, const double *d_Xg, uint64_t n0, uint64
     PHK_HIP(hipMemcpyAsync(alpha, a0.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PHK_HIP(hipMemcpyAsync(dctl, &c0, sizeof(SvmCtl), hipMemcpyHostToDevice, ctx->stream));
     PHK_TRY(phk_launch_rownorm(ctx, d_Xg, n, D, xn));
-    const dim3 grid((unsigned)phk_div_up(n, GT_CHUNK), (unsigned)phk_div_up(n, GT_QB));
-    if (D % GT_KC == 0) {
-        PHK_LAUNCH(ctx, "phk_svm_gram_kernel",
-                   (phk_svm_tile_kernel<true, true><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
-                       d_Xg, xn, n, d_Xg, xn, n, D, gamma, nullptr, dy, Qf, nullptr)));
-    } else {
-        PHK_LAUNCH(ctx, "phk_svm_gram_kernel",
-                   (phk_svm_tile_kernel<false, true><<<grid, dim3(GT_WAVES * 64), 0, ctx->stream>>>(
-                       d_Xg, xn, n, d_Xg, xn, n, D, gamma, nullptr, dy, Qf, nullptr)));
-    }
+    PHK_TRY(svm_launch_gram(ctx, d_Xg, xn, n, D, gamma, dy, Qf));
     PHK_LAUNCH(ctx, "phk_svm_grad_init_kernel",
                phk_svm_grad_init_kernel<<<dim3((unsigned)phk_div_up(n, 256)), dim3(256), 0, ctx->stream>>>(Qf, alpha, n, G));
     SvmCtl c;
@@ -475,9 +283,9 @@ static int svm_fit_grouped(phk_ctx *ctx, const double *d_Xg, uint64_t n0, uint64
 // Decision over support vectors d_sv[n_sv][D] (norms d_svn, coefficients d_coef) for queries d_Q[N][D] or uint32 count
 // rows (normalised into the workspace first).  SCORE: the method's 1.0 / 0.0 (NaN rows NaN, counted in d_status); else
 // libsvm's value.
-static int svm_decision_run(phk_ctx *ctx, const double *d_Q, const uint32_t *d_counts, uint64_t N, const double *d_sv,
-                            const double *d_svn, const double *d_coef, uint64_t n_sv, uint64_t D, double gamma, double rho,
-                            bool score, double *d_out, uint32_t *d_status) {
+int svm_decision_run(phk_ctx *ctx, const double *d_Q, const uint32_t *d_counts, uint64_t N, const double *d_sv,
+                     const double *d_svn, const double *d_coef, uint64_t n_sv, uint64_t D, double gamma, double rho, bool score,
+                     double *d_out, uint32_t *d_status) {
     const uint32_t S = (uint32_t)phk_div_up(n_sv, GT_CHUNK);
     const bool full = D % GT_KC == 0;
     return gram_query_batches(

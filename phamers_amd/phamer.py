@@ -89,7 +89,9 @@ class phamer_scorer(object):
         self.both_strands = False           # fold every count row with its reverse complement (module docstring)
         self.positive_bandwidth = 0.005     # scripts/phamer.py:82-83 (density method)
         self.negative_bandwidth = 0.01
-        self.k_clusters_positive = 86       # scripts/phamer.py:80-89 (dbscan method: its k-means fallback, eps, min_samples)
+        self.svm_nu = 0.5                   # NuSVC()'s defaults (svm method); a table of other values: svm_grid.py
+        self.svm_gamma = 'scale'
+        self.k_clusters_positive = 86      # scripts/phamer.py:80-89 (dbscan method: its k-means fallback, eps, min_samples)
         self.k_clusters_negative = 20
         self.eps = [1, 1]
         self.min_samples = [2, 2]
@@ -462,7 +464,7 @@ class phamer_scorer(object):
             if method == 'density':
                 model.set_bandwidths(self.positive_bandwidth, self.negative_bandwidth)
             elif method == 'svm':
-                model.fit_svm()                                   # NuSVC() defaults: nu 0.5, gamma 'scale', tol 1e-3
+                model.fit_svm(self.svm_nu, self.svm_gamma)        # NuSVC() defaults: nu 0.5, gamma 'scale', tol 1e-3
             if self._batch is not None:
                 return self._batch.score(model, method)          # resident counts; NaN rows raise ValueError
             q = np.asarray(self._rows, dtype=np.float64)
