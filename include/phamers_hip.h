@@ -534,6 +534,40 @@ int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint32_t *ks, c
                   const uint64_t *draw_off, double tol_rel, int max_iter, uint32_t chunk, int64_t pair_budget, uint32_t *labels,
                   uint32_t *seeds, double *sil, uint32_t *status, int32_t *n_iter, double *min_gap, double *seed_margin);
 
+/* ---- the cross-validated k_neighbors x k_clusters grid of the knn / kmeans / combo methods.  Host
+ * pointers, float64.  create: X[M][D] = vstack(positive, negative) with a held-out fold (< folds) and a class (non-zero =
+ * positive) per row, all resident.  Train set `slot * folds + f` (slot 0 = positive, 1 = negative) = the rows of that class
+ * outside fold f, in row order.
+ *   fit: S k-means problems, problem s on train set set[s] with k = ks[s], first centre first_seed[s] (a position in the
+ *     set) and draws as phk_sweep_run takes them; the stages run on the set's rows less set_mean[set][D] (the caller's:
+ *     NumPy's column mean of those rows), tolerance set_tol[set] (absolute).  The problems of a chunk (`chunk`, 0 = 64) share
+ *     their row count.  The centroids of problem s -- the mean of its clusters' member rows of X as given, summed in row
+ *     order -- go to rows bank_off[s] .. + ks[s] of the resident bank of bank_rows rows (a call with another bank_rows makes
+ *     a new, zeroed bank; S = 0 only does that).  status[s]: PHK_COMBO_GRID_EMPTY; n_iter, min_gap, seed_margin as
+ *     phk_sweep_run reports them;
+ *   get_centroids / put_centroids: rows row0 .. row0 + rows of the bank to / from the host;
+ *   score: knn_out[Kn][M] = the vote (+-1.0, an even split is -1) of the first kn[i] <= 64 rows outside the row's own
+ *     fold in order of (direct-difference chain, row index); km_out[Ku][M] = tanh((en - ep) / (ep + en)) of the square roots
+ *     of the smallest chains to the positive / negative centroids of value j of the row's fold, the bank laid out as fold f at
+ *     rows f * Cb, Cb = 2 * sum(ku): the positive segments ku[0], ku[1], ... then the negative ones.  Kn or Ku may be 0.
+ *     rows_per_pass (0 = a 256 MiB block of the pair matrix; rounded up to 64) = query rows per launch of the pair passes.
+ * A cell does not depend on the other values, on `chunk` or on rows_per_pass.  PHK_ERR_NAN for NaN / infinite rows (create);
+ * PHK_ERR_ARG for folds < 2, M > 2^22, a k outside 1..n of its train set, kn outside 1..min(64, smallest train set), a bank
+ * that does not match ku. */
+#define PHK_COMBO_GRID_EMPTY PHK_PLACEMENT_EMPTY
+typedef struct phk_combo_grid phk_combo_grid;
+int phk_combo_grid_create(phk_ctx *ctx, const double *X, uint64_t M, uint64_t D, const uint32_t *fold_of, const uint8_t *is_positive,
+                          uint32_t folds, phk_combo_grid **out);
+int phk_combo_grid_destroy(phk_ctx *ctx, phk_combo_grid *g);
+int phk_combo_grid_fit(phk_ctx *ctx, phk_combo_grid *g, uint64_t S, const uint32_t *set, const uint32_t *ks, const uint32_t *first_seed,
+                       const double *draws, const uint64_t *draw_off, const double *set_mean, const double *set_tol, int max_iter,
+                       uint32_t chunk, uint64_t bank_rows, const uint64_t *bank_off, uint32_t *status, int32_t *n_iter, double *min_gap,
+                       double *seed_margin);
+int phk_combo_grid_get_centroids(phk_ctx *ctx, phk_combo_grid *g, uint64_t row0, uint64_t rows, double *out);
+int phk_combo_grid_put_centroids(phk_ctx *ctx, phk_combo_grid *g, uint64_t row0, uint64_t rows, const double *in);
+int phk_combo_grid_score(phk_ctx *ctx, phk_combo_grid *g, uint32_t Kn, const uint32_t *kn, uint32_t Ku, const uint32_t *ku,
+                         uint64_t rows_per_pass, double *knn_out, double *km_out);
+
 /* ---- PCA and t-SNE (phamer_scorer.do_tsne, scripts/phamer.py:337-366).  Host pointers, float64 throughout;
  * every sum is taken in an order fixed by the shapes alone (no floating-point atomics): results are bit-identical from run
  * to run.  The callers (phamers_amd/manifold.py) reject NaN / infinite input first. ---- */

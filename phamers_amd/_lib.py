@@ -124,6 +124,13 @@ SIGNATURES = {
     "phk_sweep_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_sweep_run": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_u32,
                               ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_combo_grid_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u32, P(c_void_p)]),
+    "phk_combo_grid_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_combo_grid_fit": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_u32, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_combo_grid_get_centroids": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p]),
+    "phk_combo_grid_put_centroids": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p]),
+    "phk_combo_grid_score": (c_int, [c_void_p, c_void_p, c_u32, c_void_p, c_u32, c_void_p, c_u64, c_void_p, c_void_p]),
     "phk_pca_covariance": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p]),
     "phk_pca_project": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u64, c_void_p]),
     "phk_tsne_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
@@ -536,6 +543,120 @@ class Sweep(object):
     def close(self):
         if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
             self.ctx.lib.phk_sweep_destroy(self.ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+COMBO_GRID_EMPTY = 2
+COMBO_GRID_MAX_NEIGHBORS = 64   # a row's neighbour classes are one 64-bit word
+COMBO_GRID_MAX_ROWS = 1 << 22
+
+
+class ComboGrid(object):
+    """Device-resident state of the k_neighbors x k_clusters grid (phk_combo_grid): the rows of ``vstack(positive,
+    negative)`` with their held-out fold and class, the row lists of the train sets and the centroid bank.  Train set
+    ``slot * folds + fold`` (slot 0: positive, 1: negative) holds that class's rows outside the fold, in row order."""
+
+    def __init__(self, ctx, X, fold_of, is_positive, folds):
+        self.ctx = ctx
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("the rows must be a non-empty 2-D array")
+        self.M, self.D = X.shape
+        self.folds = int(folds)
+        fold_of = np.ascontiguousarray(fold_of, dtype=np.uint32)
+        cls = np.ascontiguousarray(np.asarray(is_positive) != 0, dtype=np.uint8)
+        if fold_of.shape != (self.M,) or cls.shape != (self.M,):
+            raise ValueError("one fold and one class per row")
+        h = ctypes.c_void_p()
+        rc = ctx.lib.phk_combo_grid_create(ctx.handle, ptr(X), self.M, self.D, ptr(fold_of), ptr(cls), self.folds, ctypes.byref(h))
+        if rc == PHK_ERR_NAN:
+            raise ValueError("Input contains NaN.")
+        if rc == PHK_ERR_ARG:
+            raise ValueError(last_error())
+        check(rc)
+        self.handle = h
+        self.bank_rows = 0
+
+    def _call(self, rc):
+        if rc == PHK_ERR_ARG:
+            raise ValueError(last_error())
+        check(rc)
+
+    def _open(self):
+        if not getattr(self, "handle", None):
+            raise ValueError("this ComboGrid is closed")
+
+    def fit(self, sets, ks, first_seeds, draws, set_mean, set_tol, bank_rows, bank_off, max_iter=300, chunk=0):
+        """One k-means problem per entry (``draws[s]``: the (ks[s] - 1, 2 + int(ln ks[s])) uniforms); the centroids go to
+        rows ``bank_off[s]`` .. of a bank of ``bank_rows`` rows.  dict of per-problem status (COMBO_GRID_EMPTY bit), n_iter,
+        min_gap, seed_margin."""
+        self._open()
+        sets = np.ascontiguousarray(sets, dtype=np.uint32)
+        ks = np.ascontiguousarray(ks, dtype=np.uint32)
+        first = np.ascontiguousarray(first_seeds, dtype=np.uint32)
+        bank_off = np.ascontiguousarray(bank_off, dtype=np.uint64)
+        S = len(ks)
+        if sets.shape != (S,) or first.shape != (S,) or bank_off.shape != (S,) or len(draws) != S:
+            raise ValueError("one train set, first seed, bank offset and set of draws per problem")
+        set_mean = np.ascontiguousarray(set_mean, dtype=np.float64)
+        set_tol = np.ascontiguousarray(set_tol, dtype=np.float64)
+        if set_mean.shape != (2 * self.folds, self.D) or set_tol.shape != (2 * self.folds,):
+            raise ValueError("set_mean must be (%d, %d) and set_tol (%d,)" % (2 * self.folds, self.D, 2 * self.folds))
+        flat, offs, at = [], np.zeros(S, dtype=np.uint64), 0
+        for s in range(S):
+            k = int(ks[s])
+            d = np.ascontiguousarray(draws[s], dtype=np.float64)
+            if k >= 1 and d.size != (k - 1) * (2 + int(np.log(k))):
+                raise ValueError("draws of problem %d must be (%d, %d)" % (s, k - 1, 2 + int(np.log(k))))
+            offs[s] = at
+            at += d.size
+            flat.append(d.ravel())
+        flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0), dtype=np.float64)
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.float64)
+        out = {"status": np.zeros(S, dtype=np.uint32), "n_iter": np.zeros(S, dtype=np.int32),
+               "min_gap": np.zeros(S, dtype=np.float64), "seed_margin": np.zeros(S, dtype=np.float64)}
+        self._call(self.ctx.lib.phk_combo_grid_fit(self.ctx.handle, self.handle, S, ptr(sets), ptr(ks), ptr(first), ptr(flat), ptr(offs),
+                                                   ptr(set_mean), ptr(set_tol), int(max_iter), int(chunk), int(bank_rows), ptr(bank_off),
+                                                   ptr(out["status"]), ptr(out["n_iter"]), ptr(out["min_gap"]),
+                                                   ptr(out["seed_margin"])))
+        self.bank_rows = int(bank_rows)
+        return out
+
+    def get_centroids(self, row0, rows):
+        self._open()
+        out = np.empty((int(rows), self.D), dtype=np.float64)
+        self._call(self.ctx.lib.phk_combo_grid_get_centroids(self.ctx.handle, self.handle, int(row0), int(rows), ptr(out)))
+        return out
+
+    def put_centroids(self, row0, centroids):
+        self._open()
+        C = np.ascontiguousarray(centroids, dtype=np.float64)
+        if C.ndim != 2 or C.shape[1] != self.D:
+            raise ValueError("centroids must be (rows, %d)" % self.D)
+        self._call(self.ctx.lib.phk_combo_grid_put_centroids(self.ctx.handle, self.handle, int(row0), C.shape[0], ptr(C)))
+
+    def score(self, k_neighbors, k_clusters, rows_per_pass=0):
+        """(knn (Kn, M) of +-1.0, kmeans (Ku, M)) for the bank laid out as include/phamers_hip.h describes."""
+        self._open()
+        kn = np.ascontiguousarray(k_neighbors, dtype=np.uint32).ravel()
+        ku = np.ascontiguousarray(k_clusters, dtype=np.uint32).ravel()
+        knn = np.empty((len(kn), self.M), dtype=np.float64)
+        km = np.empty((len(ku), self.M), dtype=np.float64)
+        self._call(self.ctx.lib.phk_combo_grid_score(self.ctx.handle, self.handle, len(kn), ptr(kn) if len(kn) else None, len(ku),
+                                                     ptr(ku) if len(ku) else None, int(rows_per_pass),
+                                                     ptr(knn) if len(kn) else None, ptr(km) if len(ku) else None))
+        return knn, km
+
+    def close(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self.ctx.lib.phk_combo_grid_destroy(self.ctx.handle, self.handle)
         self.handle = None
 
     def __del__(self):

@@ -231,12 +231,8 @@ class cross_validator(object):
         return os.path.join(self.output_directory, "all_algorithms_auc.txt")
 
 
-def main(argv=None):
-    """The reference's command line (scripts/cross_validate.py:240-307) without its plots: metrics.txt and scores.txt in the
-    output directory, with -a also all_algorithms_auc.txt (``method<TAB>repr(auc)`` per line).  --seed and --kmeans are
-    this project's additions, and so is --both_strands."""
+def _parser():
     import argparse
-    from . import fileIO, kmer
     parser = argparse.ArgumentParser(description="This script is for doing N-fold cross validation of the Phamer scoring algorithm",
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     input_group = parser.add_argument_group("Inputs")
@@ -254,9 +250,23 @@ def main(argv=None):
     options_group.add_argument('--kmeans', default='sklearn', choices=('sklearn', 'gpu'), help="Per-fold k-means fit")
     options_group.add_argument('--both_strands', action='store_true',
                                help="Fold both feature files with their reverse complement before normalising")
+    # (long options only, as in phamers_amd.phamer, where -k is the k-mer length; absent, the validator keeps its own values)
+    options_group.add_argument('--k_neighbors', type=int, default=argparse.SUPPRESS, metavar='K',
+                               help="Neighbours of the k-NN vote (the validator's default: 3; combo_grid.py tables others)")
+    options_group.add_argument('--k_clusters', type=int, default=argparse.SUPPRESS, metavar='K',
+                               help="Clusters per class of the per-fold k-means fit (the validator's default: 86)")
     console_options_group = parser.add_argument_group("Console Options")
     console_options_group.add_argument('-v', '--verbose', action='store_true', default=False, help="Verbose output")
     console_options_group.add_argument('--debug', action='store_true', default=False, help="Debug console")
+    return parser
+
+
+def main(argv=None):
+    """The reference's command line (scripts/cross_validate.py:240-307) without its plots: metrics.txt and scores.txt in the
+    output directory, with -a also all_algorithms_auc.txt (``method<TAB>repr(auc)`` per line).  --seed and --kmeans are
+    this project's additions, and so are --both_strands and --k_neighbors / --k_clusters (4.18)."""
+    from . import fileIO, kmer
+    parser = _parser()
     args = parser.parse_args(argv)
     logger.setLevel(logging.DEBUG if args.debug else logging.INFO if args.verbose else logging.WARNING)
 
@@ -264,6 +274,7 @@ def main(argv=None):
     validator.method, validator.N = args.method, args.N_fold
     validator.output_directory = args.output_directory
     validator.seed, validator.kmeans = args.seed, args.kmeans
+    phamer._apply_k_options(validator, args)
     validator.positive_ids, positive_data = fileIO.read_feature_file(args.positive_features_file)
     validator.negative_ids, negative_data = fileIO.read_feature_file(args.negative_features_file)
     if args.both_strands:

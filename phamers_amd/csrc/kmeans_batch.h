@@ -1,4 +1,4 @@
-// kmeans_batch.h -- the batched k-means core of placement.hip and sweep.hip (4.11): a chunk of independent
+// kmeans_batch.h -- the batched k-means core of placement.hip, sweep.hip (4.11) and combo_grid.hip (4.18): a chunk of independent
 // k-means problems, every stage one launch for the whole chunk, the grid's second dimension (or its only one) the problem.
 //   seeding : scikit-learn's k-means++ with the caller's draws (learning.kmeans_plusplus_seeds is the specification): per
 //             centre a distance launch (trial candidates to all rows, float64 direct differences) and a choose/search launch
@@ -8,7 +8,7 @@
 //   Lloyd   : kmeans.hip's phk_kmeans_lloyd iteration, operation order included (labels, sweep counts and min_gap equal the
 //             single-problem path's bit for bit), each problem with its own centres, labels, stopping flags and sweep count;
 //             the host reads one word per sweep for the chunk, a finished problem's workgroups return at once.
-// Where a problem's rows come from is a compile-time parameter of the kernels (KbCentredRows, KbAppendedRows below); each
+// Where a problem's rows come from is a compile-time parameter of the kernels (KbCentredRows, KbAppendedRows, KbFoldRows below); each
 // client instantiates them for its own source.  Everything is float64 and order-deterministic (the only atomics are integer
 // counts and minima); every sum's order is fixed by the rows, the labels and the problem alone, so a problem's result does
 // not depend on its place in the chunk, on the chunking or on the run.
@@ -70,6 +70,17 @@ struct KbAppendedRows {       // nX resident reference rows plus problem b's own
     uint64_t nX;
     __device__ __forceinline__ const double *row(uint32_t b, uint64_t i, uint64_t D) const { return i < nX ? X + i * D : Z + (uint64_t)b * D; }
     __device__ __forceinline__ double shift(uint32_t b, uint64_t d, uint64_t D) const { return mean[(uint64_t)b * D + d]; }
+    __device__ static __forceinline__ double value(double x, double m) { return x - m; }
+};
+
+struct KbFoldRows {           // problem b's row i is the resident row X[idx[ioff[b] + i]] (a fold's train rows), centred on the fly
+    const double *X;          // [M][D]
+    const int32_t *idx;       // the row lists of the train sets, one after the other
+    const uint64_t *ioff;     // [Bc] where problem b's list starts in idx
+    const double *mean;       // the train sets' column means, one after the other
+    const uint64_t *moff;     // [Bc] where problem b's mean starts
+    __device__ __forceinline__ const double *row(uint32_t b, uint64_t i, uint64_t D) const { return X + (uint64_t)idx[ioff[b] + i] * D; }
+    __device__ __forceinline__ double shift(uint32_t b, uint64_t d, uint64_t) const { return mean[moff[b] + d]; }
     __device__ static __forceinline__ double value(double x, double m) { return x - m; }
 };
 

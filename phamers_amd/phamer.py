@@ -645,6 +645,11 @@ def _parser():
             (('--neighbors',), dict(type=int, default=argparse.SUPPRESS, metavar='K',
                                     help='Also write phamer_neighbors.csv: the K nearest reference rows of every contig '
                                          '(1..28; one GPU only)')),
+            # (long options only: -k is the k-mer length.  No default, as --neighbors: absent, the scorer keeps its own)
+            (('--k_neighbors',), dict(type=int, default=argparse.SUPPRESS, metavar='K',
+                                      help="Neighbours of the k-NN vote (the scorer's default: 3; combo_grid.py tables others)")),
+            (('--k_clusters',), dict(type=int, default=argparse.SUPPRESS, metavar='K',
+                                     help="Clusters per class of the k-means fit (the scorer's default: 86)")),
             (('-v', '--verbose'), dict(action='store_true')),
             (('--debug',), dict(action='store_true')),
             # the rest of the reference's command line (scripts/phamer.py:515-553), so that its launch scripts
@@ -665,12 +670,22 @@ def _parser():
     return ap
 
 
+def _apply_k_options(scorer, args):
+    """--k_neighbors / --k_clusters, where given, onto the scorer's attributes of those names."""
+    for name in ("k_neighbors", "k_clusters"):
+        if hasattr(args, name):
+            if getattr(args, name) < 1:
+                raise SystemExit("--%s must be >= 1 (got %d). Exiting..." % (name, getattr(args, name)))
+            setattr(scorer, name, getattr(args, name))
+
+
 def _run(ap, args):
     logger.setLevel(logging.DEBUG if args.debug else logging.INFO if args.verbose else logging.WARNING)
 
     scorer = phamer_scorer()
     scorer.kmer_length = args.kmer_length
     scorer.both_strands = args.both_strands
+    _apply_k_options(scorer, args)
     scorer.input_directory, scorer.fasta_file, scorer.features_file = args.input_directory, args.fasta_file, args.features_file
     if args.data_directory:
         scorer.data_directory = args.data_directory
@@ -776,6 +791,7 @@ def _run_rank(ap, args):
         scorer = phamer_scorer()
         scorer.kmer_length = args.kmer_length
         scorer.both_strands = args.both_strands
+        _apply_k_options(scorer, args)
         scorer.input_directory, scorer.fasta_file, scorer.features_file = args.input_directory, args.fasta_file, args.features_file
         if args.data_directory:
             scorer.data_directory = args.data_directory
