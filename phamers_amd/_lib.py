@@ -227,6 +227,58 @@ def last_error():
     return msg.split(": ", 1)[1] if msg.startswith("phk_") and ": " in msg else msg
 
 
+def check_value(rc, nan=True, arg=True):
+    """``check`` for calls whose refusals are the caller's ValueError: PHK_ERR_NAN (``nan``) as scikit-learn words it for the
+    reference, PHK_ERR_ARG (``arg``) with the library's message."""
+    if nan and rc == PHK_ERR_NAN:
+        raise ValueError("Input contains NaN.")
+    if arg and rc == PHK_ERR_ARG:
+        raise ValueError(last_error())
+    check(rc)
+
+
+def kmeans_trials(k):
+    """Seeding trials per centre of a k-means problem (kb_trials, csrc/kmeans_batch.h)."""
+    return 2 + int(np.log(k))
+
+
+def _pack_draws(ks, draws):
+    """The problems' draws one after the other, as the batched k-means entry points take them: (flat float64, offsets
+    uint64).  ``draws[s]`` holds the (ks[s] - 1) * kmeans_trials(ks[s]) uniforms of problem s; an empty result is one zero."""
+    flat, offs, at = [], np.zeros(len(ks), dtype=np.uint64), 0
+    for s, k in enumerate(int(k) for k in ks):
+        d = np.ascontiguousarray(draws[s], dtype=np.float64)
+        if k >= 1 and d.size != (k - 1) * kmeans_trials(k):
+            raise ValueError("draws of problem %d must be (%d, %d)" % (s, k - 1, kmeans_trials(k)))
+        offs[s] = at
+        at += d.size
+        flat.append(d.ravel())
+    flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0), dtype=np.float64)
+    return (flat if flat.size else np.zeros(1, dtype=np.float64)), offs
+
+
+class _Resident(object):
+    """A handle the library keeps for a context (``self.ctx``, ``self.handle``); ``_destroy`` names the entry point
+    ``(ctx handle, handle)`` that releases it.  Closing twice, or after the context, does nothing."""
+    _destroy = None
+
+    def _open(self):
+        if not getattr(self, "handle", None):
+            raise ValueError("this %s is closed" % type(self).__name__)
+
+    def close(self):
+        ctx = getattr(self, "ctx", None)
+        if getattr(self, "handle", None) and getattr(ctx, "handle", None):
+            getattr(ctx.lib, self._destroy)(ctx.handle, self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def default_device():
     for var in ("PHAMERS_HIP_DEVICE", "LOCAL_RANK"):
         v = os.environ.get(var)
@@ -329,8 +381,9 @@ class Context(object):
         return out
 
 
-class Model(object):
+class Model(_Resident):
     """Device-resident training side of phamer_scorer.score_points."""
+    _destroy = "phk_model_destroy"
 
     def __init__(self, ctx, positive, negative, positive_centroids=None, negative_centroids=None,
                  k_neighbors=3):
@@ -357,17 +410,6 @@ class Model(object):
                                        self.D, int(k_neighbors), ctypes.byref(h)))
         self.handle = h
 
-    def close(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx.lib.phk_model_destroy(self.ctx.handle, self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_centroids(self, positive_centroids, negative_centroids):
         """Replace the centroid segments (same counts as at creation): a cross-validation fold's k-means result."""
         cp = np.ascontiguousarray(positive_centroids, dtype=np.float64)
@@ -391,9 +433,7 @@ class Model(object):
             X = X[~self._mask]
         g = svm_gamma(X, gamma)
         rc = self.ctx.lib.phk_model_fit_svm(self.ctx.handle, self.handle, float(nu), g, float(tol))
-        if rc == PHK_ERR_ARG:
-            raise ValueError(last_error())
-        check(rc)
+        check_value(rc, nan=False)
         return g
 
     def set_bandwidths(self, h_pos, h_neg):
@@ -427,9 +467,10 @@ PLACEMENT_DUPLICATE, PLACEMENT_EMPTY = 1, 2
 SWEEP_EMPTY = 2
 
 
-class Placement(object):
+class Placement(_Resident):
     """Device-resident reference rows of the batched per-contig placement (phk_placement): ``run`` solves, for every row
     of ``Z``, k-means of the reference rows with that row appended and the silhouettes of the row's cluster."""
+    _destroy = "phk_placement_destroy"
 
     def __init__(self, ctx, reference):
         self.ctx = ctx
@@ -438,25 +479,20 @@ class Placement(object):
             raise ValueError("reference rows must be a non-empty 2-D array")
         self.n, self.D = X.shape
         h = ctypes.c_void_p()
-        rc = ctx.lib.phk_placement_create(ctx.handle, ptr(X), self.n, self.D, ctypes.byref(h))
-        if rc == PHK_ERR_NAN:
-            raise ValueError("Input contains NaN.")
-        check(rc)
+        check_value(ctx.lib.phk_placement_create(ctx.handle, ptr(X), self.n, self.D, ctypes.byref(h)), arg=False)
         self.handle = h
 
     def run(self, Z, k, first_seed, draws, tol=1e-4, max_iter=300, chunk=0):
         """dict of per-problem arrays: labels (B, n + 1) uint32, seeds (B, k), sil (B, n + 1) of which the first
         n_members[b] count, n_members, status (PLACEMENT_* bits), n_iter, min_gap, seed_margin."""
-        if not getattr(self, "handle", None):
-            raise ValueError("this Placement is closed")
+        self._open()
         Z = np.ascontiguousarray(Z, dtype=np.float64)
         if Z.ndim != 2 or Z.shape[1] != self.D:
             raise ValueError("contig rows must be (B, %d)" % self.D)
         B, n1, k = Z.shape[0], self.n + 1, int(k)
         draws = np.ascontiguousarray(draws, dtype=np.float64)
-        trials = 2 + int(np.log(k))
-        if draws.shape != (k - 1, trials):
-            raise ValueError("draws must be (%d, %d)" % (k - 1, trials))
+        if k >= 1 and draws.shape != (k - 1, kmeans_trials(k)):   # (k < 1 is the library's to refuse, as in Sweep.run)
+            raise ValueError("draws must be (%d, %d)" % (k - 1, kmeans_trials(k)))
         out = {"labels": np.empty((B, n1), dtype=np.uint32), "seeds": np.empty((B, k), dtype=np.uint32),
                "sil": np.empty((B, n1), dtype=np.float64), "n_members": np.empty(B, dtype=np.uint32),
                "status": np.empty(B, dtype=np.uint32), "n_iter": np.empty(B, dtype=np.int32),
@@ -465,28 +501,14 @@ class Placement(object):
                                             int(max_iter), int(chunk), ptr(out["labels"]), ptr(out["seeds"]), ptr(out["sil"]),
                                             ptr(out["n_members"]), ptr(out["status"]), ptr(out["n_iter"]), ptr(out["min_gap"]),
                                             ptr(out["seed_margin"]))
-        if rc == PHK_ERR_NAN:
-            raise ValueError("Input contains NaN.")
-        if rc == PHK_ERR_ARG:
-            raise ValueError(last_error())
-        check(rc)
+        check_value(rc)
         return out
 
-    def close(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx.lib.phk_placement_destroy(self.ctx.handle, self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Sweep(object):
+class Sweep(_Resident):
     """Device-resident rows of the k-means sweep (phk_sweep): ``run`` solves one k-means problem per entry of ``ks`` on the
     same rows, each with its own first centre and draws, and (optionally) the silhouettes of every row of every problem."""
+    _destroy = "phk_sweep_destroy"
 
     def __init__(self, ctx, data):
         self.ctx = ctx
@@ -495,35 +517,20 @@ class Sweep(object):
             raise ValueError("the rows must be a non-empty 2-D array")
         self.n, self.D = X.shape
         h = ctypes.c_void_p()
-        rc = ctx.lib.phk_sweep_create(ctx.handle, ptr(X), self.n, self.D, ctypes.byref(h))
-        if rc == PHK_ERR_NAN:
-            raise ValueError("Input contains NaN.")
-        check(rc)
+        check_value(ctx.lib.phk_sweep_create(ctx.handle, ptr(X), self.n, self.D, ctypes.byref(h)), arg=False)
         self.handle = h
 
     def run(self, ks, first_seeds, draws, silhouettes=True, tol=1e-4, max_iter=300, chunk=0, pair_budget=-1):
         """``draws[s]`` = the (ks[s] - 1, 2 + int(ln ks[s])) uniforms of problem s.  dict of per-problem results: labels
         (S, n) uint32, seeds (list of S arrays), sil (S, n) or None, status (SWEEP_EMPTY bit), n_iter, min_gap,
         seed_margin.  ``pair_budget``: bytes the stored pair distances may take (-1: a quarter of the free memory)."""
-        if not getattr(self, "handle", None):
-            raise ValueError("this Sweep is closed")
+        self._open()
         ks = np.ascontiguousarray(ks, dtype=np.uint32)
         S, n = len(ks), self.n
         first = np.ascontiguousarray(first_seeds, dtype=np.uint32)
         if first.shape != (S,) or len(draws) != S:
             raise ValueError("one first seed and one set of draws per problem")
-        flat, offs, at = [], np.zeros(S, dtype=np.uint64), 0
-        for s in range(S):
-            k = int(ks[s])
-            d = np.ascontiguousarray(draws[s], dtype=np.float64)
-            if k >= 1 and d.size != (k - 1) * (2 + int(np.log(k))):
-                raise ValueError("draws of problem %d must be (%d, %d)" % (s, k - 1, 2 + int(np.log(k))))
-            offs[s] = at
-            at += d.size
-            flat.append(d.ravel())
-        flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0), dtype=np.float64)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.float64)
+        flat, offs = _pack_draws(ks, draws)
         seeds = np.empty(int(ks.sum()), dtype=np.uint32)
         out = {"labels": np.empty((S, n), dtype=np.uint32), "sil": np.empty((S, n), dtype=np.float64) if silhouettes else None,
                "status": np.empty(S, dtype=np.uint32), "n_iter": np.empty(S, dtype=np.int32),
@@ -532,24 +539,9 @@ class Sweep(object):
                                         int(max_iter), int(chunk), int(pair_budget), ptr(out["labels"]), ptr(seeds),
                                         ptr(out["sil"]) if silhouettes else None, ptr(out["status"]), ptr(out["n_iter"]),
                                         ptr(out["min_gap"]), ptr(out["seed_margin"]))
-        if rc == PHK_ERR_NAN:
-            raise ValueError("Input contains NaN.")
-        if rc == PHK_ERR_ARG:
-            raise ValueError(last_error())
-        check(rc)
+        check_value(rc)
         out["seeds"] = np.split(seeds, np.cumsum(ks.astype(np.int64))[:-1]) if S else []
         return out
-
-    def close(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx.lib.phk_sweep_destroy(self.ctx.handle, self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 COMBO_GRID_EMPTY = 2
@@ -557,10 +549,11 @@ COMBO_GRID_MAX_NEIGHBORS = 64   # a row's neighbour classes are one 64-bit word
 COMBO_GRID_MAX_ROWS = 1 << 22
 
 
-class ComboGrid(object):
+class ComboGrid(_Resident):
     """Device-resident state of the k_neighbors x k_clusters grid (phk_combo_grid): the rows of ``vstack(positive,
     negative)`` with their held-out fold and class, the row lists of the train sets and the centroid bank.  Train set
     ``slot * folds + fold`` (slot 0: positive, 1: negative) holds that class's rows outside the fold, in row order."""
+    _destroy = "phk_combo_grid_destroy"
 
     def __init__(self, ctx, X, fold_of, is_positive, folds):
         self.ctx = ctx
@@ -574,23 +567,13 @@ class ComboGrid(object):
         if fold_of.shape != (self.M,) or cls.shape != (self.M,):
             raise ValueError("one fold and one class per row")
         h = ctypes.c_void_p()
-        rc = ctx.lib.phk_combo_grid_create(ctx.handle, ptr(X), self.M, self.D, ptr(fold_of), ptr(cls), self.folds, ctypes.byref(h))
-        if rc == PHK_ERR_NAN:
-            raise ValueError("Input contains NaN.")
-        if rc == PHK_ERR_ARG:
-            raise ValueError(last_error())
-        check(rc)
+        check_value(ctx.lib.phk_combo_grid_create(ctx.handle, ptr(X), self.M, self.D, ptr(fold_of), ptr(cls), self.folds,
+                                                  ctypes.byref(h)))
         self.handle = h
         self.bank_rows = 0
 
     def _call(self, rc):
-        if rc == PHK_ERR_ARG:
-            raise ValueError(last_error())
-        check(rc)
-
-    def _open(self):
-        if not getattr(self, "handle", None):
-            raise ValueError("this ComboGrid is closed")
+        check_value(rc, nan=False)
 
     def fit(self, sets, ks, first_seeds, draws, set_mean, set_tol, bank_rows, bank_off, max_iter=300, chunk=0):
         """One k-means problem per entry (``draws[s]``: the (ks[s] - 1, 2 + int(ln ks[s])) uniforms); the centroids go to
@@ -608,18 +591,7 @@ class ComboGrid(object):
         set_tol = np.ascontiguousarray(set_tol, dtype=np.float64)
         if set_mean.shape != (2 * self.folds, self.D) or set_tol.shape != (2 * self.folds,):
             raise ValueError("set_mean must be (%d, %d) and set_tol (%d,)" % (2 * self.folds, self.D, 2 * self.folds))
-        flat, offs, at = [], np.zeros(S, dtype=np.uint64), 0
-        for s in range(S):
-            k = int(ks[s])
-            d = np.ascontiguousarray(draws[s], dtype=np.float64)
-            if k >= 1 and d.size != (k - 1) * (2 + int(np.log(k))):
-                raise ValueError("draws of problem %d must be (%d, %d)" % (s, k - 1, 2 + int(np.log(k))))
-            offs[s] = at
-            at += d.size
-            flat.append(d.ravel())
-        flat = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0), dtype=np.float64)
-        if flat.size == 0:
-            flat = np.zeros(1, dtype=np.float64)
+        flat, offs = _pack_draws(ks, draws)
         out = {"status": np.zeros(S, dtype=np.uint32), "n_iter": np.zeros(S, dtype=np.int32),
                "min_gap": np.zeros(S, dtype=np.float64), "seed_margin": np.zeros(S, dtype=np.float64)}
         self._call(self.ctx.lib.phk_combo_grid_fit(self.ctx.handle, self.handle, S, ptr(sets), ptr(ks), ptr(first), ptr(flat), ptr(offs),
@@ -654,17 +626,6 @@ class ComboGrid(object):
                                                      ptr(knn) if len(kn) else None, ptr(km) if len(ku) else None))
         return knn, km
 
-    def close(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx.lib.phk_combo_grid_destroy(self.ctx.handle, self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 NEIGHBORS_MAX_K = 28
 
@@ -677,11 +638,7 @@ def _neighbor_outputs(n, k):
 
 
 def _neighbor_result(rc, idx, dist):
-    if rc == PHK_ERR_NAN:
-        raise ValueError("Input contains NaN.")   # as scoring does
-    if rc == PHK_ERR_ARG:
-        raise ValueError(last_error())
-    check(rc)
+    check_value(rc)   # (NaN rows: as scoring does)
     return dist, idx.astype(np.int64)
 
 
@@ -810,8 +767,9 @@ def dbscan(ctx, X, eps, min_samples):
     return labels, core.astype(bool), int(k.value)
 
 
-class DbscanRows(object):
+class DbscanRows(_Resident):
     """Rows resident on the device for the DBSCAN parameter sweep (phk_dbscan_sweep_create); ``run`` solves up to 64 cells."""
+    _destroy = "phk_dbscan_sweep_destroy"
 
     def __init__(self, ctx, X):
         X = np.ascontiguousarray(X, dtype=np.float64)
@@ -835,10 +793,6 @@ class DbscanRows(object):
                                             ptr(out["labels"]), ptr(out["coremask"]), ptr(out["n_clusters"]), ptr(out["launches"])))
         return out
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self.ctx.lib.phk_dbscan_sweep_destroy(self.ctx.handle, self.handle)
-            self.handle = None
 
 
 def svm_gamma(X, gamma):
@@ -868,9 +822,7 @@ def nusvc_fit(ctx, X, labels, nu, gamma, tol, max_iter=-1):
     rho, n_sv, n_iter = c_double(), ctypes.c_int32(), ctypes.c_int32()
     rc = ctx.lib.phk_nusvc_fit(ctx.handle, ptr(X), n, X.shape[1], ptr(y), float(nu), float(gamma), float(tol), int(max_iter),
                                ptr(support), ptr(coef), ctypes.byref(rho), ctypes.byref(n_sv), ctypes.byref(n_iter))
-    if rc == PHK_ERR_ARG:
-        raise ValueError(last_error())
-    check(rc)
+    check_value(rc, nan=False)
     k = n_sv.value
     return support[:k].copy(), coef[:k].copy(), rho.value, n_iter.value
 
@@ -941,14 +893,13 @@ def nusvc_sweep(ctx, X, labels, nus, gammas, fold_of=None, folds=0, tol=1e-3, ma
                                  folds, float(tol), int(max_iter), int(lds_rows), int(gammas_per_pass), int(threads),
                                  ptr(out["status"]), ptr(out["n_iter"]), ptr(out["n_sv"]), ptr(out["rho"]), ptr(out["coef"]),
                                  ptr(out["held_dec"]))
-    if rc == PHK_ERR_ARG:
-        raise ValueError(last_error())
-    check(rc)
+    check_value(rc, nan=False)
     return out
 
 
-class Batch(object):
+class Batch(_Resident):
     """Device-resident contig batch (phk_batch): counts + row sums in HBM; see include/phamers_hip.h."""
+    _destroy = "phk_batch_free"
 
     def __init__(self, ctx, handle):
         self.ctx = ctx
@@ -1078,9 +1029,7 @@ class Batch(object):
     def score(self, model, method="combo"):
         out = np.empty(self.n, dtype=np.float64)
         rc = self.ctx.lib.phk_batch_score(self.ctx.handle, model.handle, self.handle, METHODS[method], ptr(out))
-        if rc == PHK_ERR_NAN:
-            raise ValueError("Input contains NaN.")   # what scikit-learn raises for the reference
-        check(rc)
+        check_value(rc, arg=False)
         return out
 
     def neighbors(self, model, k):
@@ -1089,17 +1038,6 @@ class Batch(object):
         idx, dist = _neighbor_outputs(self.n, k)
         return _neighbor_result(self.ctx.lib.phk_batch_neighbors(self.ctx.handle, model.handle, self.handle, int(k), ptr(idx),
                                                                  ptr(dist)), idx, dist)
-
-    def close(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self.ctx.lib.phk_batch_free(self.ctx.handle, self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Fasta(object):

@@ -31,19 +31,15 @@
 struct phk_combo_grid {
     uint64_t M = 0, D = 0;
     uint32_t folds = 0;
-    double *d_x = nullptr;
-    uint32_t *d_fold = nullptr;
-    uint8_t *d_cls = nullptr;
-    int32_t *d_idx = nullptr;            // the train lists of set 0 .. 2 F - 1 (set = slot * F + fold; slot 0 = positive), then
-    uint64_t *d_held_off = nullptr;      // the held-out lists of fold 0 .. F - 1: held_off[f] .. held_off[f + 1] in d_idx
-    std::vector<uint64_t> set_off;       // [2 F + 1] into d_idx
-    std::vector<uint64_t> held_off;      // [F + 1] into d_idx
-    double *d_bank = nullptr;
+    PhkDevMem x, fold, cls;              // X[M][D] (double), a fold id (uint32_t) and a class (uint8_t) per row
+    PhkDevMem idx;                       // int32_t: the train lists of set 0 .. 2 F - 1 (set = slot * F + fold; slot 0 = positive), then
+    PhkDevMem held;                      // the held-out lists of fold 0 .. F - 1: held_off[f] .. held_off[f + 1] in idx (uint64_t here)
+    std::vector<uint64_t> set_off;       // [2 F + 1] into idx
+    std::vector<uint64_t> held_off;      // [F + 1] into idx
+    PhkDevMem bank;                      // double [bank_rows][D]
     uint64_t bank_rows = 0;
-    void *ws = nullptr;                  // the k-means chunks' workspace
-    uint64_t ws_bytes = 0;
-    void *ps = nullptr;                  // the scoring passes' workspace
-    uint64_t ps_bytes = 0;
+    PhkDevMem ws;                        // the k-means chunks' workspace
+    PhkDevMem ps;                        // the scoring passes' workspace
 };
 
 struct CgTile {               // a column tile of the centroid pass: columns [begin, end) of a fold's bank, all of segment seg
@@ -204,18 +200,6 @@ __global__ __launch_bounds__(256) void cg_epilogue_kernel(const uint64_t *__rest
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-static void cg_free(phk_combo_grid *g) {
-    if (g->d_x) (void)hipFree(g->d_x);
-    if (g->d_fold) (void)hipFree(g->d_fold);
-    if (g->d_cls) (void)hipFree(g->d_cls);
-    if (g->d_idx) (void)hipFree(g->d_idx);
-    if (g->d_held_off) (void)hipFree(g->d_held_off);
-    if (g->d_bank) (void)hipFree(g->d_bank);
-    if (g->ws) (void)hipFree(g->ws);
-    if (g->ps) (void)hipFree(g->ps);
-    delete g;
-}
-
 extern "C" int phk_combo_grid_create(phk_ctx *ctx, const double *X, uint64_t M, uint64_t D, const uint32_t *fold_of,
                                      const uint8_t *is_positive, uint32_t folds, phk_combo_grid **out) {
     PHK_ENTER(ctx, "phk_combo_grid_create");
@@ -226,11 +210,10 @@ extern "C" int phk_combo_grid_create(phk_ctx *ctx, const double *X, uint64_t M, 
     for (uint64_t i = 0; i < M; ++i)
         PHK_REQUIRE(fold_of[i] < folds, "phk_combo_grid_create: fold %u of row %llu is not below folds = %u", fold_of[i],
                     (unsigned long long)i, folds);
-    for (uint64_t i = 0; i < M * D; ++i)
-        if (!(X[i] - X[i] == 0.0)) {
-            phk_set_error("phk_combo_grid_create: the rows contain NaN or infinity");
-            return PHK_ERR_NAN;
-        }
+    if (!phk_rows_finite(X, M * D)) {
+        phk_set_error("phk_combo_grid_create: the rows contain NaN or infinity");
+        return PHK_ERR_NAN;
+    }
     const uint32_t F = folds;
     phk_combo_grid *g = new phk_combo_grid;
     g->M = M;
@@ -254,22 +237,18 @@ extern "C" int phk_combo_grid_create(phk_ctx *ctx, const double *X, uint64_t M, 
         g->held_off[f + 1] = idx.size();
     }
     int rc = PHK_OK;
-    if (hipMalloc((void **)&g->d_x, M * D * 8) != hipSuccess || hipMalloc((void **)&g->d_fold, M * 4) != hipSuccess ||
-        hipMalloc((void **)&g->d_cls, M) != hipSuccess || hipMalloc((void **)&g->d_idx, idx.size() * 4) != hipSuccess ||
-        hipMalloc((void **)&g->d_held_off, ((uint64_t)F + 1) * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        cg_free(g);
-        phk_set_error("phk_combo_grid_create: out of device memory (%llu bytes of rows)", (unsigned long long)(M * D * 8));
-        return PHK_ERR_NOMEM;
-    }
-    rc = phk_copy_to_device(ctx, g->d_x, X, M * D * 8);
-    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, g->d_fold, fold_of, M * 4);
-    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, g->d_cls, is_positive, M);
-    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, g->d_idx, idx.data(), idx.size() * 4);
-    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, g->d_held_off, g->held_off.data(), ((uint64_t)F + 1) * 8);
+    auto put = [&](PhkDevMem &m, const char *what, const void *src, uint64_t bytes) {
+        if (rc == PHK_OK) rc = m.alloc("phk_combo_grid_create", what, bytes);
+        if (rc == PHK_OK) rc = phk_copy_to_device(ctx, m.ptr, src, bytes);
+    };
+    put(g->x, "rows", X, M * D * 8);
+    put(g->fold, "fold ids", fold_of, M * 4);
+    put(g->cls, "classes", is_positive, M);
+    put(g->idx, "row lists", idx.data(), idx.size() * 4);
+    put(g->held, "row lists", g->held_off.data(), ((uint64_t)F + 1) * 8);
     if (rc == PHK_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = PHK_ERR_HIP;
     if (rc != PHK_OK) {
-        cg_free(g);
+        delete g;
         return rc;
     }
     *out = g;
@@ -280,7 +259,7 @@ extern "C" int phk_combo_grid_destroy(phk_ctx *ctx, phk_combo_grid *g) {
     PHK_ENTER(ctx, "phk_combo_grid_destroy");
     if (!g) return PHK_OK;
     PHK_HIP(hipStreamSynchronize(ctx->stream));
-    cg_free(g);
+    delete g;
     return PHK_OK;
 }
 
@@ -291,90 +270,51 @@ extern "C" int phk_combo_grid_fit(phk_ctx *ctx, phk_combo_grid *g, uint64_t S, c
     PHK_ENTER(ctx, "phk_combo_grid_fit");
     PHK_REQUIRE(g, "phk_combo_grid_fit: NULL grid");
     const uint64_t D = g->D, nsets = 2 * (uint64_t)g->folds;
-    PHK_REQUIRE(max_iter >= 1 && chunk <= 65535 && bank_rows >= 1 && bank_rows < (1ull << 31),
-                "phk_combo_grid_fit: bad max_iter / chunk / bank_rows");
+    PHK_TRY(kb_check_call("phk_combo_grid_fit", max_iter, chunk));
+    PHK_REQUIRE(bank_rows >= 1 && bank_rows < (1ull << 31), "phk_combo_grid_fit: bad bank_rows");
     PHK_REQUIRE(S == 0 || (set && ks && first_seed && draw_off && set_mean && set_tol && bank_off && status && n_iter && min_gap &&
                            seed_margin),
                 "phk_combo_grid_fit: NULL pointer");
+    auto size_of = [&](uint64_t s) { return g->set_off[set[s] + 1] - g->set_off[set[s]]; };
     uint64_t n_max = 0;
     for (uint64_t s = 0; s < S; ++s) {
         PHK_REQUIRE(set[s] < nsets, "phk_combo_grid_fit: problem %llu names train set %u of %llu", (unsigned long long)s, set[s],
                     (unsigned long long)nsets);
-        const uint64_t n = g->set_off[set[s] + 1] - g->set_off[set[s]];
-        const uint32_t k = ks[s];
-        PHK_REQUIRE(k >= 1 && k <= n, "phk_combo_grid_fit: need 1 <= k <= n (problem %llu: k=%u, n=%llu)", (unsigned long long)s, k,
-                    (unsigned long long)n);
-        PHK_REQUIRE(first_seed[s] < n, "phk_combo_grid_fit: first seed %u of problem %llu is not a row", first_seed[s],
-                    (unsigned long long)s);
-        const uint32_t T = 2 + (uint32_t)std::log((double)k);
-        PHK_REQUIRE(T <= KB_MAX_TRIALS, "phk_combo_grid_fit: k = %u needs %u seeding trials per centre, at most %d are built", k, T,
-                    KB_MAX_TRIALS);
-        PHK_REQUIRE(draws || k == 1, "phk_combo_grid_fit: NULL draws");
-        PHK_REQUIRE(bank_off[s] + k <= bank_rows, "phk_combo_grid_fit: the centroids of problem %llu do not fit the bank",
+        PHK_TRY(kb_check_problem("phk_combo_grid_fit", s, ks[s], size_of(s), first_seed[s], draws));
+        PHK_REQUIRE(bank_off[s] + ks[s] <= bank_rows, "phk_combo_grid_fit: the centroids of problem %llu do not fit the bank",
                     (unsigned long long)s);
         PHK_REQUIRE(set_tol[set[s]] >= 0.0, "phk_combo_grid_fit: bad tolerance of train set %u", set[s]);
-        n_max = std::max(n_max, n);
+        n_max = std::max(n_max, size_of(s));
     }
     if (g->bank_rows != bank_rows) {
         PHK_HIP(hipStreamSynchronize(ctx->stream));
-        if (g->d_bank) (void)hipFree(g->d_bank);
-        g->d_bank = nullptr;
         g->bank_rows = 0;
-        if (hipMalloc((void **)&g->d_bank, bank_rows * D * 8) != hipSuccess) {
-            g->d_bank = nullptr;
-            (void)hipGetLastError();
-            phk_set_error("phk_combo_grid_fit: out of device memory (%llu bytes of centroids)", (unsigned long long)(bank_rows * D * 8));
-            return PHK_ERR_NOMEM;
-        }
+        PHK_TRY(g->bank.alloc("phk_combo_grid_fit", "centroids", bank_rows * D * 8));
         g->bank_rows = bank_rows;
-        PHK_HIP(hipMemsetAsync(g->d_bank, 0, bank_rows * D * 8, ctx->stream));
+        PHK_HIP(hipMemsetAsync(g->bank.ptr, 0, bank_rows * D * 8, ctx->stream));
     }
     if (S == 0) return PHK_OK;
     // chunks: the problems in order of their train set's size (stable), cut where the size changes and after Sc problems
     const uint64_t Sc = std::min<uint64_t>(S, chunk ? chunk : CG_DEFAULT_CHUNK);
-    auto size_of = [&](uint64_t s) { return g->set_off[set[s] + 1] - g->set_off[set[s]]; };
     std::vector<uint64_t> order(S);
     std::iota(order.begin(), order.end(), 0ull);
     std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return size_of(a) < size_of(b); });
     std::vector<uint64_t> cut(1, 0);
     for (uint64_t p = 1; p <= S; ++p)
         if (p == S || p - cut.back() == Sc || size_of(order[p]) != size_of(order[cut.back()])) cut.push_back(p);
-    uint64_t ksum_max = 0, dsum_max = 0;
-    for (uint64_t c = 0; c + 1 < cut.size(); ++c) {
-        uint64_t ksum = 0, dsum = 0;
-        for (uint64_t p = cut[c]; p < cut[c + 1]; ++p) {
-            const uint32_t k = ks[order[p]];
-            ksum += k;
-            dsum += (uint64_t)(k - 1) * (2 + (uint32_t)std::log((double)k));
-        }
-        ksum_max = std::max(ksum_max, ksum);
-        dsum_max = std::max(dsum_max, dsum);
-    }
+    // the chunk's workspace: the core's regions for the largest train set, then what KbFoldRows and the centroids read
     PhkLayout ws;
-    const uint64_t n = n_max;
-    const uint64_t o_cen = ws.take(2 * ksum_max * D * 8), o_lab = ws.take(Sc * n * 4), o_clo = ws.take(Sc * n * 8),
-                   o_td = ws.take(Sc * KB_MAX_TRIALS * n * 8), o_cand = ws.take(Sc * KB_MAX_TRIALS * 4),
-                   o_seed = ws.take(ksum_max * 4), o_size = ws.take(ksum_max * 4), o_st = ws.take(Sc * sizeof(KbState)),
-                   o_draw = ws.take(dsum_max * 8 + 8), o_act = ws.take(256), o_mean = ws.take(nsets * D * 8),
-                   o_ioff = ws.take(Sc * 8), o_moff = ws.take(Sc * 8), o_boff = ws.take(Sc * 8), o_empty = ws.take(Sc * 4);
-    PHK_TRY(kb_grow(ctx, &g->ws, &g->ws_bytes, ws.bytes, "phk_combo_grid_fit", Sc));
-    char *w = (char *)g->ws;
-    KbView v;
-    v.cen = (double *)(w + o_cen);
-    v.labels = (uint32_t *)(w + o_lab);
-    v.closest = (double *)(w + o_clo);
-    v.td = (double *)(w + o_td);
-    v.cand = (uint32_t *)(w + o_cand);
-    v.seeds = (uint32_t *)(w + o_seed);
-    v.sizes = (uint32_t *)(w + o_size);
-    v.st = (KbState *)(w + o_st);
-    v.draws = (const double *)(w + o_draw);
-    v.D = D;
-    v.trials = KB_MAX_TRIALS;
-    const KbFoldRows rows = {g->d_x, g->d_idx, (const uint64_t *)(w + o_ioff), (const double *)(w + o_mean),
-                             (const uint64_t *)(w + o_moff)};
+    const KbSpace core(ws, kb_extent(ks, order.data(), cut, n_max, D));
+    const uint64_t o_mean = ws.take(nsets * D * 8), o_ioff = ws.take(Sc * 8), o_moff = ws.take(Sc * 8), o_boff = ws.take(Sc * 8),
+                   o_empty = ws.take(Sc * 4);
+    PHK_TRY(g->ws.grow(ctx, "phk_combo_grid_fit", ws.bytes, Sc));
+    char *w = g->ws.as<char>();
+    uint32_t *d_act, *d_empty = (uint32_t *)(w + o_empty);
+    KbView v = core.bind(w, &d_act);
+    const double *d_x = g->x.as<double>();
+    const int32_t *d_idx = g->idx.as<int32_t>();
+    const KbFoldRows rows = {d_x, d_idx, (const uint64_t *)(w + o_ioff), (const double *)(w + o_mean), (const uint64_t *)(w + o_moff)};
     const KbNames names = {"cg_seed_dist_kernel", "cg_seed_choose_kernel", "cg_assign_kernel", "cg_update_kernel", "cg_stop_kernel"};
-    uint32_t *d_act = (uint32_t *)(w + o_act), *d_empty = (uint32_t *)(w + o_empty);
     PHK_HIP(hipMemcpyAsync(w + o_mean, set_mean, nsets * D * 8, hipMemcpyHostToDevice, ctx->stream));
 
     KbChunk ch;
@@ -383,14 +323,10 @@ extern "C" int phk_combo_grid_fit(phk_ctx *ctx, phk_combo_grid *g, uint64_t S, c
     for (uint64_t c = 0; c + 1 < cut.size(); ++c) {
         const uint64_t p0 = cut[c], nb = cut[c + 1] - p0;
         v.n = size_of(order[p0]);
-        uint64_t dsum = 0;
         ch.clear();
         for (uint64_t b = 0; b < nb; ++b) {
             const uint64_t s = order[p0 + b];
-            ch.add(ks[s], first_seed[s], dsum, set_tol[set[s]]);
-            const uint64_t nd = (uint64_t)(ch.st[b].k - 1) * ch.st[b].T;
-            if (nd) PHK_HIP(hipMemcpyAsync(w + o_draw + dsum * 8, draws + draw_off[s], nd * 8, hipMemcpyHostToDevice, ctx->stream));
-            dsum += nd;
+            PHK_TRY(ch.add(ctx, v, ks[s], first_seed[s], draws ? draws + draw_off[s] : nullptr, set_tol[set[s]]));
             ioff[b] = g->set_off[set[s]];
             moff[b] = (uint64_t)set[s] * D;
             boff[b] = bank_off[s];
@@ -403,17 +339,15 @@ extern "C" int phk_combo_grid_fit(phk_ctx *ctx, phk_combo_grid *g, uint64_t S, c
         PHK_TRY(kb_solve_chunk(ctx, v, rows, ch, max_iter, d_act, names));
         PHK_LAUNCH(ctx, "cg_centroid_kernel",
                    cg_centroid_kernel<<<dim3(ch.kmax, (unsigned)nb), dim3(256), 0, ctx->stream>>>(
-                       v, g->d_x, g->d_idx, (const uint64_t *)(w + o_ioff), (const uint64_t *)(w + o_boff), g->d_bank, d_empty));
-        PHK_HIP(hipMemcpyAsync(ch.st.data(), v.st, nb * sizeof(KbState), hipMemcpyDeviceToHost, ctx->stream));
+                       v, d_x, d_idx, (const uint64_t *)(w + o_ioff), (const uint64_t *)(w + o_boff), g->bank.as<double>(), d_empty));
         PHK_HIP(hipMemcpyAsync(empty.data(), d_empty, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-        PHK_HIP(hipStreamSynchronize(ctx->stream));   // (the host vectors above are reused by the next chunk)
+        PHK_TRY(ch.download(ctx, v));   // (the host vectors above are reused by the next chunk)
         for (uint64_t b = 0; b < nb; ++b) {
-            const KbState &st = ch.st[b];
             const uint64_t s = order[p0 + b];
-            status[s] = (st.n_empty || empty[b]) ? PHK_COMBO_GRID_EMPTY : 0u;
-            n_iter[s] = (int32_t)st.n_iter;
-            seed_margin[s] = st.seed_margin;
-            min_gap[s] = KbChunk::min_gap(st);
+            status[s] = (ch.met_empty(b) || empty[b]) ? PHK_COMBO_GRID_EMPTY : 0u;
+            n_iter[s] = ch.n_iter(b);
+            seed_margin[s] = ch.seed_margin(b);
+            min_gap[s] = ch.min_gap(b);
         }
     }
     return PHK_OK;
@@ -425,7 +359,7 @@ extern "C" int phk_combo_grid_get_centroids(phk_ctx *ctx, phk_combo_grid *g, uin
     PHK_REQUIRE(row0 + rows <= g->bank_rows, "phk_combo_grid_get_centroids: rows %llu..%llu are not in the bank (%llu rows)",
                 (unsigned long long)row0, (unsigned long long)(row0 + rows), (unsigned long long)g->bank_rows);
     if (rows == 0) return PHK_OK;
-    return phk_copy_to_host(ctx, out, g->d_bank + row0 * g->D, rows * g->D * 8);
+    return phk_copy_to_host(ctx, out, g->bank.as<double>() + row0 * g->D, rows * g->D * 8);
 }
 
 extern "C" int phk_combo_grid_put_centroids(phk_ctx *ctx, phk_combo_grid *g, uint64_t row0, uint64_t rows, const double *in) {
@@ -434,7 +368,7 @@ extern "C" int phk_combo_grid_put_centroids(phk_ctx *ctx, phk_combo_grid *g, uin
     PHK_REQUIRE(row0 + rows <= g->bank_rows, "phk_combo_grid_put_centroids: rows %llu..%llu are not in the bank (%llu rows)",
                 (unsigned long long)row0, (unsigned long long)(row0 + rows), (unsigned long long)g->bank_rows);
     if (rows == 0) return PHK_OK;
-    PHK_TRY(phk_copy_to_device(ctx, g->d_bank + row0 * g->D, in, rows * g->D * 8));
+    PHK_TRY(phk_copy_to_device(ctx, g->bank.as<double>() + row0 * g->D, in, rows * g->D * 8));
     PHK_HIP(hipStreamSynchronize(ctx->stream));   // (the caller's rows may go away)
     return PHK_OK;
 }
@@ -462,7 +396,7 @@ extern "C" int phk_combo_grid_score(phk_ctx *ctx, phk_combo_grid *g, uint32_t Kn
         Ksum += ku[j];
     }
     const uint64_t Cb = 2 * Ksum;
-    PHK_REQUIRE(!Ku || (g->d_bank && g->bank_rows == (uint64_t)F * Cb),
+    PHK_REQUIRE(!Ku || (g->bank.ptr && g->bank_rows == (uint64_t)F * Cb),
                 "phk_combo_grid_score: the bank holds %llu rows, these values need %llu", (unsigned long long)g->bank_rows,
                 (unsigned long long)((uint64_t)F * Cb));
     // query rows per launch of the two pair passes: whole tiles, the pair matrix's block within CG_PASS_BYTES by default
@@ -488,8 +422,8 @@ extern "C" int phk_combo_grid_score(phk_ctx *ctx, phk_combo_grid *g, uint32_t Kn
     const uint64_t o_dist = ps.take(Kn ? R * M * 8 : 0), o_word = ps.take(Kn ? M * 8 : 0), o_kn = ps.take(Kn * 4ull),
                    o_min = ps.take(M * 2 * Ku * 8), o_tile = ps.take(tiles.size() * sizeof(CgTile)), o_knn = ps.take((uint64_t)Kn * M * 8),
                    o_km = ps.take((uint64_t)Ku * M * 8);
-    PHK_TRY(kb_grow(ctx, &g->ps, &g->ps_bytes, ps.bytes, "phk_combo_grid_score", Kn + Ku));
-    char *w = (char *)g->ps;
+    PHK_TRY(g->ps.grow(ctx, "phk_combo_grid_score", ps.bytes, Kn + Ku));
+    char *w = g->ps.as<char>();
     double *d_dist = (double *)(w + o_dist), *d_knn = (double *)(w + o_knn), *d_km = (double *)(w + o_km);
     uint64_t *d_word = (uint64_t *)(w + o_word);
     unsigned long long *d_min = (unsigned long long *)(w + o_min);
@@ -499,10 +433,10 @@ extern "C" int phk_combo_grid_score(phk_ctx *ctx, phk_combo_grid *g, uint32_t Kn
             const uint64_t nq = std::min(R, M - q0);
             PHK_LAUNCH(ctx, "cg_pair_kernel",
                        cg_pair_kernel<<<dim3((unsigned)coltiles, (unsigned)phk_div_up(nq, CL_T)), dim3(CL_THREADS), 0, ctx->stream>>>(
-                           g->d_x, M, D, g->d_fold, q0, d_dist));
+                           g->x.as<double>(), M, D, g->fold.as<uint32_t>(), q0, d_dist));
             PHK_LAUNCH(ctx, "cg_select_kernel",
-                       cg_select_kernel<<<dim3((unsigned)phk_div_up(nq, 4)), dim3(256), 0, ctx->stream>>>(d_dist, nq, M, g->d_cls, (int)kmax,
-                                                                                                         d_word + q0));
+                       cg_select_kernel<<<dim3((unsigned)phk_div_up(nq, 4)), dim3(256), 0, ctx->stream>>>(
+                           d_dist, nq, M, g->cls.as<uint8_t>(), (int)kmax, d_word + q0));
         }
     }
     if (Ku) {
@@ -517,8 +451,9 @@ extern "C" int phk_combo_grid_score(phk_ctx *ctx, phk_combo_grid *g, uint32_t Kn
         for (uint64_t x0 = 0; x0 < qtiles; x0 += step)
             PHK_LAUNCH(ctx, "cg_centroid_pass_kernel",
                        cg_centroid_pass_kernel<<<dim3((unsigned)std::min(step, qtiles - x0), (unsigned)tiles.size(), F), dim3(CL_THREADS), 0,
-                                                 ctx->stream>>>(g->d_x, D, g->d_idx, g->d_held_off, g->d_bank, Cb,
-                                                                (const CgTile *)(w + o_tile), 2 * Ku, x0, d_min));
+                                                 ctx->stream>>>(g->x.as<double>(), D, g->idx.as<int32_t>(), g->held.as<uint64_t>(),
+                                                                g->bank.as<double>(), Cb, (const CgTile *)(w + o_tile), 2 * Ku, x0,
+                                                                d_min));
     }
     PHK_LAUNCH(ctx, "cg_epilogue_kernel",
                cg_epilogue_kernel<<<dim3((unsigned)phk_div_up(M, 256)), dim3(256), 0, ctx->stream>>>(

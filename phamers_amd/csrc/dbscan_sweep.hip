@@ -27,7 +27,7 @@
 
 struct phk_dbscan_rows {
     uint64_t n = 0, D = 0;
-    double *d_x = nullptr;   // the rows, free of NaN
+    PhkDevMem x;   // the rows, free of NaN
 };
 
 // The thresholds, the cell sets ge[0 .. E] and the tile staging every pair pass keeps in LDS.
@@ -229,11 +229,6 @@ __global__ __launch_bounds__(256) void phk_ds_fill_kernel(int32_t *__restrict__ 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static void ds_free(phk_dbscan_rows *h) {
-    if (h->d_x) (void)hipFree(h->d_x);
-    delete h;
-}
-
 extern "C" int phk_dbscan_sweep_create(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, phk_dbscan_rows **out) {
     PHK_ENTER(ctx, "phk_dbscan_sweep_create");
     PHK_REQUIRE(out, "phk_dbscan_sweep_create: NULL pointer");
@@ -245,16 +240,11 @@ extern "C" int phk_dbscan_sweep_create(phk_ctx *ctx, const double *X, uint64_t n
     h->D = D;
     if (n) {
         const uint64_t bytes = n * D * sizeof(double);
-        if (hipMalloc((void **)&h->d_x, bytes) != hipSuccess) {
-            h->d_x = nullptr;
-            ds_free(h);
-            phk_set_error("phk_dbscan_sweep_create: out of device memory (%llu bytes)", (unsigned long long)bytes);
-            return PHK_ERR_NOMEM;
-        }
-        int rc = phk_copy_to_device(ctx, h->d_x, X, bytes);
-        if (rc == PHK_OK) rc = cl_refuse_nan(ctx, "phk_dbscan_sweep_create", h->d_x, n * D);
+        int rc = h->x.alloc("phk_dbscan_sweep_create", "rows", bytes);
+        if (rc == PHK_OK) rc = phk_copy_to_device(ctx, h->x.ptr, X, bytes);
+        if (rc == PHK_OK) rc = cl_refuse_nan(ctx, "phk_dbscan_sweep_create", h->x.as<double>(), n * D);
         if (rc != PHK_OK) {
-            ds_free(h);
+            delete h;
             return rc;
         }
     }
@@ -266,7 +256,7 @@ extern "C" int phk_dbscan_sweep_destroy(phk_ctx *ctx, phk_dbscan_rows *rows) {
     PHK_ENTER(ctx, "phk_dbscan_sweep_destroy");
     if (!rows) return PHK_OK;
     PHK_HIP(hipStreamSynchronize(ctx->stream));
-    ds_free(rows);
+    delete rows;
     return PHK_OK;
 }
 
@@ -282,6 +272,7 @@ extern "C" int phk_dbscan_sweep(phk_ctx *ctx, phk_dbscan_rows *rows, uint32_t C,
         PHK_REQUIRE(min_samples[c] >= 1, "phk_dbscan_sweep: min_samples must be >= 1 (cell %u)", c);
     }
     const uint64_t n = rows->n, D = rows->D;
+    const double *d_x = rows->x.as<double>();
     if (launches) launches[0] = launches[1] = launches[2] = 0;
     if (n == 0) {
         if (n_clusters) std::fill(n_clusters, n_clusters + C, 0ull);
@@ -340,7 +331,7 @@ extern "C" int phk_dbscan_sweep(phk_ctx *ctx, phk_dbscan_rows *rows, uint32_t C,
         for (uint64_t b0 = 0; b0 < T; b0 += step) {
             PHK_LAUNCH(ctx, "phk_ds_count_kernel",
                        phk_ds_count_kernel<<<dim3((unsigned)std::min(step, T - b0), G), dim3(CL_THREADS), 0, ctx->stream>>>(
-                           rows->d_x, n, D, d_th, E, top, b0, G, d_cnt));
+                           d_x, n, D, d_th, E, top, b0, G, d_cnt));
             if (launches) ++launches[0];
         }
     }
@@ -366,7 +357,7 @@ extern "C" int phk_dbscan_sweep(phk_ctx *ctx, phk_dbscan_rows *rows, uint32_t C,
         for (uint64_t i0 = 0; i0 < Tu; i0 += step) {
             PHK_LAUNCH(ctx, "phk_ds_union_kernel",
                        phk_ds_union_kernel<<<dim3((unsigned)Tu, (unsigned)std::min(step, Tu - i0)), dim3(CL_THREADS),
-                                             C * DS_SLOTS * sizeof(int), ctx->stream>>>(rows->d_x, D, d_th, d_ge, E, top, C, d_u, d_cm, nu,
+                                             C * DS_SLOTS * sizeof(int), ctx->stream>>>(d_x, D, d_th, d_ge, E, top, C, d_u, d_cm, nu,
                                                                                         i0, d_parent));
             if (launches) ++launches[1];
         }
@@ -384,7 +375,7 @@ extern "C" int phk_dbscan_sweep(phk_ctx *ctx, phk_dbscan_rows *rows, uint32_t C,
         for (uint64_t b0 = 0; b0 < Tq; b0 += step) {
             PHK_LAUNCH(ctx, "phk_ds_border_kernel",
                        phk_ds_border_kernel<<<dim3((unsigned)std::min(step, Tq - b0), G), dim3(CL_THREADS), CL_T * C * sizeof(int),
-                                              ctx->stream>>>(rows->d_x, D, d_th, d_ge, E, top, C, d_b, nb, d_u, nu, d_cm, d_root, b0, G,
+                                              ctx->stream>>>(d_x, D, d_th, d_ge, E, top, C, d_b, nb, d_u, nu, d_cm, d_root, b0, G,
                                                              d_best));
             if (launches) ++launches[2];
         }

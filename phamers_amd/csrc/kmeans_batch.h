@@ -9,7 +9,13 @@
 //             single-problem path's bit for bit), each problem with its own centres, labels, stopping flags and sweep count;
 //             the host reads one word per sweep for the chunk, a finished problem's workgroups return at once.
 // Where a problem's rows come from is a compile-time parameter of the kernels (KbCentredRows, KbAppendedRows, KbFoldRows below); each
-// client instantiates them for its own source.  Everything is float64 and order-deterministic (the only atomics are integer
+// client instantiates them for its own source.
+// The host half, below the kernels, is shared as well: the trial and draw counts (kb_trials, kb_draws), the refusals of a call
+// and of a problem (kb_check_call, kb_check_problem), the largest chunk of a call (kb_extent), the one statement of the chunk's
+// workspace (KbSpace: the core's ten regions out of the client's PhkLayout, bound to a KbView after the allocation), the
+// chunk's way in and out (KbChunk: add a problem with its draws, upload, download, the per-problem results) and
+// kb_solve_chunk.  A client is its own checks, its own regions and a loop over chunks around those calls.
+// Everything is float64 and order-deterministic (the only atomics are integer
 // counts and minima); every sum's order is fixed by the rows, the labels and the problem alone, so a problem's result does
 // not depend on its place in the chunk, on the chunking or on the run.
 #pragma once
@@ -368,39 +374,107 @@ static __global__ __launch_bounds__(256) void kb_stop_kernel(KbView v, uint32_t 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// grow a handle's workspace to `need` bytes (the stream is drained first: the old block may be in use)
-static inline int kb_grow(phk_ctx *ctx, void **ws, uint64_t *ws_bytes, uint64_t need, const char *fname, uint64_t problems) {
-    if (*ws_bytes >= need) return PHK_OK;
-    PHK_HIP(hipStreamSynchronize(ctx->stream));
-    if (*ws) (void)hipFree(*ws);
-    *ws = nullptr;
-    *ws_bytes = 0;
-    if (hipMalloc(ws, need) != hipSuccess) {
-        *ws = nullptr;
-        phk_set_error("%s: out of device memory (%llu bytes for %llu problems at once)", fname, (unsigned long long)need,
-                      (unsigned long long)problems);
-        return PHK_ERR_NOMEM;
-    }
-    *ws_bytes = need;
+// scikit-learn's seeding trials per centre, and the uniforms a problem's seeding takes (none for its first centre)
+static inline uint32_t kb_trials(uint32_t k) { return 2 + (uint32_t)std::log((double)k); }
+static inline uint64_t kb_draws(uint32_t k) { return (uint64_t)(k - 1) * kb_trials(k); }
+
+// what every client refuses: of a call, and of its problem s (k centres among n rows); fname = the client's entry point
+static inline int kb_check_call(const char *fname, int max_iter, uint32_t chunk) {
+    PHK_REQUIRE(max_iter >= 1 && chunk <= 65535, "%s: bad max_iter / chunk", fname);
+    return PHK_OK;
+}
+static inline int kb_check_problem(const char *fname, uint64_t s, uint32_t k, uint64_t n, uint32_t first_seed, const double *draws) {
+    PHK_REQUIRE(k >= 1 && k <= n, "%s: need 1 <= k <= n (problem %llu: k=%u, n=%llu)", fname, (unsigned long long)s, k,
+                (unsigned long long)n);
+    PHK_REQUIRE(first_seed < n, "%s: first seed %u of problem %llu is not a row", fname, first_seed, (unsigned long long)s);
+    PHK_REQUIRE(kb_trials(k) <= KB_MAX_TRIALS, "%s: k = %u needs %u seeding trials per centre, at most %d are built", fname, k,
+                kb_trials(k), KB_MAX_TRIALS);
+    PHK_REQUIRE(draws || k == 1, "%s: NULL draws", fname);
     return PHK_OK;
 }
 
-// the host's side of a chunk: the problems' states and first centres, filled by add(), sent by upload()
+// What the workspace has to hold: the most of each over the call's chunks.
+struct KbExtent {
+    uint64_t problems, rows, D;   // problems of a chunk; rows of a problem; columns
+    uint64_t ksum;                // centres of a chunk's problems
+    uint32_t trials;              // trial stride of td
+    uint64_t draws;               // uniforms of a chunk
+};
+
+// The extent of the chunks [cut[c], cut[c + 1]) of the problems ks[order[p]] (order = nullptr: as given), n rows each at most.
+static inline KbExtent kb_extent(const uint32_t *ks, const uint64_t *order, const std::vector<uint64_t> &cut, uint64_t n, uint64_t D) {
+    KbExtent e = {0, n, D, 0, KB_MAX_TRIALS, 0};
+    for (uint64_t c = 0; c + 1 < cut.size(); ++c) {
+        uint64_t ksum = 0, dsum = 0;
+        for (uint64_t p = cut[c]; p < cut[c + 1]; ++p) {
+            const uint32_t k = ks[order ? order[p] : p];
+            ksum += k;
+            dsum += kb_draws(k);
+        }
+        e.problems = std::max(e.problems, cut[c + 1] - cut[c]);
+        e.ksum = std::max(e.ksum, ksum);
+        e.draws = std::max(e.draws, dsum);
+    }
+    return e;
+}
+
+// The core's regions of a client's workspace: taken from the client's layout (its own regions go before or behind, in the
+// same allocation), bound to the allocation's address afterwards.
+struct KbSpace {
+    KbExtent e;
+    uint64_t o_cen, o_lab, o_clo, o_td, o_cand, o_seed, o_size, o_st, o_draw, o_act;
+    KbSpace(PhkLayout &ws, const KbExtent &x) : e(x) {
+        o_cen = ws.take(2 * e.ksum * e.D * 8);
+        o_lab = ws.take(e.problems * e.rows * 4);
+        o_clo = ws.take(e.problems * e.rows * 8);
+        o_td = ws.take(e.problems * e.trials * e.rows * 8);
+        o_cand = ws.take(e.problems * KB_MAX_TRIALS * 4);
+        o_seed = ws.take(e.ksum * 4);
+        o_size = ws.take(e.ksum * 4);
+        o_st = ws.take(e.problems * sizeof(KbState));
+        o_draw = ws.take(e.draws * 8 + 8);
+        o_act = ws.take(256);
+    }
+    // the view of chunks of e.rows rows (a chunk of fewer sets v.n) and the device word of kb_solve_chunk's read-back
+    KbView bind(void *base, uint32_t **d_active) const {
+        char *w = (char *)base;
+        KbView v;
+        v.cen = (double *)(w + o_cen);
+        v.labels = (uint32_t *)(w + o_lab);
+        v.closest = (double *)(w + o_clo);
+        v.td = (double *)(w + o_td);
+        v.cand = (uint32_t *)(w + o_cand);
+        v.seeds = (uint32_t *)(w + o_seed);
+        v.sizes = (uint32_t *)(w + o_size);
+        v.st = (KbState *)(w + o_st);
+        v.draws = (const double *)(w + o_draw);
+        v.n = e.rows;
+        v.D = e.D;
+        v.trials = e.trials;
+        *d_active = (uint32_t *)(w + o_act);
+        return v;
+    }
+};
+
+// the host's side of a chunk: the problems' states and first centres, filled by add(), sent by upload(), back by download()
 struct KbChunk {
     std::vector<KbState> st;
     std::vector<uint32_t> cand;   // [problems][KB_MAX_TRIALS], the first centre's row in front
     uint32_t ksum = 0, kmax = 0;  // centres of the chunk's problems, and the most of one problem
+    uint64_t dsum = 0;            // draws of the chunk's problems so far
 
     void clear() {
         st.clear();
         cand.clear();
         ksum = kmax = 0;
+        dsum = 0;
     }
+    // a problem whose draws are in the workspace already, at doff (the placement: one set for every problem)
     void add(uint32_t k, uint32_t first_seed, uint64_t doff, double tol) {
         KbState s;
         memset(&s, 0, sizeof(s));
         s.k = k;
-        s.T = 2 + (uint32_t)std::log((double)k);
+        s.T = kb_trials(k);
         s.koff = ksum;
         s.doff = doff;
         s.active = 1;
@@ -414,16 +488,33 @@ struct KbChunk {
         ksum += k;
         kmax = std::max(kmax, k);
     }
+    // a problem and its own kb_draws(k) uniforms, which go up behind those of the chunk's earlier problems
+    int add(phk_ctx *ctx, const KbView &v, uint32_t k, uint32_t first_seed, const double *draws, double tol) {
+        add(k, first_seed, dsum, tol);
+        const uint64_t nd = kb_draws(k);
+        if (nd) PHK_HIP(hipMemcpyAsync((double *)v.draws + dsum, draws, nd * 8, hipMemcpyHostToDevice, ctx->stream));
+        dsum += nd;
+        return PHK_OK;
+    }
     int upload(phk_ctx *ctx, const KbView &v) const {
         PHK_HIP(hipMemcpyAsync(v.st, st.data(), st.size() * sizeof(KbState), hipMemcpyHostToDevice, ctx->stream));
         PHK_HIP(hipMemcpyAsync(v.cand, cand.data(), cand.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         PHK_HIP(hipMemsetAsync(v.labels, 0xFF, st.size() * v.n * 4, ctx->stream));
         return PHK_OK;
     }
-    static double min_gap(const KbState &s) {
+    // after kb_solve_chunk and whatever the client queued behind it: the states back, the stream drained; then per problem
+    int download(phk_ctx *ctx, const KbView &v) {
+        PHK_HIP(hipMemcpyAsync(st.data(), v.st, st.size() * sizeof(KbState), hipMemcpyDeviceToHost, ctx->stream));
+        PHK_HIP(hipStreamSynchronize(ctx->stream));
+        return PHK_OK;
+    }
+    int32_t n_iter(uint64_t b) const { return (int32_t)st[b].n_iter; }
+    double seed_margin(uint64_t b) const { return st[b].seed_margin; }
+    bool met_empty(uint64_t b) const { return st[b].n_empty != 0; }
+    double min_gap(uint64_t b) const {
         double gap;
-        static_assert(sizeof(gap) == sizeof(s.gapbits), "");
-        memcpy(&gap, &s.gapbits, 8);
+        static_assert(sizeof(gap) == sizeof(st[b].gapbits), "");
+        memcpy(&gap, &st[b].gapbits, 8);
         return gap;
     }
 };

@@ -236,6 +236,49 @@ struct phk_ctx {
 
 int phk_ws(phk_ctx *ctx, int slot, uint64_t bytes, void **out);
 
+// One device allocation and its owner: freed when the owner goes (a handle's `delete`, a call's way out), so no create or
+// run function frees by hand.  Move-only.  The context's own scratch is phk_ws above; this is for what a handle keeps and
+// for the buffers of one call.
+struct PhkDevMem {
+    void *ptr = nullptr;
+    uint64_t bytes = 0;
+    PhkDevMem() = default;
+    PhkDevMem(const PhkDevMem &) = delete;
+    PhkDevMem &operator=(const PhkDevMem &) = delete;
+    PhkDevMem(PhkDevMem &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    ~PhkDevMem() { release(); }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+    template <class T> T *as() const { return (T *)ptr; }
+    // `bytes` of `what` for `fname`; what the owner held is freed first (the caller drains the stream if it may be in use).
+    // A failure leaves the owner empty and no HIP error pending.
+    int alloc(const char *fname, const char *what, uint64_t b) {
+        release();
+        if (hipMalloc(&ptr, b ? b : 1) != hipSuccess) {
+            ptr = nullptr;
+            (void)hipGetLastError();
+            phk_set_error("%s: out of device memory (%llu bytes of %s)", fname, (unsigned long long)b, what);
+            return PHK_ERR_NOMEM;
+        }
+        bytes = b;
+        return PHK_OK;
+    }
+    // a handle's workspace, grown to `need` bytes (the stream is drained first: the old block may be in use)
+    int grow(phk_ctx *ctx, const char *fname, uint64_t need, uint64_t problems) {
+        if (bytes >= need) return PHK_OK;
+        PHK_HIP(hipStreamSynchronize(ctx->stream));
+        if (alloc(fname, "workspace", need) != PHK_OK) {
+            phk_set_error("%s: out of device memory (%llu bytes for %llu problems at once)", fname, (unsigned long long)need,
+                          (unsigned long long)problems);
+            return PHK_ERR_NOMEM;
+        }
+        return PHK_OK;
+    }
+};
+
 // Large transfers between caller arrays and the device go through the context's two pinned staging buffers (64 MB each),
 // host threads copying on one side while the bus works on the other: an array handed to hipMemcpy as it is has its pages
 // pinned inside the runtime and costs 0.05 - 0.1 s per GB to free afterwards (tools/diag/fasta_free_time.py).  Below 128 MB
@@ -318,6 +361,13 @@ static inline void phk_parallel_for(uint64_t n, F fn) {
             for (uint64_t i = n * t / nt; i < n * (t + 1) / nt; ++i) fn(i);
         });
     for (auto &th : pool) th.join();
+}
+
+// every value finite: what the resident handles ask of their rows before anything goes up (the caller's PHK_ERR_NAN)
+static inline bool phk_rows_finite(const double *x, uint64_t count) {
+    for (uint64_t i = 0; i < count; ++i)
+        if (!(x[i] - x[i] == 0.0)) return false;
+    return true;
 }
 
 // x / T for the elements of ONE count row: T and y = 1.0 / T (one IEEE division) are shared by the row, each element costs

@@ -18,10 +18,9 @@
 
 struct phk_placement {
     uint64_t n = 0, D = 0;
-    double *d_x = nullptr;
+    PhkDevMem x;                 // the reference rows
     std::vector<double> S, SS;   // column sums of x and x^2 in row order
-    void *ws = nullptr;
-    uint64_t ws_bytes = 0;
+    PhkDevMem ws;                // the chunks' workspace
 };
 
 __device__ __forceinline__ const double *pl_row(const double *__restrict__ X, const double *__restrict__ z, uint64_t n, uint64_t D,
@@ -135,11 +134,10 @@ extern "C" int phk_placement_create(phk_ctx *ctx, const double *X, uint64_t n, u
     PHK_REQUIRE(X && out, "phk_placement_create: NULL pointer");
     PHK_REQUIRE(n >= 1 && D >= 1 && n < (1ull << 31) - 1, "phk_placement_create: bad shape (%llu x %llu)", (unsigned long long)n,
                 (unsigned long long)D);
-    for (uint64_t i = 0; i < n * D; ++i)
-        if (!(X[i] - X[i] == 0.0)) {
-            phk_set_error("phk_placement_create: the reference rows contain NaN or infinity");
-            return PHK_ERR_NAN;
-        }
+    if (!phk_rows_finite(X, n * D)) {
+        phk_set_error("phk_placement_create: the reference rows contain NaN or infinity");
+        return PHK_ERR_NAN;
+    }
     phk_placement *pl = new phk_placement;
     pl->n = n;
     pl->D = D;
@@ -151,15 +149,10 @@ extern "C" int phk_placement_create(phk_ctx *ctx, const double *X, uint64_t n, u
             pl->S[d] += x;             // row order: NumPy's add.reduce over axis 0 of a C-contiguous matrix
             pl->SS[d] += x * x;
         }
-    if (hipMalloc((void **)&pl->d_x, n * D * sizeof(double)) != hipSuccess) {
-        delete pl;
-        phk_set_error("phk_placement_create: out of device memory (%llu bytes)", (unsigned long long)(n * D * sizeof(double)));
-        return PHK_ERR_NOMEM;
-    }
-    int rc = phk_copy_to_device(ctx, pl->d_x, X, n * D * sizeof(double));
+    int rc = pl->x.alloc("phk_placement_create", "reference rows", n * D * sizeof(double));
+    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, pl->x.ptr, X, n * D * sizeof(double));
     if (rc == PHK_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = PHK_ERR_HIP;
     if (rc != PHK_OK) {
-        (void)hipFree(pl->d_x);
         delete pl;
         return rc;
     }
@@ -171,8 +164,6 @@ extern "C" int phk_placement_destroy(phk_ctx *ctx, phk_placement *pl) {
     PHK_ENTER(ctx, "phk_placement_destroy");
     if (!pl) return PHK_OK;
     PHK_HIP(hipStreamSynchronize(ctx->stream));
-    if (pl->d_x) (void)hipFree(pl->d_x);
-    if (pl->ws) (void)hipFree(pl->ws);
     delete pl;
     return PHK_OK;
 }
@@ -185,45 +176,29 @@ extern "C" int phk_placement_run(phk_ctx *ctx, phk_placement *pl, const double *
     PHK_REQUIRE(pl, "phk_placement_run: NULL placement");
     const uint64_t n = pl->n, D = pl->D, n1 = n + 1;
     PHK_REQUIRE(k >= 1 && k <= n1, "phk_placement_run: need 1 <= k <= n + 1 (k=%u, n=%llu)", k, (unsigned long long)n);
-    const uint32_t T = 2 + (uint32_t)std::log((double)k);
-    PHK_REQUIRE(T <= KB_MAX_TRIALS, "phk_placement_run: k = %u needs %u seeding trials per centre, at most %d are built", k, T,
-                KB_MAX_TRIALS);
-    PHK_REQUIRE(max_iter >= 1 && tol_rel >= 0.0 && first_seed < n1 && chunk <= 65535, "phk_placement_run: bad max_iter / tol / first seed / chunk");
+    PHK_TRY(kb_check_call("phk_placement_run", max_iter, chunk));
+    PHK_REQUIRE(tol_rel >= 0.0, "phk_placement_run: bad tol");
+    PHK_TRY(kb_check_problem("phk_placement_run", 0, k, n1, first_seed, draws));
     if (B == 0) return PHK_OK;
-    PHK_REQUIRE(Z && labels && sil && n_members && status && n_iter && min_gap && seed_margin && (draws || k == 1),
-                "phk_placement_run: NULL pointer");
-    for (uint64_t i = 0; i < B * D; ++i)
-        if (!(Z[i] - Z[i] == 0.0)) {
-            phk_set_error("phk_placement_run: the contig rows contain NaN or infinity");
-            return PHK_ERR_NAN;
-        }
+    PHK_REQUIRE(Z && labels && sil && n_members && status && n_iter && min_gap && seed_margin, "phk_placement_run: NULL pointer");
+    if (!phk_rows_finite(Z, B * D)) {
+        phk_set_error("phk_placement_run: the contig rows contain NaN or infinity");
+        return PHK_ERR_NAN;
+    }
     const uint64_t Bc = std::min<uint64_t>(B, chunk ? chunk : PL_DEFAULT_CHUNK);
-    // the chunk's workspace
+    // the chunk's workspace: the core's regions (every problem k centres, its own trial stride, one set of draws for all:
+    // doff = 0), then the placement's
     PhkLayout ws;
-    const uint64_t o_z = ws.take(Bc * D * 8), o_mean = ws.take(Bc * D * 8), o_cen = ws.take(Bc * 2 * k * D * 8),
-                   o_lab = ws.take(Bc * n1 * 4), o_clo = ws.take(Bc * n1 * 8), o_td = ws.take(Bc * T * n1 * 8),
-                   o_cand = ws.take(Bc * KB_MAX_TRIALS * 4), o_seed = ws.take(Bc * k * 4), o_size = ws.take(Bc * k * 4),
-                   o_st = ws.take(Bc * sizeof(KbState)), o_own = ws.take(2 * Bc * 4), o_mem = ws.take(Bc * n1 * 4),
+    const KbSpace core(ws, {Bc, n1, D, Bc * k, kb_trials(k), kb_draws(k)});
+    const uint64_t o_z = ws.take(Bc * D * 8), o_mean = ws.take(Bc * D * 8), o_own = ws.take(2 * Bc * 4), o_mem = ws.take(Bc * n1 * 4),
                    o_sd = ws.take(Bc * PL_SIL_GROUPS * n1 * 8), o_ss = ws.take(Bc * PL_SIL_GROUPS * (uint64_t)k * 8),
-                   o_sc = ws.take(Bc * PL_SIL_GROUPS * (uint64_t)k * 4), o_sil = ws.take(Bc * n1 * 8),
-                   o_draw = ws.take((uint64_t)k * T * 8), o_act = ws.take(256);
-    PHK_TRY(kb_grow(ctx, &pl->ws, &pl->ws_bytes, ws.bytes, "phk_placement_run", Bc));
-    char *w = (char *)pl->ws;
-    KbView kv;
-    kv.cen = (double *)(w + o_cen);       // problem b's centres, seeds and sizes at koff = b * k
-    kv.labels = (uint32_t *)(w + o_lab);
-    kv.closest = (double *)(w + o_clo);
-    kv.td = (double *)(w + o_td);
-    kv.cand = (uint32_t *)(w + o_cand);
-    kv.seeds = (uint32_t *)(w + o_seed);
-    kv.sizes = (uint32_t *)(w + o_size);
-    kv.st = (KbState *)(w + o_st);
-    kv.draws = (const double *)(w + o_draw);   // the same draws for every problem: doff = 0
-    kv.n = n1;
-    kv.D = D;
-    kv.trials = T;
+                   o_sc = ws.take(Bc * PL_SIL_GROUPS * (uint64_t)k * 4), o_sil = ws.take(Bc * n1 * 8);
+    PHK_TRY(pl->ws.grow(ctx, "phk_placement_run", ws.bytes, Bc));
+    char *w = pl->ws.as<char>();
+    uint32_t *d_act;
+    const KbView kv = core.bind(w, &d_act);
     PlView v;
-    v.X = pl->d_x;
+    v.X = pl->x.as<double>();
     v.Z = (const double *)(w + o_z);
     v.labels = kv.labels;
     v.dup = (uint32_t *)(w + o_own);
@@ -236,8 +211,7 @@ extern "C" int phk_placement_run(phk_ctx *ctx, phk_placement *pl, const double *
     v.n = n; v.n1 = n1; v.D = D; v.k = k;
     const KbAppendedRows rows = {v.X, v.Z, (const double *)(w + o_mean), n};
     const KbNames names = {"pl_seed_dist_kernel", "pl_seed_choose_kernel", "pl_assign_kernel", "pl_update_kernel", "pl_stop_kernel"};
-    uint32_t *d_act = (uint32_t *)(w + o_act);
-    if (k > 1) PHK_HIP(hipMemcpyAsync(w + o_draw, draws, (uint64_t)(k - 1) * T * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (k > 1) PHK_HIP(hipMemcpyAsync((double *)kv.draws, draws, kb_draws(k) * 8, hipMemcpyHostToDevice, ctx->stream));
 
     std::vector<double> mean(Bc * D);
     std::vector<uint32_t> own(2 * Bc);
@@ -272,16 +246,14 @@ extern "C" int phk_placement_run(phk_ctx *ctx, phk_placement *pl, const double *
         PHK_HIP(hipMemcpyAsync(labels + b0 * n1, v.labels, nb * n1 * 4, hipMemcpyDeviceToHost, ctx->stream));
         PHK_HIP(hipMemcpyAsync(sil + b0 * n1, v.sil, nb * n1 * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (seeds) PHK_HIP(hipMemcpyAsync(seeds + b0 * k, kv.seeds, nb * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-        PHK_HIP(hipMemcpyAsync(ch.st.data(), kv.st, nb * sizeof(KbState), hipMemcpyDeviceToHost, ctx->stream));
         PHK_HIP(hipMemcpyAsync(own.data(), v.dup, 2 * Bc * 4, hipMemcpyDeviceToHost, ctx->stream));
-        PHK_HIP(hipStreamSynchronize(ctx->stream));
+        PHK_TRY(ch.download(ctx, kv));
         for (uint64_t b = 0; b < nb; ++b) {
-            const KbState &s = ch.st[b];
-            status[b0 + b] = (own[b] ? PHK_PLACEMENT_DUPLICATE : 0u) | (s.n_empty ? PHK_PLACEMENT_EMPTY : 0u);
-            n_iter[b0 + b] = (int32_t)s.n_iter;
+            status[b0 + b] = (own[b] ? PHK_PLACEMENT_DUPLICATE : 0u) | (ch.met_empty(b) ? PHK_PLACEMENT_EMPTY : 0u);
+            n_iter[b0 + b] = ch.n_iter(b);
             n_members[b0 + b] = own[Bc + b];
-            seed_margin[b0 + b] = s.seed_margin;
-            min_gap[b0 + b] = KbChunk::min_gap(s);
+            seed_margin[b0 + b] = ch.seed_margin(b);
+            min_gap[b0 + b] = ch.min_gap(b);
         }
     }
     return PHK_OK;

@@ -163,15 +163,6 @@ __global__ __launch_bounds__(256) void phk_svm_gather_kernel(const double *__res
 // ---- host side ---------------------------------------------------------------------------------------------------------
 namespace {
 
-// device buffers of one fit, freed on every way out
-struct SvmFitBufs {
-    void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~SvmFitBufs() {
-        for (void *q : p)
-            if (q) (void)hipFree(q);
-    }
-};
-
 bool svm_gamma_ok(double g) { return g > 0.0 && g < __builtin_inf(); }
 
 }   // namespace
@@ -214,16 +205,16 @@ static int svm_check(uint64_t n0, uint64_t n1, double nu, double gamma, double t
 // alpha_i y_i / r for every grouped row (0 where alpha_i = 0), rho / r, the iteration count.
 static int svm_fit_grouped(phk_ctx *ctx, const double *d_Xg, uint64_t n0, uint64_t n, uint64_t D, double nu, double gamma,
                            double tol, int32_t max_iter, std::vector<double> &coef, double *rho, int32_t *n_iter) {
-    SvmFitBufs b;
-    PHK_HIP(hipMalloc(&b.p[0], n * sizeof(double)));                // |x|^2
-    PHK_HIP(hipMalloc(&b.p[1], n * n * sizeof(float)));             // Q
-    PHK_HIP(hipMalloc(&b.p[2], 2 * n * sizeof(double)));            // alpha, G
-    PHK_HIP(hipMalloc(&b.p[3], n));                                 // y
-    PHK_HIP(hipMalloc(&b.p[4], sizeof(SvmCtl)));
-    double *xn = (double *)b.p[0], *alpha = (double *)b.p[2], *G = alpha + n;
-    float *Qf = (float *)b.p[1];
-    int8_t *dy = (int8_t *)b.p[3];
-    SvmCtl *dctl = (SvmCtl *)b.p[4];
+    PhkDevMem b[5];   // the fit's buffers, freed on every way out
+    PHK_TRY(b[0].alloc("phk_nusvc_fit", "row norms", n * sizeof(double)));
+    PHK_TRY(b[1].alloc("phk_nusvc_fit", "Q", n * n * sizeof(float)));
+    PHK_TRY(b[2].alloc("phk_nusvc_fit", "alpha and G", 2 * n * sizeof(double)));
+    PHK_TRY(b[3].alloc("phk_nusvc_fit", "y", n));
+    PHK_TRY(b[4].alloc("phk_nusvc_fit", "control words", sizeof(SvmCtl)));
+    double *xn = b[0].as<double>(), *alpha = b[2].as<double>(), *G = alpha + n;
+    float *Qf = b[1].as<float>();
+    int8_t *dy = b[3].as<int8_t>();
+    SvmCtl *dctl = b[4].as<SvmCtl>();
 
     // solve_nu_svc: y, and alpha filled class by class up to nu l / 2 (nu_l = sum of nu * C_i, C_i = 1)
     std::vector<int8_t> y(n);

@@ -101,19 +101,6 @@ __global__ __launch_bounds__(SVM_T) void phk_svm_sweep_solve_kernel(const SvsPro
 // ---- host side ---------------------------------------------------------------------------------------------------------
 namespace {
 
-// device buffers of one call, freed on every way out
-struct SvsBufs {
-    std::vector<void *> p;
-    int alloc(uint64_t bytes, void **out) {
-        PHK_HIP(hipMalloc(out, bytes ? bytes : 1));
-        p.push_back(*out);
-        return PHK_OK;
-    }
-    ~SvsBufs() {
-        for (void *q : p) (void)hipFree(q);
-    }
-};
-
 // solve_nu_svc's start for the rows with y != 0: alpha filled class by class, in row order, up to nu l / 2
 void svs_alpha_start(const int8_t *y, uint64_t n, uint64_t m, double nu, double *a0) {
 #pragma clang fp contract(off)
@@ -235,27 +222,29 @@ extern "C" int phk_nusvc_sweep(phk_ctx *ctx, const double *X, uint64_t n, uint64
     gp = gp < 1 ? 1 : (gp > Gm ? Gm : gp);
     const uint64_t NP = per_gamma * gp;   // problems of a pass, at most
 
-    SvsBufs b;
-    void *d_x, *d_idx, *d_flags, *v_xg, *v_xn, *v_y, *v_Q, *v_state, *v_ctl, *v_probs, *v_open, *v_held, *v_sv, *v_dec;
+    const char *fn = "phk_nusvc_sweep";
+    PhkDevMem m_xg, m_xn, m_y, m_Q, m_state, m_ctl, m_probs, m_open, m_held, m_sv, m_dec;   // the call's buffers, freed on every way out
+    void *d_x, *d_idx, *d_flags;
     PHK_TRY(phk_ws(ctx, WS_WIDE, n * D * sizeof(double), &d_x));
     PHK_TRY(phk_ws(ctx, WS_OFFSETS, n * sizeof(uint32_t), &d_idx));
     PHK_TRY(phk_ws(ctx, WS_FLAGS, 64, &d_flags));
-    PHK_TRY(b.alloc(n * D * sizeof(double), &v_xg));
-    PHK_TRY(b.alloc(n * sizeof(double), &v_xn));
-    PHK_TRY(b.alloc((uint64_t)S * n, &v_y));
-    PHK_TRY(b.alloc((uint64_t)gp * n * n * sizeof(float), &v_Q));
-    PHK_TRY(b.alloc(NP * 2 * n * sizeof(double), &v_state));
-    PHK_TRY(b.alloc(NP * sizeof(SvmCtl), &v_ctl));
-    PHK_TRY(b.alloc(NP * sizeof(SvsProb), &v_probs));
-    PHK_TRY(b.alloc(NP * sizeof(uint32_t), &v_open));
-    PHK_TRY(b.alloc(F ? n * D * sizeof(double) : 0, &v_held));
-    PHK_TRY(b.alloc(F ? n * D * sizeof(double) + 2 * n * sizeof(double) : 0, &v_sv));
-    PHK_TRY(b.alloc(F ? (uint64_t)Gm * V * n * sizeof(double) : 0, &v_dec));
-    double *d_xg = (double *)v_xg, *d_xn = (double *)v_xn, *d_state = (double *)v_state;
-    double *d_sv = (double *)v_sv, *d_svn = d_sv + n * D, *d_svcoef = d_svn + n, *d_dec = (double *)v_dec;
-    int8_t *d_y = (int8_t *)v_y;
-    float *d_Q = (float *)v_Q;
-    SvmCtl *d_ctl = (SvmCtl *)v_ctl;
+    PHK_TRY(m_xg.alloc(fn, "grouped rows", n * D * sizeof(double)));
+    PHK_TRY(m_xn.alloc(fn, "row norms", n * sizeof(double)));
+    PHK_TRY(m_y.alloc(fn, "y", (uint64_t)S * n));
+    PHK_TRY(m_Q.alloc(fn, "Q", (uint64_t)gp * n * n * sizeof(float)));
+    PHK_TRY(m_state.alloc(fn, "solver states", NP * 2 * n * sizeof(double)));
+    PHK_TRY(m_ctl.alloc(fn, "control words", NP * sizeof(SvmCtl)));
+    PHK_TRY(m_probs.alloc(fn, "problems", NP * sizeof(SvsProb)));
+    PHK_TRY(m_open.alloc(fn, "open problems", NP * sizeof(uint32_t)));
+    PHK_TRY(m_held.alloc(fn, "held-out rows", F ? n * D * sizeof(double) : 0));
+    PHK_TRY(m_sv.alloc(fn, "support vectors", F ? n * D * sizeof(double) + 2 * n * sizeof(double) : 0));
+    PHK_TRY(m_dec.alloc(fn, "decision values", F ? (uint64_t)Gm * V * n * sizeof(double) : 0));
+    void *v_probs = m_probs.ptr, *v_open = m_open.ptr, *v_held = m_held.ptr;
+    double *d_xg = m_xg.as<double>(), *d_xn = m_xn.as<double>(), *d_state = m_state.as<double>();
+    double *d_sv = m_sv.as<double>(), *d_svn = d_sv + n * D, *d_svcoef = d_svn + n, *d_dec = m_dec.as<double>();
+    int8_t *d_y = m_y.as<int8_t>();
+    float *d_Q = m_Q.as<float>();
+    SvmCtl *d_ctl = m_ctl.as<SvmCtl>();
 
     PHK_TRY(phk_copy_to_device(ctx, d_x, X, n * D * sizeof(double)));
     PHK_HIP(hipMemcpyAsync(d_idx, perm.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));

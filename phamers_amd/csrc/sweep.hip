@@ -23,12 +23,10 @@
 
 struct phk_sweep {
     uint64_t n = 0, D = 0;
-    double *d_x = nullptr;    // raw rows
-    double *d_xc = nullptr;   // centred rows
+    PhkDevMem x, xc;          // raw rows, centred rows
     double var_mean = 0.0;    // np.mean(np.var(centred rows, axis=0))
-    void *ws = nullptr;
-    uint64_t ws_bytes = 0;
-    double *d_pair = nullptr; // d[n][n], kept between calls
+    PhkDevMem ws;             // the chunks' workspace
+    PhkDevMem pair;           // d[n][n], kept between calls
 };
 
 // ---- silhouettes ----------------------------------------------------------------------------------------------------
@@ -109,24 +107,15 @@ static double sw_np_sum(const double *a, uint64_t n) {
     return s;
 }
 
-static void sw_free(phk_sweep *sw) {
-    if (sw->d_x) (void)hipFree(sw->d_x);
-    if (sw->d_xc) (void)hipFree(sw->d_xc);
-    if (sw->ws) (void)hipFree(sw->ws);
-    if (sw->d_pair) (void)hipFree(sw->d_pair);
-    delete sw;
-}
-
 extern "C" int phk_sweep_create(phk_ctx *ctx, const double *X, uint64_t n, uint64_t D, phk_sweep **out) {
     PHK_ENTER(ctx, "phk_sweep_create");
     PHK_REQUIRE(X && out, "phk_sweep_create: NULL pointer");
     PHK_REQUIRE(n >= 1 && D >= 1 && n < (1ull << 31) - 1, "phk_sweep_create: bad shape (%llu x %llu)", (unsigned long long)n,
                 (unsigned long long)D);
-    for (uint64_t i = 0; i < n * D; ++i)
-        if (!(X[i] - X[i] == 0.0)) {
-            phk_set_error("phk_sweep_create: the rows contain NaN or infinity");
-            return PHK_ERR_NAN;
-        }
+    if (!phk_rows_finite(X, n * D)) {
+        phk_set_error("phk_sweep_create: the rows contain NaN or infinity");
+        return PHK_ERR_NAN;
+    }
     // NumPy's X - X.mean(axis=0) and np.mean(np.var(that, axis=0)): column sums in row order, one division each -- except
     // that a matrix of ONE column is a contiguous vector to NumPy's reduction, which it sums pairwise
     std::vector<double> mean(D, 0.0), xc(n * D), m2(D, 0.0), var(D, 0.0), sq;
@@ -155,16 +144,13 @@ extern "C" int phk_sweep_create(phk_ctx *ctx, const double *X, uint64_t n, uint6
     sw->D = D;
     sw->var_mean = sw_np_sum(var.data(), D) / (double)D;
     const uint64_t bytes = n * D * sizeof(double);
-    if (hipMalloc((void **)&sw->d_x, bytes) != hipSuccess || hipMalloc((void **)&sw->d_xc, bytes) != hipSuccess) {
-        sw_free(sw);
-        phk_set_error("phk_sweep_create: out of device memory (2 x %llu bytes)", (unsigned long long)bytes);
-        return PHK_ERR_NOMEM;
-    }
-    int rc = phk_copy_to_device(ctx, sw->d_x, X, bytes);
-    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, sw->d_xc, xc.data(), bytes);
+    int rc = sw->x.alloc("phk_sweep_create", "rows", bytes);
+    if (rc == PHK_OK) rc = sw->xc.alloc("phk_sweep_create", "centred rows", bytes);
+    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, sw->x.ptr, X, bytes);
+    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, sw->xc.ptr, xc.data(), bytes);
     if (rc == PHK_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = PHK_ERR_HIP;
     if (rc != PHK_OK) {
-        sw_free(sw);
+        delete sw;
         return rc;
     }
     *out = sw;
@@ -175,7 +161,7 @@ extern "C" int phk_sweep_destroy(phk_ctx *ctx, phk_sweep *sw) {
     PHK_ENTER(ctx, "phk_sweep_destroy");
     if (!sw) return PHK_OK;
     PHK_HIP(hipStreamSynchronize(ctx->stream));
-    sw_free(sw);
+    delete sw;
     return PHK_OK;
 }
 
@@ -186,33 +172,21 @@ extern "C" int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint
     PHK_ENTER(ctx, "phk_sweep_run");
     PHK_REQUIRE(sw, "phk_sweep_run: NULL sweep");
     const uint64_t n = sw->n, D = sw->D;
-    PHK_REQUIRE(max_iter >= 1 && tol_rel >= 0.0 && chunk <= 65535, "phk_sweep_run: bad max_iter / tol / chunk");
+    const double *d_x = sw->x.as<double>();
+    PHK_TRY(kb_check_call("phk_sweep_run", max_iter, chunk));
+    PHK_REQUIRE(tol_rel >= 0.0, "phk_sweep_run: bad tol");
     if (S == 0) return PHK_OK;
     PHK_REQUIRE(ks && first_seed && draw_off && labels && status && n_iter && min_gap && seed_margin, "phk_sweep_run: NULL pointer");
     for (uint64_t s = 0; s < S; ++s) {
-        const uint32_t k = ks[s];
-        PHK_REQUIRE(k >= 1 && k <= n, "phk_sweep_run: need 1 <= k <= n (problem %llu: k=%u, n=%llu)", (unsigned long long)s, k,
-                    (unsigned long long)n);
-        PHK_REQUIRE(!sil || (k >= 2 && (uint64_t)k <= n - 1 && n >= 3),
-                    "phk_sweep_run: Number of labels is %u. Valid values are 2 to n_samples - 1 (inclusive)", k);
-        PHK_REQUIRE(first_seed[s] < n, "phk_sweep_run: first seed %u of problem %llu is not a row", first_seed[s], (unsigned long long)s);
-        const uint32_t T = 2 + (uint32_t)std::log((double)k);
-        PHK_REQUIRE(T <= KB_MAX_TRIALS, "phk_sweep_run: k = %u needs %u seeding trials per centre, at most %d are built", k, T,
-                    KB_MAX_TRIALS);
-        PHK_REQUIRE(draws || k == 1, "phk_sweep_run: NULL draws");
+        PHK_TRY(kb_check_problem("phk_sweep_run", s, ks[s], n, first_seed[s], draws));
+        PHK_REQUIRE(!sil || (ks[s] >= 2 && (uint64_t)ks[s] <= n - 1 && n >= 3),
+                    "phk_sweep_run: Number of labels is %u. Valid values are 2 to n_samples - 1 (inclusive)", ks[s]);
     }
+    // chunks of Sc problems in the caller's order
     const uint64_t Sc = std::min<uint64_t>(S, chunk ? chunk : SW_DEFAULT_CHUNK);
-    // the largest chunk's centres and draws
-    uint64_t ksum_max = 0, dsum_max = 0;
-    for (uint64_t s0 = 0; s0 < S; s0 += Sc) {
-        uint64_t ksum = 0, dsum = 0;
-        for (uint64_t s = s0; s < std::min(S, s0 + Sc); ++s) {
-            ksum += ks[s];
-            dsum += (uint64_t)(ks[s] - 1) * (2 + (uint32_t)std::log((double)ks[s]));
-        }
-        ksum_max = std::max(ksum_max, ksum);
-        dsum_max = std::max(dsum_max, dsum);
-    }
+    std::vector<uint64_t> cut;
+    for (uint64_t s0 = 0; s0 < S; s0 += Sc) cut.push_back(s0);
+    cut.push_back(S);
     // the pair distances, once per call, when they fit the budget
     bool stored = false;
     if (sil) {
@@ -220,15 +194,13 @@ extern "C" int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint
         if (pair_budget < 0) {
             size_t free_b = 0, total_b = 0;
             PHK_HIP(hipMemGetInfo(&free_b, &total_b));
-            budget = (uint64_t)free_b / 4 + (sw->d_pair ? n * n * 8 : 0);   // (the kept matrix is not "used" memory here)
+            budget = (uint64_t)free_b / 4 + sw->pair.bytes;   // (the kept matrix is not "used" memory here)
         } else {
             budget = (uint64_t)pair_budget;
         }
         stored = n * n * 8 <= budget;
-        if (stored && !sw->d_pair) {
-            if (hipMalloc((void **)&sw->d_pair, n * n * 8) != hipSuccess) {
-                sw->d_pair = nullptr;
-                (void)hipGetLastError();
+        if (stored && !sw->pair.ptr) {
+            if (sw->pair.alloc("phk_sweep_run", "pair distances", n * n * 8) != PHK_OK) {
                 stored = false;   // no room after all: the per-problem pass
             } else {
                 const uint64_t tiles = phk_div_up(n, CL_T);
@@ -237,35 +209,21 @@ extern "C" int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint
                     PHK_LAUNCH(ctx, "sw_pair_kernel",
                                cl_matrix_kernel<SwStoreSqrt>
                                <<<dim3((unsigned)tiles, (unsigned)std::min(step, tiles - y0)), dim3(CL_THREADS), 0, ctx->stream>>>(
-                                   sw->d_x, n, y0, sw->d_x, n, D, sw->d_pair + y0 * CL_T * n, nullptr));
+                                   d_x, n, y0, d_x, n, D, sw->pair.as<double>() + y0 * CL_T * n, nullptr));
             }
         }
     }
-    // the chunk's workspace
+    // the chunk's workspace: the core's regions, then the silhouettes'
     PhkLayout ws;
-    const uint64_t o_cen = ws.take(2 * ksum_max * D * 8), o_lab = ws.take(Sc * n * 4), o_clo = ws.take(Sc * n * 8),
-                   o_td = ws.take(Sc * KB_MAX_TRIALS * n * 8), o_cand = ws.take(Sc * KB_MAX_TRIALS * 4),
-                   o_seed = ws.take(ksum_max * 4), o_size = ws.take(ksum_max * 4), o_st = ws.take(Sc * sizeof(KbState)),
-                   o_draw = ws.take(dsum_max * 8 + 8), o_act = ws.take(256), o_perm = ws.take(sil ? Sc * n * 4 : 0),
-                   o_first = ws.take(sil ? (ksum_max + Sc) * 4 : 0), o_want = ws.take(Sc), o_sil = ws.take(sil ? Sc * n * 8 : 0);
-    PHK_TRY(kb_grow(ctx, &sw->ws, &sw->ws_bytes, ws.bytes, "phk_sweep_run", Sc));
-    char *w = (char *)sw->ws;
-    KbView v;
-    v.cen = (double *)(w + o_cen);
-    v.labels = (uint32_t *)(w + o_lab);
-    v.closest = (double *)(w + o_clo);
-    v.td = (double *)(w + o_td);
-    v.cand = (uint32_t *)(w + o_cand);
-    v.seeds = (uint32_t *)(w + o_seed);
-    v.sizes = (uint32_t *)(w + o_size);
-    v.st = (KbState *)(w + o_st);
-    v.draws = (const double *)(w + o_draw);
-    v.n = n;
-    v.D = D;
-    v.trials = KB_MAX_TRIALS;
-    const KbCentredRows rows = {sw->d_xc};
+    const KbSpace core(ws, kb_extent(ks, nullptr, cut, n, D));
+    const uint64_t o_perm = ws.take(sil ? Sc * n * 4 : 0), o_first = ws.take(sil ? (core.e.ksum + Sc) * 4 : 0), o_want = ws.take(Sc),
+                   o_sil = ws.take(sil ? Sc * n * 8 : 0);
+    PHK_TRY(sw->ws.grow(ctx, "phk_sweep_run", ws.bytes, Sc));
+    char *w = sw->ws.as<char>();
+    uint32_t *d_act;
+    const KbView v = core.bind(w, &d_act);
+    const KbCentredRows rows = {sw->xc.as<double>()};
     const KbNames names = {"sw_seed_dist_kernel", "sw_seed_choose_kernel", "sw_assign_kernel", "sw_update_kernel", "sw_stop_kernel"};
-    uint32_t *d_act = (uint32_t *)(w + o_act);
     uint32_t *d_perm = (uint32_t *)(w + o_perm), *d_first = (uint32_t *)(w + o_first);
     uint8_t *d_want = (uint8_t *)(w + o_want);
     double *d_sil = (double *)(w + o_sil);
@@ -275,30 +233,22 @@ extern "C" int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint
     std::vector<uint8_t> want(Sc);
     const double tol = sw->var_mean * tol_rel;
     uint64_t seed_out = 0;   // centres of the problems before the chunk
-    for (uint64_t s0 = 0; s0 < S; s0 += Sc) {
-        const uint64_t nb = std::min(Sc, S - s0);
+    for (uint64_t ci = 0; ci + 1 < cut.size(); ++ci) {
+        const uint64_t s0 = cut[ci], nb = cut[ci + 1] - s0;
         const unsigned gb = (unsigned)nb;
-        uint64_t dsum = 0;
         ch.clear();
-        for (uint64_t b = 0; b < nb; ++b) {
-            ch.add(ks[s0 + b], first_seed[s0 + b], dsum, tol);
-            const uint64_t nd = (uint64_t)(ch.st[b].k - 1) * ch.st[b].T;
-            if (nd)
-                PHK_HIP(hipMemcpyAsync(w + o_draw + dsum * 8, draws + draw_off[s0 + b], nd * 8, hipMemcpyHostToDevice, ctx->stream));
-            dsum += nd;
-        }
+        for (uint64_t s = s0; s < s0 + nb; ++s)
+            PHK_TRY(ch.add(ctx, v, ks[s], first_seed[s], draws ? draws + draw_off[s] : nullptr, tol));
         PHK_TRY(ch.upload(ctx, v));
         PHK_TRY(kb_solve_chunk(ctx, v, rows, ch, max_iter, d_act, names));
         PHK_HIP(hipMemcpyAsync(labels + s0 * n, v.labels, nb * n * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (seeds) PHK_HIP(hipMemcpyAsync(seeds + seed_out, v.seeds, (uint64_t)ch.ksum * 4, hipMemcpyDeviceToHost, ctx->stream));
-        PHK_HIP(hipMemcpyAsync(ch.st.data(), v.st, nb * sizeof(KbState), hipMemcpyDeviceToHost, ctx->stream));
-        PHK_HIP(hipStreamSynchronize(ctx->stream));
+        PHK_TRY(ch.download(ctx, v));
         for (uint64_t b = 0; b < nb; ++b) {
-            const KbState &s = ch.st[b];
-            status[s0 + b] = s.n_empty ? PHK_SWEEP_EMPTY : 0u;
-            n_iter[s0 + b] = (int32_t)s.n_iter;
-            seed_margin[s0 + b] = s.seed_margin;
-            min_gap[s0 + b] = KbChunk::min_gap(s);
+            status[s0 + b] = ch.met_empty(b) ? PHK_SWEEP_EMPTY : 0u;
+            n_iter[s0 + b] = ch.n_iter(b);
+            seed_margin[s0 + b] = ch.seed_margin(b);
+            min_gap[s0 + b] = ch.min_gap(b);
         }
         if (sil && stored) {
             // rows sorted by label (stable) and the clusters' first positions, per problem
@@ -324,11 +274,11 @@ extern "C" int phk_sweep_run(phk_ctx *ctx, phk_sweep *sw, uint64_t S, const uint
             PHK_HIP(hipMemcpyAsync(d_want, want.data(), nb, hipMemcpyHostToDevice, ctx->stream));
             PHK_LAUNCH(ctx, "sw_silhouette_kernel",
                        sw_silhouette_kernel<<<dim3((unsigned)phk_div_up(n, 256), gb), dim3(256), 0, ctx->stream>>>(
-                           sw->d_pair, n, v.st, v.labels, d_perm, d_first, d_want, d_sil));
+                           sw->pair.as<double>(), n, v.st, v.labels, d_perm, d_first, d_want, d_sil));
             PHK_TRY(phk_copy_to_host(ctx, sil + s0 * n, d_sil, nb * n * 8));
         } else if (sil) {
             for (uint64_t b = 0; b < nb; ++b)
-                PHK_TRY(phk_silhouettes_resident(ctx, sw->d_x, n, D, labels + (s0 + b) * n, ch.st[b].k, sil + (s0 + b) * n));
+                PHK_TRY(phk_silhouettes_resident(ctx, d_x, n, D, labels + (s0 + b) * n, ch.st[b].k, sil + (s0 + b) * n));
         }
         seed_out += ch.ksum;
     }

@@ -1,6 +1,7 @@
-"""The batched k-means core (csrc/kmeans_batch.h) through its two clients, on the GPU: the placement (reference rows plus one
-appended row, centred on the fly) and the sweep (resident centred rows) must agree bit for bit on the same problem; a fit that
-runs out of sweeps; k = 1."""
+"""The batched k-means core (csrc/kmeans_batch.h) through its three clients, on the GPU: the placement (reference rows plus one
+appended row, centred on the fly), the sweep (resident centred rows) and the combo grid (a fold's train rows, centred on the
+fly) must agree bit for bit on the same problem; a fit that runs out of sweeps; k = 1; the refusals the core's host half
+states once for all three."""
 import ctypes
 
 import numpy as np
@@ -149,3 +150,135 @@ def test_running_out_of_sweeps(unfinished, max_iter):
         assert got["min_gap"] == _bits(gap).item()
     if mixed:
         assert _same(swept[1], short)
+
+
+# ---- the third client ----------------------------------------------------------------------------------------------------
+def _grid_over(X):
+    """A ComboGrid whose train set 0 (positive class less fold 0) is exactly X in row order: X is positive and held out by
+    fold 1; two more positive rows and three negative ones are held out by fold 0.  -> (grid, set_mean, set_tol)."""
+    from phamers_amd import _lib
+    rng = np.random.RandomState(len(X))
+    D = X.shape[1]
+    rows = np.vstack((X, rng.randn(2, D), rng.randn(3, D) + 2.0))
+    fold_of = np.r_[np.ones(len(X)), np.zeros(5)].astype(np.uint32)
+    positive = np.r_[np.ones(len(X) + 2), np.zeros(3)].astype(np.uint8)
+    mean = X.mean(axis=0)
+    set_mean, set_tol = np.zeros((4, D)), np.zeros(4)
+    set_mean[0], set_tol[0] = mean, np.mean(np.var(X - mean, axis=0)) * 1e-4
+    return _lib.ComboGrid(_lib.get_context(), rows, fold_of, positive, 2), set_mean, set_tol
+
+
+@pytest.mark.parametrize("chunk", ["0", "1", "all but one"])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_the_combo_grid_agrees_with_the_sweep_bit_for_bit(both, shape, chunk):
+    """The same problems -- rows, k, first seed, draws, tolerance -- through phk_combo_grid_fit (rows read through their index
+    list, centred on the fly): sweep counts, min_gap and seed_margin as bit patterns and "empty cluster met" equal the sweep's,
+    and the bank holds NumPy's mean of X[labels == c] for the sweep's labels, whatever the chunking."""
+    from phamers_amd import _lib, learning
+    X, ks, _, swept = both[shape]
+    chunk = {"0": 0, "1": 1, "all but one": len(ks) - 1}[chunk]
+    drawn = [learning.placement_draws(len(X), k) for k in ks]
+    bank_off = np.concatenate(([0], np.cumsum(ks)[:-1]))
+    grid, set_mean, set_tol = _grid_over(X)
+    try:
+        out = grid.fit(np.zeros(len(ks)), ks, [d[0] for d in drawn], [d[1] for d in drawn], set_mean, set_tol, int(np.sum(ks)),
+                       bank_off, chunk=chunk)
+        bank = grid.get_centroids(0, int(np.sum(ks)))
+    finally:
+        grid.close()
+    for i, (k, s) in enumerate(zip(ks, swept)):
+        print("n=%d D=%d k=%d chunk=%d: sweeps %d / %d, min_gap %016x / %016x, seed_margin %016x / %016x, empty %s / %s"
+              % (shape + (k, chunk, out["n_iter"][i], s["n_iter"], _bits(out["min_gap"][i]).item(), s["min_gap"],
+                          _bits(out["seed_margin"][i]).item(), s["seed_margin"], bool(out["status"][i] & _lib.COMBO_GRID_EMPTY),
+                          s["empty"])))
+        assert int(out["n_iter"][i]) == s["n_iter"], k
+        assert _bits(out["min_gap"][i]).item() == s["min_gap"] and _bits(out["seed_margin"][i]).item() == s["seed_margin"], k
+        assert bool(out["status"][i] & _lib.COMBO_GRID_EMPTY) == s["empty"], k
+        for c in range(k):
+            members = X[s["labels"] == c]
+            want = np.mean(members, axis=0) if len(members) else np.zeros(X.shape[1])
+            assert np.array_equal(_bits(bank[bank_off[i] + c]), _bits(want)), (k, c)
+
+
+# ---- the refusals the three clients share --------------------------------------------------------------------------------
+class _Client(object):
+    """One client's handle over `rows` and one problem at a time through it: run(k, first, draws, ...) -> every result array
+    as bytes.  `rows_of_problem`: what k and the first seed are measured against (the placement appends a row)."""
+
+    def __init__(self, name, rows):
+        from phamers_amd import _lib
+        self.name, self.rows = name, rows
+        self.rows_of_problem = len(rows) + (1 if name == "placement" else 0)
+        self.k_too_large = self.rows_of_problem + 1
+        if name == "placement":
+            self.handle = _lib.Placement(_lib.get_context(), rows)
+        elif name == "sweep":
+            self.handle = _lib.Sweep(_lib.get_context(), rows)
+        else:
+            self.handle, self.set_mean, self.set_tol = _grid_over(rows)
+
+    def run(self, k, first, draws, max_iter=300, chunk=0):
+        if self.name == "placement":
+            out = self.handle.run(self.rows[:1] + 0.125, k, first, draws, max_iter=max_iter, chunk=chunk)
+        elif self.name == "sweep":
+            out = self.handle.run([k], [first], [draws], silhouettes=False, max_iter=max_iter, chunk=chunk)
+            out = dict(out, seeds=out["seeds"][0], sil=0)
+        else:
+            out = self.handle.fit([0], [k], [first], [draws], self.set_mean, self.set_tol, max(k, 1), [0], max_iter=max_iter,
+                                  chunk=chunk)
+            out = dict(out, bank=self.handle.get_centroids(0, max(k, 1)))
+        return {key: np.asarray(v).tobytes() for key, v in out.items()}
+
+    def valid(self):
+        from phamers_amd import learning
+        return self.run(3, *learning.placement_draws(self.rows_of_problem, 3))
+
+
+CLIENTS = ["placement", "sweep", "combo_grid"]
+
+
+@pytest.fixture(scope="module")
+def clients():
+    """(client, "small" | "large") -> (the client over 40 x 3 or 8104 x 1 rows, its valid problem's results), made on demand."""
+    made = {}
+
+    def get(name, size):
+        if (name, size) not in made:
+            rows = _blobs(40, 3, 43) if size == "small" else np.random.RandomState(8104).randn(8104, 1)
+            client = _Client(name, rows)
+            made[(name, size)] = (client, client.valid())
+        return made[(name, size)]
+    yield get
+    for client, _ in made.values():
+        client.handle.close()
+
+
+@pytest.mark.parametrize("case", ["k = 0", "k too large", "first seed past the rows", "chunk = 65536", "max_iter = 0", "trials"])
+@pytest.mark.parametrize("name", CLIENTS)
+def test_the_shared_refusals(clients, name, case):
+    """kb_check_call / kb_check_problem through each client: ValueError, and the handle then solves a valid problem with the
+    bits it gave before.  "trials": k = 8104 needs 2 + int(ln 8104) = 11 seeding trials per centre (e^9 = 8103.08...),
+    KB_MAX_TRIALS = 10 are built."""
+    from phamers_amd import learning
+    client, before = clients(name, "large" if case == "trials" else "small")
+    n = client.rows_of_problem
+    first, draws = learning.placement_draws(n, 3)
+    if case == "k = 0":
+        bad = dict(k=0, first=first, draws=np.zeros((0, 2)))
+    elif case == "k too large":
+        k = client.k_too_large
+        bad = dict(k=k, first=first, draws=learning.placement_draws(n, k)[1])
+    elif case == "first seed past the rows":
+        bad = dict(k=3, first=n, draws=draws)
+    elif case == "chunk = 65536":
+        bad = dict(k=3, first=first, draws=draws, chunk=65536)
+    elif case == "max_iter = 0":
+        bad = dict(k=3, first=first, draws=draws, max_iter=0)
+    else:
+        k = 8104
+        assert 2 + int(np.log(k)) == 11 and k <= len(client.rows)
+        bad = dict(k=k, first=first, draws=learning.placement_draws(n, k)[1])
+    with pytest.raises(ValueError, match="seeding trials" if case == "trials" else None) as err:
+        client.run(**bad)
+    print("%s, %s: %s" % (name, case, err.value))
+    assert client.valid() == before
