@@ -648,6 +648,33 @@ int phk_roc_curve_dev(phk_ctx *ctx, const double *d_scores, const uint8_t *d_lab
  * negatives with >=, positives with <, negatives with <.  Host pointers. */
 int phk_truth_counts(phk_ctx *ctx, const double *scores, const uint8_t *labels, uint64_t n, double threshold, uint64_t *counts);
 
+/* Paired comparison of the ROC areas of C score vectors over the SAME rows: DeLong's structural components
+ * as integers, and a stratified bootstrap.  scores[C][n] float64, one row per cell, columns in vstack(positive, negative)
+ * order: the first n_pos = P columns are the positives, N = n - P.  -0.0 == +0.0 as in the sort.
+ *   twice-placements  t_pos[c][i] = 2 #{j : y_j < x_i} + #{j : y_j == x_i},  t_neg[c][j] = 2 #{i : x_i > y_j} + #{i : x_i == y_j}
+ *                     (uint32); both sum to area2[c] = 2 P N AUC, the integer phk_roc_curve returns for the cell
+ *   Gram matrices     g10[a][b] = sum_i t_pos[a][i] t_pos[b][i],  g01[a][b] = sum_j t_neg[a][j] t_neg[b][j] (uint64, exact)
+ *   bootstrap         resample b draws P positives and N negatives with replacement: key(b, s) = splitmix64(splitmix64(seed) ^
+ *                     (2 b + s)), s = 0 for the positives and 1 for the negatives; draw t = 0 .. n_s - 1 picks the class's row
+ *                     (splitmix64(key + t) * n_s) >> 64; w[row] = times drawn; area2_boot[b][c] = sum_ij w_i w_j
+ *                     (2 [x_i > y_j] + [x_i == y_j]) <= 2 P N.  Resample b depends on (seed, b) alone; all cells share it.
+ * phk_compare_create uploads, sorts every cell and makes placements and Grams; the handle keeps the sorted orders for the
+ * bootstrap.  PHK_ERR_ARG for C == 0, C > PHK_COMPARE_MAX_CELLS, n_pos == 0 or n_pos == n; PHK_ERR_NAN for a score that is
+ * NaN or infinite; PHK_ERR_UNSUPPORTED for n >= 2^31 or when 4 N^2 P or 4 P^2 N reaches 2^64 (the Gram sums' bound).
+ * phk_compare_placements: t_pos[C][P], t_neg[C][N].  phk_compare_grams: area2[C], g10[C][C], g01[C][C].
+ * phk_compare_bootstrap: area2_boot[count][C] for the resamples first_resample .. first_resample + count - 1, per_launch of
+ * them per launch (0 = the default; the results do not depend on it); PHK_ERR_UNSUPPORTED beyond
+ * PHK_COMPARE_BOOT_MAX_ROWS rows (a resample's weights live in LDS).  Host pointers. */
+#define PHK_COMPARE_MAX_CELLS 256
+#define PHK_COMPARE_BOOT_MAX_ROWS 65535
+typedef struct phk_compare phk_compare;
+int phk_compare_create(phk_ctx *ctx, const double *scores, uint64_t C, uint64_t n, uint64_t n_pos, phk_compare **out);
+int phk_compare_destroy(phk_ctx *ctx, phk_compare *cmp);
+int phk_compare_placements(phk_ctx *ctx, phk_compare *cmp, uint32_t *t_pos, uint32_t *t_neg);
+int phk_compare_grams(phk_ctx *ctx, phk_compare *cmp, uint64_t *area2, uint64_t *g10, uint64_t *g01);
+int phk_compare_bootstrap(phk_ctx *ctx, phk_compare *cmp, uint64_t seed, uint64_t first_resample, uint64_t count,
+                          uint64_t per_launch, uint64_t *area2_boot);
+
 /* ---- device API -------------------------------------------------------------------- */
 /* ASCII -> packed stream (+ mask).  d_any_invalid (one uint32, device) is set non-zero when
  * some base is not one of symbols4; it may be NULL. */

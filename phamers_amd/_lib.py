@@ -146,6 +146,11 @@ SIGNATURES = {
     "phk_roc_curve": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p, c_void_p, P(c_u64), P(c_u64)]),
     "phk_roc_curve_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p, c_void_p, P(c_u64), P(c_u64)]),
     "phk_truth_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p]),
+    "phk_compare_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_u64, P(c_void_p)]),
+    "phk_compare_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_compare_placements": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_compare_grams": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_compare_bootstrap": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_u64, c_u64, c_void_p]),
     "phk_pack_ascii_dev": (c_int, [c_void_p, c_void_p, c_u64, c_char_p, c_void_p, c_void_p, c_void_p]),
     "phk_count_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_int,
                               c_void_p, c_void_p]),
@@ -793,6 +798,57 @@ class DbscanRows(_Resident):
                                             ptr(out["labels"]), ptr(out["coremask"]), ptr(out["n_clusters"]), ptr(out["launches"])))
         return out
 
+
+COMPARE_MAX_CELLS = 256            # PHK_COMPARE_MAX_CELLS
+COMPARE_BOOT_MAX_ROWS = 65535      # PHK_COMPARE_BOOT_MAX_ROWS: a resample's weights live in LDS
+
+
+def _check_compare(rc):
+    """``check`` for the phk_compare_* calls: a refusal of the input is the caller's ValueError."""
+    if rc == PHK_ERR_NAN:
+        raise ValueError("Input contains NaN or infinity.")
+    if rc in (PHK_ERR_ARG, PHK_ERR_UNSUPPORTED):
+        raise ValueError(last_error())
+    check(rc)
+
+
+class Compare(_Resident):
+    """C score vectors over the same rows, sorted on the device (phk_compare_create): placements, Gram matrices and the
+    stratified bootstrap of phamers_amd/compare.py.  ``scores`` is (C, n) float64, the first ``n_pos`` columns positive."""
+    _destroy = "phk_compare_destroy"
+
+    def __init__(self, ctx, scores, n_pos):
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        if scores.ndim != 2:
+            raise ValueError("scores must be 2-D")
+        self.ctx, self.C, self.n, self.n_pos = ctx, scores.shape[0], scores.shape[1], int(n_pos)
+        h = ctypes.c_void_p()
+        _check_compare(ctx.lib.phk_compare_create(ctx.handle, ptr(scores), self.C, self.n, self.n_pos, ctypes.byref(h)))
+        self.handle = h
+
+    def placements(self):
+        """(t_pos (C, P) uint32, t_neg (C, N) uint32)."""
+        self._open()
+        t_pos = np.empty((self.C, self.n_pos), dtype=np.uint32)
+        t_neg = np.empty((self.C, self.n - self.n_pos), dtype=np.uint32)
+        _check_compare(self.ctx.lib.phk_compare_placements(self.ctx.handle, self.handle, ptr(t_pos), ptr(t_neg)))
+        return t_pos, t_neg
+
+    def grams(self):
+        """(area2 (C,), G10 (C, C), G01 (C, C)), uint64."""
+        self._open()
+        area2 = np.empty(self.C, dtype=np.uint64)
+        g10, g01 = np.empty((self.C, self.C), dtype=np.uint64), np.empty((self.C, self.C), dtype=np.uint64)
+        _check_compare(self.ctx.lib.phk_compare_grams(self.ctx.handle, self.handle, ptr(area2), ptr(g10), ptr(g01)))
+        return area2, g10, g01
+
+    def bootstrap(self, seed, count, first=0, per_launch=0):
+        """area2_boot (count, C) uint64 of the resamples first .. first + count - 1."""
+        self._open()
+        out = np.empty((int(count), self.C), dtype=np.uint64)
+        _check_compare(self.ctx.lib.phk_compare_bootstrap(self.ctx.handle, self.handle, int(seed) & (2 ** 64 - 1), int(first),
+                                                          int(count), int(per_launch), ptr(out)))
+        return out
 
 
 def svm_gamma(X, gamma):
