@@ -429,6 +429,36 @@ int phk_kde_log_density(phk_ctx *ctx, const double *Q, uint64_t N, const double 
 int phk_kde_sweep(phk_ctx *ctx, const double *Q, uint64_t N, const double *X, uint64_t M, uint64_t D, const double *h,
                   uint32_t B, int exclude_self, uint64_t batch_rows, double *out);
 
+/* ---- multinomial likelihood scoring (this project's own method) ------------------------------------
+ * A contig is scored from its integer count row c (D bins) by the log-likelihood ratio of two mixtures of multinomials,
+ * one component per reference row r with the smoothed profile p_r[j] = (x_r[j] + a) / (sum_j x_r[j] + D a):
+ *     S[q, r]  = sum_j c_q[j] log p_r[j]
+ *     l_C(q)   = logsumexp_{r in class C, not excluded for q} S[q, r] - log n_eff(q, C)
+ *     score(q) = l_+(q) - l_-(q)              (nats; >= 0 reads as phage)
+ * n_eff(q, C) = the rows of class C that are not excluded for q.  Row r is excluded for query q when both carry a group id
+ * >= 0 and the two are equal (cross-validation: the group is the fold).  Everything is float64; the result of a query is a
+ * function of its count row, its group and the table alone -- not of N, the batch split or the entry point.
+ *
+ * phk_lik_table_create: a resident table from the two HOST log tables log_pos[n_pos][D], log_neg[n_neg][D] (the values
+ * log p_r[j]; the library never takes a logarithm of a profile) with optional group ids groups_pos[n_pos] / groups_neg[n_neg]
+ * (NULL = none; a negative id = no group).  n_neg == 0 (log_neg NULL) makes a one-class table: l_- = 0, score = l_+.
+ * PHK_ERR_NAN when a table entry is not finite; PHK_ERR_ARG for an empty positive table or D == 0. */
+typedef struct phk_lik_table phk_lik_table;
+int phk_lik_table_create(phk_ctx *ctx, const double *log_pos, uint64_t n_pos, const int32_t *groups_pos,
+                         const double *log_neg, uint64_t n_neg, const int32_t *groups_neg, uint64_t D, phk_lik_table **out);
+int phk_lik_table_destroy(phk_ctx *ctx, phk_lik_table *table);
+/* score(q) of the formula above for the HOST count rows counts[N][D] (uint32), with optional group ids query_groups[N]
+ * (NULL = none; they exclude rows only when the table has group ids too).  l_pos[N], l_neg[N] (either may be NULL) and
+ * scores[N], float64, to the host.  batch_rows: queries per device batch, 0 = the default (for tests; no result depends on
+ * it).  PHK_ERR_ARG, before any launch, when some query's n_eff is 0 in a class, or D is not the table's.  A row without
+ * counts scores exactly 0: every S is 0 and both class terms are log 1.  N == 0 is PHK_OK. */
+int phk_lik_score(phk_ctx *ctx, const phk_lik_table *table, const uint32_t *counts, uint64_t N, uint64_t D,
+                  const int32_t *query_groups, uint64_t batch_rows, double *l_pos, double *l_neg, double *scores);
+/* The same for the resident rows of a batch, read in place (folded rows when phk_batch_fold_strands has run -- the table
+ * should then come from folded reference counts); no groups. */
+int phk_batch_lik_score(phk_ctx *ctx, const phk_lik_table *table, const phk_batch *b, double *l_pos, double *l_neg,
+                        double *scores);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -94,6 +94,10 @@ SIGNATURES = {
     "phk_model_set_bandwidths": (c_int, [c_void_p, c_void_p, c_double, c_double]),
     "phk_kde_log_density": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_double, c_void_p]),
     "phk_kde_sweep": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_void_p, c_u32, c_int, c_u64, c_void_p]),
+    "phk_lik_table_create": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_u64, c_void_p, c_u64, P(c_void_p)]),
+    "phk_lik_table_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_lik_score": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u64, c_void_p, c_void_p, c_void_p]),
+    "phk_batch_lik_score": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -953,6 +957,57 @@ def nusvc_sweep(ctx, X, labels, nus, gammas, fold_of=None, folds=0, tol=1e-3, ma
     return out
 
 
+def _groups(groups, n, what):
+    """int32 C-contiguous group ids (n,), or None."""
+    if groups is None:
+        return None
+    g = np.ascontiguousarray(groups, dtype=np.int32)
+    if g.shape != (n,):
+        raise ValueError("%s: one group id per row (%d), got shape %r" % (what, n, g.shape))
+    return g
+
+
+class LikelihoodTable(_Resident):
+    """The resident log table of the multinomial likelihood scorer (phk_lik_table): ``log_pos`` (M+, D) and ``log_neg``
+    (M-, D, or None for a one-class table) float64 rows of log p_r[j], with optional group ids per row."""
+    _destroy = "phk_lik_table_destroy"
+
+    def __init__(self, ctx, log_pos, log_neg=None, groups_pos=None, groups_neg=None):
+        lp = np.ascontiguousarray(log_pos, dtype=np.float64)
+        ln = None if log_neg is None else np.ascontiguousarray(log_neg, dtype=np.float64)
+        if lp.ndim != 2 or (ln is not None and (ln.ndim != 2 or ln.shape[1] != lp.shape[1])):
+            raise ValueError("the log tables must be 2-D with the same number of columns")
+        self.ctx, self.D, self.n_pos, self.n_neg = ctx, lp.shape[1], lp.shape[0], 0 if ln is None else ln.shape[0]
+        gp = _groups(groups_pos, self.n_pos, "groups_pos")
+        gn = None if ln is None else _groups(groups_neg, self.n_neg, "groups_neg")
+        h = ctypes.c_void_p()
+        rc = ctx.lib.phk_lik_table_create(ctx.handle, ptr(lp), self.n_pos, ptr(gp), ptr(ln), self.n_neg, ptr(gn), self.D,
+                                          ctypes.byref(h))
+        if rc == PHK_ERR_NAN:
+            raise ValueError(last_error())
+        check_value(rc, nan=False)
+        self.handle = h
+
+    def _score(self, call, n, details):
+        lp, ln, sc = (np.empty(n, dtype=np.float64) for _ in range(3))
+        check_value(call(lp, ln, sc), nan=False)
+        if details is not None:
+            details["l_pos"], details["l_neg"] = lp, ln
+        return sc
+
+    def score(self, counts, query_groups=None, batch_rows=0, details=None):
+        """Scores (N,) float64 of the uint32 count rows ``counts`` (N, D) on the host (phk_lik_score).  ValueError when a
+        query's group leaves a class without rows."""
+        self._open()
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        if c.ndim != 2 or c.shape[1] != self.D:
+            raise ValueError("the counts must be (N, %d), got shape %r" % (self.D, c.shape))
+        g = _groups(query_groups, c.shape[0], "query_groups")
+        return self._score(lambda lp, ln, sc: self.ctx.lib.phk_lik_score(
+            self.ctx.handle, self.handle, ptr(c), c.shape[0], self.D, ptr(g), int(batch_rows), ptr(lp), ptr(ln), ptr(sc)),
+            c.shape[0], details)
+
+
 class Batch(_Resident):
     """Device-resident contig batch (phk_batch): counts + row sums in HBM; see include/phamers_hip.h."""
     _destroy = "phk_batch_free"
@@ -1087,6 +1142,13 @@ class Batch(_Resident):
         rc = self.ctx.lib.phk_batch_score(self.ctx.handle, model.handle, self.handle, METHODS[method], ptr(out))
         check_value(rc, arg=False)
         return out
+
+    def likelihood(self, table, details=None):
+        """Multinomial likelihood scores (n,) float64 of the resident count rows under a ``LikelihoodTable``
+        (phk_batch_lik_score); ``details``: a dict that receives 'l_pos' and 'l_neg'."""
+        self._open()
+        return table._score(lambda lp, ln, sc: self.ctx.lib.phk_batch_lik_score(
+            self.ctx.handle, table.handle, self.handle, ptr(lp), ptr(ln), ptr(sc)), self.n, details)
 
     def neighbors(self, model, k):
         """(distances (n, k), indices (n, k) int64 into the model's vstack(positive, negative)) of the k nearest train rows of

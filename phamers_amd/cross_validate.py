@@ -13,7 +13,9 @@ fold is then
       combo only),
     * for the svm method, a NuSVC fit on the rows the mask leaves in (phk_model_fit_svm),
     * one scoring call for the held-out rows.
-The dbscan method runs through the reference's per-fold calls of phamer.score_points.
+The dbscan method runs through the reference's per-fold calls of phamer.score_points.  The likelihood method (this
+project's own; ``positive_counts`` / ``negative_counts``, the integer rows) is one call of likelihood.cross_validate: the
+fold is a group id on the queries and on the table's rows.
 Scores are those of a model built from the fold's train rows alone (the k-NN search is translation invariant: only
 the error bounds depend on the centring vector, and they are evaluated for the one in use);
 tests/golden/cross_validation.npz holds what the reference's own cross_validate produced.
@@ -60,6 +62,7 @@ class cross_validator(object):
 
     def __init__(self):
         self.positive_data = self.negative_data = None
+        self.positive_counts = self.negative_counts = None   # the integer count rows: what method 'likelihood' scores
         self.positive_ids = self.negative_ids = None
         self.positive_scores = self.negative_scores = None
         self.equalize_reference = False
@@ -74,6 +77,8 @@ class cross_validator(object):
         self.negative_bandwidth = 0.01
         self.svm_nu = 0.5                            # NuSVC()'s defaults (method 'svm'); svm_grid.py tables other values
         self.svm_gamma = 'scale'
+        self.pseudocount = 0.5                       # method 'likelihood' (likelihood.py)
+        self.likelihood_per_kmer = False
         self.score_threshold = 0                    # scripts/cross_validate.py:53
         self.output_directory = "cross_validation"   # scripts/cross_validate.py:55
         self.methods = list(ALL_METHODS)             # what cross_validate_all_algorithms runs (scripts/cross_validate.py:304)
@@ -83,6 +88,8 @@ class cross_validator(object):
         """Every reference row scored by a model that has not seen its fold (scripts/cross_validate.py:57-101).
         Returns (positive_scores, negative_scores)."""
         self._equalize()
+        if self.method == 'likelihood' and self.scoring_function is phamer.score_points:
+            return self._likelihood_folds()
         self.num_positive, self.num_negative = self.positive_data.shape[0], self.negative_data.shape[0]
         plan = FoldPlan(self.num_positive, self.num_negative, self.N, self.seed)
         self.positive_assignment, self.negative_assignment = plan.positive, plan.negative
@@ -100,6 +107,24 @@ class cross_validator(object):
         self.positive_data, self.negative_data = self.positive_data[:m], self.negative_data[:m]
         self.positive_ids = None if self.positive_ids is None else self.positive_ids[:m]
         self.negative_ids = None if self.negative_ids is None else self.negative_ids[:m]
+        if self.positive_counts is not None and self.negative_counts is not None:
+            self.positive_counts, self.negative_counts = self.positive_counts[:m], self.negative_counts[:m]
+
+    def _likelihood_folds(self):
+        """Method 'likelihood': the count rows, every fold excluded by its group id in ONE device call
+        (likelihood.cross_validate on this run's FoldPlan)."""
+        from . import likelihood
+        if self.positive_counts is None or self.negative_counts is None:
+            raise ValueError("method 'likelihood' needs the integer count rows (positive_counts / negative_counts): "
+                             "positive_data / negative_data hold frequencies only")
+        self.num_positive, self.num_negative = len(self.positive_counts), len(self.negative_counts)
+        plan = FoldPlan(self.num_positive, self.num_negative, self.N, self.seed)
+        self.positive_assignment, self.negative_assignment = plan.positive, plan.negative
+        self.positive_scores, self.negative_scores = likelihood.cross_validate(
+            self.positive_counts, self.negative_counts, self.N, self.seed, self.pseudocount, self.likelihood_per_kmer,
+            _plan=plan)
+        logger.info("%d-fold cross validation complete." % self.N)
+        return self.positive_scores, self.negative_scores
 
     # ---- batched: one model, a fold = mask + centroids ---------------------------------------------------------
     def _fold_centroids(self, train_rows):
@@ -280,6 +305,7 @@ def main(argv=None):
     if args.both_strands:
         from . import transform_kmers
         positive_data, negative_data = transform_kmers.fold_strands(positive_data), transform_kmers.fold_strands(negative_data)
+    validator.positive_counts, validator.negative_counts = positive_data, negative_data
     validator.positive_data = kmer.normalize_counts(positive_data)
     validator.negative_data = kmer.normalize_counts(negative_data)
     validator.equalize_reference = args.equalize_reference

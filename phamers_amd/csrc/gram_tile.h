@@ -42,6 +42,27 @@ __device__ __forceinline__ void gram_load8(const double *__restrict__ X, uint64_
     }
 }
 
+// The same 8 columns of a uint32 count row, converted in registers (exact: every uint32 is a float64): the A operand of the
+// likelihood scorer (likelihood.hip), which multiplies the integer counts themselves.
+template <bool FULL>
+__device__ __forceinline__ void gram_load8(const uint32_t *__restrict__ X, uint64_t D, uint64_t row, bool ok, uint64_t c0,
+                                           double v[8]) {
+    if (FULL) {
+        if (ok) {
+            const uint4 *p = (const uint4 *)(X + row * D + c0);
+            const uint4 t0 = p[0], t1 = p[1];
+            v[0] = (double)t0.x, v[1] = (double)t0.y, v[2] = (double)t0.z, v[3] = (double)t0.w;
+            v[4] = (double)t1.x, v[5] = (double)t1.y, v[6] = (double)t1.z, v[7] = (double)t1.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = 0.0;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (ok && c0 + i < D) ? (double)X[row * D + c0 + i] : 0.0;
+    }
+}
+
 // The query that entry acc[a][t][r] of this lane belongs to (q0 = the wave's first query); its row is st + 16 t + li.
 __device__ __forceinline__ uint64_t gram_query(uint64_t q0, int a, int r) {
     return q0 + 16 * a + ((threadIdx.x & 63) >> 4) + 4 * r;
@@ -49,9 +70,9 @@ __device__ __forceinline__ uint64_t gram_query(uint64_t q0, int a, int r) {
 
 // acc[a][t] = Q[q0 + 16 a ..][:] . R[st + 16 t ..][:] over all D columns, in column-step order (queries at or past nq and
 // rows at or past r1 enter as zeros).  QT: the 16-query tiles the wave holds (GT_QT unless a kernel narrows its tile; a tile's
-// products do not depend on it).
-template <bool FULL, int QT = GT_QT>
-__device__ __forceinline__ void gram_tile(const double *__restrict__ Q, uint64_t nq, uint64_t q0, const double *__restrict__ R,
+// products do not depend on it).  TQ: the element type of the query rows, double or uint32_t (count rows, see gram_load8).
+template <bool FULL, int QT = GT_QT, typename TQ = double>
+__device__ __forceinline__ void gram_tile(const TQ *__restrict__ Q, uint64_t nq, uint64_t q0, const double *__restrict__ R,
                                           uint64_t r1, uint64_t st, uint64_t D, f64x4 acc[QT][GT_RT]) {
     const int li = threadIdx.x & 15, kk = (threadIdx.x & 63) >> 4;
 #pragma unroll

@@ -30,6 +30,10 @@ The silhouette method raises NotImplementedError: the reference builds its negat
 (scripts/phamer.py:295), so a faithful port scores 0 for every contig after an O((N + n)^2) silhouette pass
 (SURVEY.md section 8).  The functional score_points keeps its method set (knn / kmeans / combo / density) and raises
 for the others; score_with_scorer is the same call for every method of phamer_scorer.
+
+The likelihood method (this project's own: likelihood.py) scores the contigs' integer COUNT rows
+against the reference COUNT rows (``positive_counts`` / ``negative_counts``, which load_data() keeps beside the normalised
+matrices when it is the scoring method); frequencies alone raise ValueError.
 """
 import argparse
 import logging
@@ -45,7 +49,7 @@ logging.basicConfig(format='[%(asctime)s][%(levelname)s][%(funcName)s] - %(messa
 logger = logging.getLogger(__name__)
 logger.setLevel(logging.WARNING)
 
-_GPU_METHODS = ('dbscan', 'knn', 'kmeans', 'combo', 'density', 'svm')
+_GPU_METHODS = ('dbscan', 'knn', 'kmeans', 'combo', 'density', 'svm', 'likelihood')
 _OTHER_METHODS = ('silhouette',)
 _CENTROID_METHODS = ('kmeans', 'combo')
 _FUNCTIONAL_METHODS = ('knn', 'kmeans', 'combo', 'density')   # what the functional score_points serves
@@ -91,6 +95,9 @@ class phamer_scorer(object):
         self.negative_bandwidth = 0.01
         self.svm_nu = 0.5                   # NuSVC()'s defaults (svm method); a table of other values: svm_grid.py
         self.svm_gamma = 'scale'
+        self.pseudocount = 0.5              # likelihood method (this project's own, likelihood.py): the profiles' pseudocount,
+        self.likelihood_per_kmer = False    # and whether a score is divided by its contig's k-mers
+        self.positive_counts = self.negative_counts = None   # the reference COUNT rows, which that method scores against
         self.k_clusters_positive = 86      # scripts/phamer.py:80-89 (dbscan method: its k-means fallback, eps, min_samples)
         self.k_clusters_negative = 20
         self.eps = [1, 1]
@@ -156,6 +163,17 @@ class phamer_scorer(object):
         self._load_queries(length_requirement)
 
     def _load_reference(self):
+        if self.scoring_method == 'likelihood':   # the count rows are kept beside the normalised matrices
+            from . import kmer, transform_kmers
+            fold = transform_kmers.fold_strands if self.both_strands else (lambda counts: counts)
+            self.positive_ids, counts = fileIO.read_feature_file(self.positive_features_file, normalize=False)
+            self.positive_counts = fold(counts)
+            self.negative_ids, counts = fileIO.read_feature_file(self.negative_features_file, normalize=False)
+            self.negative_counts = fold(counts)
+            self.positive_data = kmer.normalize_counts(self.positive_counts)
+            self.negative_data = kmer.normalize_counts(self.negative_counts)
+            return
+        self.positive_counts = self.negative_counts = None
         if self.both_strands:     # the counts are folded before they are normalised
             from . import kmer, transform_kmers
             self.positive_ids, counts = fileIO.read_feature_file(self.positive_features_file)
@@ -369,6 +387,8 @@ class phamer_scorer(object):
             self.positive_data, self.negative_data = self.positive_data[:m], self.negative_data[:m]
             self.positive_ids = None if self.positive_ids is None else self.positive_ids[:m]
             self.negative_ids = None if self.negative_ids is None else self.negative_ids[:m]
+            if self.positive_counts is not None and self.negative_counts is not None:
+                self.positive_counts, self.negative_counts = self.positive_counts[:m], self.negative_counts[:m]
             self.num_positive = self.num_negative = m
 
     def score_points(self):
@@ -514,6 +534,33 @@ class phamer_scorer(object):
         """scripts/phamer.py:303-313: knn score + kmeans score (one fused GPU pass)."""
         return self._gpu_score('combo')
 
+    def likelihood_score_points(self):
+        """This project's own method (likelihood.py): the log-likelihood ratio, in nats, of the contig's integer count row
+        under the two classes' mixtures of multinomials -- ``pseudocount`` smooths the reference profiles,
+        ``likelihood_per_kmer`` divides by the contig's k-mers.  It scores counts: the resident batch (a counted FASTA
+        file or an integer features cache) against ``positive_counts`` / ``negative_counts``, which load_data() keeps
+        when this is the scoring method.  ValueError when only frequencies are there."""
+        from . import likelihood
+        ref = self.positive_counts, self.negative_counts
+        if any(c is None for c in ref) or any(d is not None and len(d) != len(c)
+                                              for c, d in zip(ref, (self.positive_data, self.negative_data))):
+            raise ValueError("scoring method 'likelihood' needs the reference COUNT rows (positive_counts / negative_counts, "
+                             "which load_data() reads from the feature files when it is the scoring method): "
+                             "positive_data / negative_data hold frequencies only")
+        if self._batch is None:
+            raise ValueError("scoring method 'likelihood' needs the contigs' integer k-mer counts (a counted FASTA file or an "
+                             "integer features file): data_points holds frequencies only")
+        table = _lib.LikelihoodTable(_lib.get_context(), likelihood.log_table(ref[0], self.pseudocount),
+                                     likelihood.log_table(ref[1], self.pseudocount))
+        try:
+            scores = self._batch.likelihood(table)
+        finally:
+            table.close()
+        if self.likelihood_per_kmer:
+            with np.errstate(invalid='ignore', divide='ignore'):
+                scores = scores / self._batch.row_sums().astype(np.float64)
+        return scores
+
 
 def _length_screen(data_ids, fasta_ids, lengths, length_requirement):
     """The rows screen_by_length keeps (scripts/phamer.py:144-157): (keep mask over data_ids, ids of the long contigs), or
@@ -598,7 +645,8 @@ def main(argv=None):
     """The reference's command line for this path (scripts/phamer.py:512-598), cut to what the path uses:
         python -m phamers_amd.phamer -in <input_dir> -data <data_dir> [--equalize_reference]
     Scores go to <input_dir>/phamer_output/phamer_scores.csv (or -out).  As in the reference the method is always
-    'combo' (its --method is parsed and never applied)."""
+    'combo' (its --method is parsed and never applied) -- unless --pseudocount or --per_kmer, this
+    project's own flags, select the likelihood method (likelihood.py)."""
     ap = _parser()
     args = ap.parse_args(argv)
     if args.do_tsne or args.plot_tsne:
@@ -609,6 +657,9 @@ def main(argv=None):
             ap.error("--neighbors must be in 1..%d (got %d)" % (_lib.NEIGHBORS_MAX_K, args.neighbors))
         if (args.gpus and args.gpus > 1) or world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1":
             ap.error("--neighbors is not sharded: run it on one GPU (without --gpus)")
+    if (hasattr(args, "pseudocount") or hasattr(args, "per_kmer")) and (
+            (args.gpus and args.gpus > 1) or world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1"):
+        ap.error("--pseudocount / --per_kmer (the likelihood method) are not sharded: run them on one GPU (without --gpus)")
     if world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1":   # one rank of a sharded run (started below, or by
                                                                         # torch.distributed.run; forced: a 1-rank group, tests)
         return _run_rank(ap, args)
@@ -650,6 +701,12 @@ def _parser():
                                       help="Neighbours of the k-NN vote (the scorer's default: 3; combo_grid.py tables others)")),
             (('--k_clusters',), dict(type=int, default=argparse.SUPPRESS, metavar='K',
                                      help="Clusters per class of the k-means fit (the scorer's default: 86)")),
+            # (no defaults either: the method stays 'combo' unless one of the two is given, and the stamped summary is unchanged)
+            (('--pseudocount',), dict(type=float, default=argparse.SUPPRESS, metavar='A',
+                                      help="Score with the likelihood method (likelihood.py), the reference profiles smoothed "
+                                           "by this pseudocount (the scorer's default: 0.5; one GPU only)")),
+            (('--per_kmer',), dict(action='store_true', default=argparse.SUPPRESS,
+                                   help="Score with the likelihood method, every score divided by its contig's k-mers")),
             (('-v', '--verbose'), dict(action='store_true')),
             (('--debug',), dict(action='store_true')),
             # the rest of the reference's command line (scripts/phamer.py:515-553), so that its launch scripts
@@ -679,6 +736,18 @@ def _apply_k_options(scorer, args):
             setattr(scorer, name, getattr(args, name))
 
 
+def _apply_likelihood_options(scorer, args):
+    """--pseudocount / --per_kmer: either one selects the likelihood method and sets the scorer's attribute."""
+    if hasattr(args, "pseudocount"):
+        if not (np.isfinite(args.pseudocount) and args.pseudocount > 0):
+            raise SystemExit("--pseudocount must be finite and > 0 (got %r). Exiting..." % (args.pseudocount,))
+        scorer.pseudocount = args.pseudocount
+    if hasattr(args, "per_kmer"):
+        scorer.likelihood_per_kmer = True
+    if hasattr(args, "pseudocount") or hasattr(args, "per_kmer"):
+        scorer.scoring_method = 'likelihood'
+
+
 def _run(ap, args):
     logger.setLevel(logging.DEBUG if args.debug else logging.INFO if args.verbose else logging.WARNING)
 
@@ -686,6 +755,7 @@ def _run(ap, args):
     scorer.kmer_length = args.kmer_length
     scorer.both_strands = args.both_strands
     _apply_k_options(scorer, args)
+    _apply_likelihood_options(scorer, args)
     scorer.input_directory, scorer.fasta_file, scorer.features_file = args.input_directory, args.fasta_file, args.features_file
     if args.data_directory:
         scorer.data_directory = args.data_directory
@@ -708,7 +778,8 @@ def _run(ap, args):
         if args.equalize_reference:
             scorer.equalize_reference_data()
         lap("reference matrices")
-        scorer.prefetch_centroids(after_fasta_read=True)
+        if scorer.scoring_method != 'likelihood':     # (which fits nothing)
+            scorer.prefetch_centroids(after_fasta_read=True)
         scorer._load_queries(args.length_requirement)
         lap("contigs counted")
         os.makedirs(scorer.output_directory, exist_ok=True)

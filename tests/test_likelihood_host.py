@@ -1,0 +1,191 @@
+"""CPU: the multinomial likelihood method's host side (phamers_amd/likelihood.py) and its restatements
+(tests/likelihood_ref.py): the float64 statement within the derived bound of the extended one, the log table and its
+argument rules, the zero-row rule, the group semantics, the command lines, and what stays as it was."""
+import numpy as np
+import pytest
+
+from tests import helpers, likelihood_ref as ref
+
+
+@pytest.fixture(scope="module")
+def golden():
+    g = helpers.load_npz("ref_features.npz")
+    return g["pos_counts"][:300].astype(np.int64), g["neg_counts"][:300].astype(np.int64)
+
+
+def _edge_rows(D=256):
+    zero = np.zeros(D, dtype=np.int64)
+    one = zero.copy()
+    one[7] = 1
+    homo = zero.copy()
+    homo[0] = 4997
+    return np.stack((zero, one, homo))
+
+
+def test_float64_statement_within_bound_of_extended(golden):
+    from phamers_amd import cross_validate
+    pos, neg = golden
+    lp, ln = ref.log_table(pos), ref.log_table(neg)
+    plan = cross_validate.FoldPlan(len(pos), len(neg), 20, 0)
+    q, qg = np.vstack((pos, neg)), np.concatenate((plan.positive, plan.negative))
+    got = ref.statement(q, lp, ln, qg, plan.positive, plan.negative)
+    want, tol = ref.check(got, q, lp, ln, qg, plan.positive, plan.negative, what="golden, 20 folds")
+    # far inside: the bound is a worst case over D terms
+    assert np.max(np.abs((got[2] - want[2]).astype(np.float64)) / tol) < 0.1
+    edge = _edge_rows()
+    ref.check(ref.statement(edge, lp, ln), edge, lp, ln, what="edge rows")
+    big = neg[np.argsort(neg.sum(axis=1))[-3:]]       # the longest genomes: the largest |S|
+    s = ref.statement(big, lp, ln)
+    assert np.isfinite(s[2]).all() and np.abs(s[0]).min() > 1e5
+    ref.check(s, big, lp, ln, what="largest rows")
+
+
+def test_log_table(golden):
+    from phamers_amd import likelihood
+    pos, _ = golden
+    t = likelihood.log_table(pos)
+    assert t.dtype == np.float64 and t.shape == pos.shape and t.flags["C_CONTIGUOUS"]
+    assert np.array_equal(t, ref.log_table(pos))
+    wide = ref.log_table(pos, dtype=np.longdouble)
+    assert np.max(np.abs(t - wide) / (1 + np.abs(wide))) <= 4 * ref.U
+    assert np.allclose(np.exp(t).sum(axis=1), 1.0, rtol=0, atol=1e-12)       # every row is a distribution
+    assert np.array_equal(likelihood.log_table(pos.astype(np.float64)), t)   # integral floats are counts
+    assert np.array_equal(likelihood.log_table(pos[0]), t[:1])               # one row
+    a2 = likelihood.log_table(pos[:2], pseudocount=2.0)
+    assert np.array_equal(a2, ref.log_table(pos[:2], 2.0)) and not np.array_equal(a2, t[:2])
+    z = likelihood.log_table(np.zeros((1, 16), dtype=np.int64))
+    assert np.array_equal(z, np.full((1, 16), np.log(0.5 / 8.0)))            # a row without counts: the flat profile
+
+
+@pytest.mark.parametrize("a", [0, 0.0, -0.5, np.inf, -np.inf, np.nan])
+def test_log_table_refuses_pseudocount(a):
+    from phamers_amd import likelihood
+    with pytest.raises(ValueError, match="pseudocount"):
+        likelihood.log_table(np.ones((2, 4), dtype=np.int64), pseudocount=a)
+
+
+def test_count_arguments():
+    from phamers_amd import likelihood
+    freq = np.full((2, 4), 0.25)
+    for call in (lambda: likelihood.log_table(freq),
+                 lambda: likelihood.score(freq, np.ones((1, 4), int), np.ones((1, 4), int)),
+                 lambda: likelihood.score(np.ones((1, 4), int), freq, np.ones((1, 4), int)),
+                 lambda: likelihood.log_likelihood(np.ones((1, 4), int), freq),
+                 lambda: likelihood.cross_validate(freq, np.ones((2, 4), int), 2, 0)):
+        with pytest.raises(ValueError, match="counts, not frequencies"):
+            call()
+    with pytest.raises(ValueError, match="counts, not frequencies"):
+        likelihood.log_table(np.array([[1.0, np.nan]]))
+    for bad in (np.array([[1, -1]]), np.array([[1, 2 ** 32]], dtype=np.int64)):
+        with pytest.raises(ValueError, match=r"\[0, 2\^32\)"):
+            likelihood.log_table(bad)
+    with pytest.raises(ValueError, match="2-D"):
+        likelihood.log_table(np.ones((2, 2, 2), dtype=int))
+    with pytest.raises(ValueError, match="integers"):
+        likelihood.log_table(np.array([["a", "b"]]))
+    with pytest.raises(ValueError, match="same number of columns"):
+        likelihood.score(np.ones((1, 4), int), np.ones((1, 16), int), np.ones((1, 16), int))
+    assert likelihood.log_table(np.array([[2 ** 32 - 1, 0]], dtype=np.uint64)).shape == (1, 2)
+
+
+def test_zero_row_rule(golden):
+    pos, neg = golden
+    lp, ln = ref.log_table(pos), ref.log_table(neg)
+    zero = np.zeros((1, 256), dtype=np.int64)
+    for dtype in (np.float64, np.longdouble):
+        l_pos, l_neg, s = ref.statement(zero, lp, ln, dtype=dtype)
+        assert s[0] == 0.0 and l_pos[0] == 0.0 and l_neg[0] == 0.0       # every S is 0, both class terms are log 1
+    from phamers_amd import likelihood
+    assert np.isnan(likelihood._per_kmer(np.zeros(1), zero)[0])          # per k-mer: 0 / 0
+    assert likelihood._per_kmer(np.array([3.0]), np.array([[1, 2]]))[0] == 1.0
+
+
+def test_group_exclusion_is_deletion(golden):
+    pos, neg = golden
+    pos, neg = pos[:60], neg[:50]
+    lp, ln = ref.log_table(pos), ref.log_table(neg)
+    gp, gn = np.arange(60) % 4, np.arange(50) % 4
+    gp[5], gn[7] = -1, -1                               # a row without a group is never excluded
+    q = np.vstack((pos[:8], neg[:8]))
+    qg = np.array([0, 1, 2, 3, 0, -1, 2, 3] * 2)
+    got = ref.statement(q, lp, ln, qg, gp, gn)
+    for i in range(len(q)):
+        kp = np.ones(60, bool) if qg[i] < 0 else gp != qg[i]
+        kn = np.ones(50, bool) if qg[i] < 0 else gn != qg[i]
+        want, tol = ref.check(tuple(v[i:i + 1] for v in got), q[i:i + 1], lp[kp], ln[kn], what="row %d" % i)
+    assert not np.array_equal(got[2], ref.statement(q, lp, ln)[2])
+    with pytest.raises(ValueError, match="without rows"):
+        ref.statement(q[:1], lp[:3], ln, [1], [1, 1, 1], gn)
+    # groups on one side only exclude nothing
+    assert np.array_equal(ref.statement(q, lp, ln, qg)[2], ref.statement(q, lp, ln)[2])
+
+
+def test_thinning_is_seeded_and_keeps_the_total(golden):
+    from phamers_amd import likelihood
+    pos, _ = golden
+    a = likelihood.thin(pos[:5], 200, np.random.RandomState(3))
+    b = likelihood.thin(pos[:5], 200, np.random.RandomState(3))
+    assert a.dtype == np.uint32 and np.array_equal(a, b) and (a.sum(axis=1) == 200).all()
+    assert ((a > 0) <= (pos[:5] > 0)).all()
+
+
+def test_command_lines_parse():
+    from phamers_amd import likelihood, phamer
+    a = likelihood._parser().parse_args("-pf p.csv -nf n.csv -N 20 --seed 0 --pseudocount 0.25 --per_kmer --lengths 200 500 "
+                                        "-out t.csv".split())
+    assert (a.positive_features_file, a.negative_features_file, a.N_fold, a.seed) == ("p.csv", "n.csv", "20", 0)
+    assert (a.pseudocount, a.per_kmer, a.lengths, a.output_file) == (0.25, True, [200, 500], "t.csv")
+    a = likelihood._parser().parse_args("-pf p.csv -nf n.csv -N loo".split())
+    assert (a.N_fold, a.seed, a.pseudocount, a.per_kmer, a.lengths, a.output_file) == ("loo", None, 0.5, False, [], None)
+    with pytest.raises(SystemExit):
+        likelihood._parser().parse_args("-pf p.csv -nf n.csv".split())
+    assert "ignores" in likelihood.__doc__ and "overlap" in likelihood.__doc__
+    # phamers_amd.phamer: the flags are absent unless given, and either selects the method
+    ap = phamer._parser()
+    plain = ap.parse_args("-in x -data y".split())
+    assert not hasattr(plain, "pseudocount") and not hasattr(plain, "per_kmer")
+    sc = phamer.phamer_scorer()
+    assert (sc.pseudocount, sc.likelihood_per_kmer, sc.scoring_method) == (0.5, False, "combo")
+    phamer._apply_likelihood_options(sc, plain)
+    assert (sc.pseudocount, sc.likelihood_per_kmer, sc.scoring_method) == (0.5, False, "combo")
+    phamer._apply_likelihood_options(sc, ap.parse_args("-in x -data y --pseudocount 1.5".split()))
+    assert (sc.pseudocount, sc.likelihood_per_kmer, sc.scoring_method) == (1.5, False, "likelihood")
+    sc = phamer.phamer_scorer()
+    phamer._apply_likelihood_options(sc, ap.parse_args("-in x -data y --per_kmer".split()))
+    assert (sc.pseudocount, sc.likelihood_per_kmer, sc.scoring_method) == (0.5, True, "likelihood")
+    with pytest.raises(SystemExit):
+        phamer._apply_likelihood_options(sc, ap.parse_args("-in x -data y --pseudocount 0".split()))
+    with pytest.raises(SystemExit):
+        phamer.main("-in x -data y --per_kmer --gpus 2".split())
+
+
+def test_scorer_refuses_frequencies():
+    from phamers_amd import phamer
+    sc = phamer.phamer_scorer()
+    assert sc.method_function_map["likelihood"] == sc.likelihood_score_points
+    assert sc.positive_counts is None and sc.negative_counts is None
+    sc.scoring_method = "likelihood"
+    sc.data_points = np.full((2, 256), 1.0 / 256)
+    sc.positive_data = sc.negative_data = np.full((3, 256), 1.0 / 256)
+    with pytest.raises(ValueError, match="'likelihood' needs the reference COUNT rows"):
+        sc.score_points()
+    sc.positive_counts = sc.negative_counts = np.ones((3, 256), dtype=np.int64)
+    with pytest.raises(ValueError, match="'likelihood' needs the contigs' integer k-mer counts"):
+        sc.score_points()
+    sc.positive_counts = np.ones((2, 256), dtype=np.int64)          # counts that are not those of positive_data
+    with pytest.raises(ValueError, match="'likelihood' needs the reference COUNT rows"):
+        sc.score_points()
+    with pytest.raises(NotImplementedError):
+        phamer.score_points(sc.data_points, sc.positive_data, sc.negative_data, method="likelihood")
+
+
+def test_validator_routes_and_keeps_its_method_list():
+    from phamers_amd import cross_validate
+    assert cross_validate.ALL_METHODS == ('dbscan', 'kmeans', 'knn', 'svm', 'density', 'combo')
+    v = cross_validate.cross_validator()
+    assert v.methods == list(cross_validate.ALL_METHODS)
+    assert (v.positive_counts, v.negative_counts, v.pseudocount, v.likelihood_per_kmer) == (None, None, 0.5, False)
+    v.method = "likelihood"
+    v.positive_data = v.negative_data = np.full((4, 16), 1.0 / 16)
+    with pytest.raises(ValueError, match="'likelihood' needs the integer count rows"):
+        v.cross_validate()
