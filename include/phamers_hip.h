@@ -459,6 +459,34 @@ int phk_lik_score(phk_ctx *ctx, const phk_lik_table *table, const uint32_t *coun
 int phk_batch_lik_score(phk_ctx *ctx, const phk_lik_table *table, const phk_batch *b, double *l_pos, double *l_neg,
                         double *scores);
 
+/* ---- likelihood-ranked reference lookup (this project's own) ----------------------------------------
+ * The first `top` rows of a HOST log table L[M][D] for every uint32 count row c, in order of (S descending, row index
+ * ascending), S[q, r] = sum_j c_q[j] L[r, j] in float64 as the likelihood scorer's Gram tile gives it -- the bits of a
+ * result do not depend on N, the batch split, the entry point or the run.  The library does not know what the table holds:
+ * the multinomial log profiles of likelihood.py or the Markov log transition table of hosts.py.  With group ids on both sides
+ * a row is skipped for a query when both ids are >= 0 and equal.
+ *
+ * phk_host_table_create: a resident table with optional group ids groups[M] (NULL = none; a negative id = no group).
+ * PHK_ERR_NAN when a table entry is not finite; PHK_ERR_ARG for an empty table. */
+#define PHK_HOSTS_MAX_TOP 16
+typedef struct phk_host_table phk_host_table;
+int phk_host_table_create(phk_ctx *ctx, const double *log_table, uint64_t M, uint64_t D, const int32_t *groups,
+                          phk_host_table **out);
+int phk_host_table_destroy(phk_ctx *ctx, phk_host_table *table);
+/* idx[N][top] (int32) and s[N][top] (float64, nats) to the host for the HOST count rows counts[N][D], with optional group
+ * ids query_groups[N].  batch_rows: queries per device batch, 0 = the default (for tests; no result depends on it).
+ * PHK_ERR_ARG, before any launch, when top is not in 1..PHK_HOSTS_MAX_TOP or exceeds the rows some query has left.  A row
+ * without counts gets rows 0..top-1 (of those it has left) with S = 0.  N == 0 is PHK_OK. */
+int phk_host_rank(phk_ctx *ctx, const phk_host_table *table, const uint32_t *counts, uint64_t N, uint64_t D,
+                  const int32_t *query_groups, int top, uint64_t batch_rows, int32_t *idx, double *s);
+/* The same for the resident rows of a batch, read in place (folded rows when phk_batch_fold_strands has run); no groups. */
+int phk_batch_host_rank(phk_ctx *ctx, const phk_host_table *table, const phk_batch *b, int top, int32_t *idx, double *s);
+/* The null of the z-score: mu[M] and sigma[M] (sample standard deviation, ddof = 1) of l[p, r] = S[p, r] / n_p over the
+ * HOST null count rows counts[P][D], n_p the row's total.  Two passes over the product, every column accumulated in row
+ * order 0..P-1: no bit depends on batch_rows (0 = the default).  PHK_ERR_ARG for P < 2 or a null row without counts. */
+int phk_host_null_fit(phk_ctx *ctx, const phk_host_table *table, const uint32_t *counts, uint64_t P, uint64_t D,
+                      uint64_t batch_rows, double *mu, double *sigma);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

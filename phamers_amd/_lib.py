@@ -98,6 +98,11 @@ SIGNATURES = {
     "phk_lik_table_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_lik_score": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u64, c_void_p, c_void_p, c_void_p]),
     "phk_batch_lik_score": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_host_table_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, P(c_void_p)]),
+    "phk_host_table_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_host_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_int, c_u64, c_void_p, c_void_p]),
+    "phk_batch_host_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "phk_host_null_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1008,6 +1013,67 @@ class LikelihoodTable(_Resident):
             c.shape[0], details)
 
 
+HOSTS_MAX_TOP = 16   # PHK_HOSTS_MAX_TOP
+
+
+def check_hosts_top(top, rows):
+    """``top`` as an int, or the ValueError of a ranking of ``rows`` reference rows -- no library needed."""
+    top = int(top)
+    if not 1 <= top <= HOSTS_MAX_TOP:
+        raise ValueError("top = %d is not in 1..%d" % (top, HOSTS_MAX_TOP))
+    if top > rows:
+        raise ValueError("top = %d exceeds the %d reference rows" % (top, rows))
+    return top
+
+
+class HostTable(_Resident):
+    """The resident log table of the likelihood-ranked lookup (phk_host_table): ``log_table`` (M, D) float64 -- multinomial
+    log profiles or Markov log transitions, see hosts.py -- with optional group ids per row."""
+    _destroy = "phk_host_table_destroy"
+
+    def __init__(self, ctx, log_table, groups=None):
+        lt = np.ascontiguousarray(log_table, dtype=np.float64)
+        if lt.ndim != 2 or lt.shape[0] == 0 or lt.shape[1] == 0:
+            raise ValueError("the log table must be 2-D with at least one row, got shape %r" % (lt.shape,))
+        self.ctx, self.M, self.D = ctx, lt.shape[0], lt.shape[1]
+        g = _groups(groups, self.M, "groups")
+        h = ctypes.c_void_p()
+        rc = ctx.lib.phk_host_table_create(ctx.handle, ptr(lt), self.M, self.D, ptr(g), ctypes.byref(h))
+        if rc == PHK_ERR_NAN:
+            raise ValueError(last_error())
+        check_value(rc, nan=False)
+        self.handle = h
+
+    def _rank(self, call, n, top):
+        idx, s = np.empty((n, top), dtype=np.int32), np.empty((n, top), dtype=np.float64)
+        check_value(call(idx, s), nan=False)
+        return idx.astype(np.int64), s
+
+    def rank(self, counts, top, query_groups=None, batch_rows=0):
+        """(indices (N, top) int64, S (N, top) float64) of the uint32 count rows ``counts`` (N, D) on the host
+        (phk_host_rank).  ValueError when ``top`` exceeds the rows a query's group leaves it."""
+        self._open()
+        top = check_hosts_top(top, self.M)
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        if c.ndim != 2 or c.shape[1] != self.D:
+            raise ValueError("the counts must be (N, %d), got shape %r" % (self.D, c.shape))
+        g = _groups(query_groups, c.shape[0], "query_groups")
+        return self._rank(lambda idx, s: self.ctx.lib.phk_host_rank(
+            self.ctx.handle, self.handle, ptr(c), c.shape[0], self.D, ptr(g), top, int(batch_rows), ptr(idx), ptr(s)),
+            c.shape[0], top)
+
+    def null_fit(self, counts, batch_rows=0):
+        """(mu (M,), sigma (M,)) of S / n over the uint32 null count rows ``counts`` (P, D) (phk_host_null_fit)."""
+        self._open()
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        if c.ndim != 2 or c.shape[1] != self.D:
+            raise ValueError("the null counts must be (P, %d), got shape %r" % (self.D, c.shape))
+        mu, sigma = np.empty(self.M, dtype=np.float64), np.empty(self.M, dtype=np.float64)
+        check_value(self.ctx.lib.phk_host_null_fit(self.ctx.handle, self.handle, ptr(c), c.shape[0], self.D, int(batch_rows),
+                                                   ptr(mu), ptr(sigma)), nan=False)
+        return mu, sigma
+
+
 class Batch(_Resident):
     """Device-resident contig batch (phk_batch): counts + row sums in HBM; see include/phamers_hip.h."""
     _destroy = "phk_batch_free"
@@ -1149,6 +1215,15 @@ class Batch(_Resident):
         self._open()
         return table._score(lambda lp, ln, sc: self.ctx.lib.phk_batch_lik_score(
             self.ctx.handle, table.handle, self.handle, ptr(lp), ptr(ln), ptr(sc)), self.n, details)
+
+    def hosts(self, table, top):
+        """(indices (n, top) int64, S (n, top) float64): the ``top`` most likely rows of a ``HostTable`` for every resident
+        count row, by (S descending, index ascending) (phk_batch_host_rank)."""
+        self._open()
+        table._open()
+        top = check_hosts_top(top, table.M)
+        return table._rank(lambda idx, s: self.ctx.lib.phk_batch_host_rank(
+            self.ctx.handle, table.handle, self.handle, top, ptr(idx), ptr(s)), self.n, top)
 
     def neighbors(self, model, k):
         """(distances (n, k), indices (n, k) int64 into the model's vstack(positive, negative)) of the k nearest train rows of

@@ -15,30 +15,11 @@
 // a~_(KC) - E), or when every unmasked row was kept.  (4) Fallback: the other queries are gathered, run through the pair
 // tile against all rows (phk_launch_dist2) and selected in order of (d2, j) by row_select.h (phk_nn_select_kernel).
 #include "gram_tile.h"
+#include "row_list.h"
 #include "row_select.h"
 #include "score_model.h"
 
 #define NN_KMAX 28
-#define NN_NOROW 0x7fffffff   // index of an empty list entry (value +inf): after every real entry
-#define NN_STEP (GT_RT * 16)  // rows per row step of the tile (64)
-
-__device__ __forceinline__ bool nn_less(double a, int32_t ja, double b, int32_t jb) { return a < b || (a == b && ja < jb); }
-
-// (v, j) into the list sorted by (value, index): one pass of compare-exchanges over registers, the displaced entry moves on.
-// A NaN value compares false everywhere and drops out.
-template <int KC>
-__device__ __forceinline__ void nn_insert(double (&lv)[KC], int32_t (&lj)[KC], double v, int32_t j) {
-#pragma unroll
-    for (int i = 0; i < KC; ++i) {
-        const bool lt = nn_less(v, j, lv[i], lj[i]);
-        const double tv = lv[i];
-        const int32_t tj = lj[i];
-        lv[i] = lt ? v : tv;
-        lj[i] = lt ? j : tj;
-        v = lt ? tv : v;
-        j = lt ? tj : j;
-    }
-}
 
 // max_j rn[j] over all rows (masked ones included: the bound only grows), one workgroup
 __global__ __launch_bounds__(256) void phk_nn_rnmax_kernel(const double *__restrict__ rn, uint64_t M, double *__restrict__ out) {

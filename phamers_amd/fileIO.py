@@ -228,6 +228,46 @@ def read_phamer_neighbors(filename):
         return [(c, int(r), i, kind, float(d)) for c, r, i, kind, d in rows]
 
 
+HOSTS_COLUMNS = ("contig_id", "rank", "host_id", "log_likelihood", "per_kmer", "z", "p_value")
+
+
+def save_phamer_hosts(file_name, contig_ids, host_ids, log_likelihood, per_kmer, z, p_value, args=None, slice_rows=65536):
+    """phamer_output/phamer_hosts.csv: the '# ' header block, the column line, then one 'contig_id,rank,host_id,
+    log_likelihood,per_kmer,z,p_value' line per (contig, hit) of hosts.py's ranking: rank from 1, the floats as
+    ``repr(float)``.  Fields are quoted as the csv module does.  ``host_ids`` and the four value arrays are (n, top);
+    written ``slice_rows`` contigs at a time."""
+    import csv
+    header = "PhaMers host prediction file"
+    if args is not None:
+        header = generate_summary(args, header=header)
+    values = [np.asarray(v, dtype=np.float64) for v in (log_likelihood, per_kmer, z, p_value)]
+    n, k = values[0].shape
+    if len(contig_ids) != n or np.shape(host_ids) != (n, k) or any(v.shape != (n, k) for v in values):
+        raise ValueError("%d contig ids, host ids %s and values %s for %s hits"
+                         % (len(contig_ids), np.shape(host_ids), [v.shape for v in values], (n, k)))
+    with open(file_name, 'w', newline='') as f:
+        f.write(_comment_block(header).decode('latin-1'))
+        w = csv.writer(f, lineterminator='\n')
+        w.writerow(HOSTS_COLUMNS)
+        for s in range(0, n, slice_rows):
+            e = min(n, s + slice_rows)
+            cids = [str(c) for c in np.asarray(contig_ids[s:e]).tolist()]
+            hids = np.asarray(host_ids[s:e]).tolist()
+            cols = [v[s:e].tolist() for v in values]
+            w.writerows([cids[i], r + 1, str(hids[i][r])] + [repr(c[i][r]) for c in cols]
+                        for i in range(e - s) for r in range(k))
+
+
+def read_phamer_hosts(filename):
+    """The rows of a host prediction file as (contig_id, rank, host_id, log_likelihood, per_kmer, z, p_value) tuples."""
+    import csv
+    with open(filename, 'r', newline='') as f:
+        rows = csv.reader(line for line in f if not line.startswith('#'))
+        if tuple(next(rows)) != HOSTS_COLUMNS:
+            raise ValueError("%s is not a host prediction file" % filename)
+        return [(c, int(r), h) + tuple(float(v) for v in rest) for c, r, h, *rest in rows]
+
+
 def read_phamer_output(filename):
     """{contig id: score} of a PhaMers score file."""
     with open(filename, 'r') as f:

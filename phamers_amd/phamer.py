@@ -34,6 +34,10 @@ for the others; score_with_scorer is the same call for every method of phamer_sc
 The likelihood method (this project's own: likelihood.py) scores the contigs' integer COUNT rows
 against the reference COUNT rows (``positive_counts`` / ``negative_counts``, which load_data() keeps beside the normalised
 matrices when it is the scoring method); frequencies alone raise ValueError.
+
+``phamer_scorer.predict_hosts`` / ``--hosts K`` (this project's own: hosts.py) ranks the negative
+reference rows by the likelihood of each contig's count row and writes phamer_hosts.csv; it needs the same count rows
+(``keep_reference_counts``) and leaves the scores as they are.
 """
 import argparse
 import logging
@@ -98,6 +102,7 @@ class phamer_scorer(object):
         self.pseudocount = 0.5              # likelihood method (this project's own, likelihood.py): the profiles' pseudocount,
         self.likelihood_per_kmer = False    # and whether a score is divided by its contig's k-mers
         self.positive_counts = self.negative_counts = None   # the reference COUNT rows, which that method scores against
+        self.keep_reference_counts = False  # load_data() keeps them for any scoring method (predict_hosts needs them)
         self.k_clusters_positive = 86      # scripts/phamer.py:80-89 (dbscan method: its k-means fallback, eps, min_samples)
         self.k_clusters_negative = 20
         self.eps = [1, 1]
@@ -163,7 +168,8 @@ class phamer_scorer(object):
         self._load_queries(length_requirement)
 
     def _load_reference(self):
-        if self.scoring_method == 'likelihood':   # the count rows are kept beside the normalised matrices
+        if self.scoring_method == 'likelihood' or self.keep_reference_counts:
+            # the count rows are kept beside the normalised matrices (which are what the other branches make of the files)
             from . import kmer, transform_kmers
             fold = transform_kmers.fold_strands if self.both_strands else (lambda counts: counts)
             self.positive_ids, counts = fileIO.read_feature_file(self.positive_features_file, normalize=False)
@@ -312,6 +318,9 @@ class phamer_scorer(object):
     def get_neighbors_output_filename(self):
         return os.path.join(self.output_directory, "phamer_neighbors.csv")
 
+    def get_hosts_output_filename(self):
+        return os.path.join(self.output_directory, "phamer_hosts.csv")
+
     def get_tsne_output_filename(self):
         """scripts/phamer.py:443-445."""
         return os.path.join(self.output_directory, "tsne_coordinates.csv")
@@ -377,6 +386,47 @@ class phamer_scorer(object):
         self.neighbors_output_filename = self.get_neighbors_output_filename()
         fileIO.save_phamer_neighbors(self.neighbors_output_filename, self.data_ids, ids, idx < self.positive_data.shape[0],
                                      self.neighbor_distances, args=args)
+
+    # ---- host prediction (this project's own: hosts.py) -----------------------------
+    def predict_hosts(self, top=5, model='markov'):
+        """The ``top`` rows of ``negative_counts`` (the bacterial genomes) every contig is most likely to come from, by the
+        likelihood of its count row under each row's ``model`` table (hosts.py), annotated with the z-score and p-value of
+        the per-k-mer log-likelihood under a null fitted on ``positive_counts`` (the phage genomes -- all of them, see
+        hosts.predict).  Sets ``host_indices`` (n, top) into the negative rows, ``host_ids`` (n, top; from
+        ``negative_ids``, or 'negative_<row>' without them), ``host_log_likelihood``, ``host_per_kmer``, ``host_z`` and
+        ``host_p_value``.  On the resident counts when there are any; with ``both_strands`` both sides are the folded rows,
+        as for the likelihood method.  The ValueErrors of likelihood_score_points when count rows are missing."""
+        from . import hosts
+        ref = self.positive_counts, self.negative_counts
+        if any(c is None for c in ref) or any(d is not None and len(d) != len(c)
+                                              for c, d in zip(ref, (self.positive_data, self.negative_data))):
+            raise ValueError("host prediction needs the reference COUNT rows (positive_counts / negative_counts, which "
+                             "load_data() reads from the feature files when keep_reference_counts is set or the scoring "
+                             "method is 'likelihood'): positive_data / negative_data hold frequencies only")
+        if self._batch is None:
+            raise ValueError("host prediction needs the contigs' integer k-mer counts (a counted FASTA file or an "
+                             "integer features file): data_points holds frequencies only")
+        top = _lib.check_hosts_top(top, len(ref[1]))
+        table = _lib.HostTable(_lib.get_context(), hosts._table(ref[1], model, self.pseudocount))
+        try:
+            null = table.null_fit(hosts._count_rows(ref[0], "positive_counts"))
+            idx, S = self._batch.hosts(table, top)
+        finally:
+            table.close()
+        r = hosts._annotate(idx, S, self._batch.row_sums(), null)
+        self.host_indices, self.host_log_likelihood, self.host_per_kmer = r.indices, r.log_likelihood, r.per_kmer
+        self.host_z, self.host_p_value = r.z, r.p_value
+        if self.negative_ids is not None:
+            self.host_ids = np.asarray(self.negative_ids, dtype=object)[idx]
+        else:
+            self.host_ids = "negative_" + idx.astype(str).astype(object)
+        return r
+
+    def make_hosts_file(self, args=None):
+        """phamer_hosts.csv beside phamer_scores.csv: one line per (contig, rank), see fileIO.save_phamer_hosts."""
+        self.hosts_output_filename = self.get_hosts_output_filename()
+        fileIO.save_phamer_hosts(self.hosts_output_filename, self.data_ids, self.host_ids, self.host_log_likelihood,
+                                 self.host_per_kmer, self.host_z, self.host_p_value, args=args)
 
     # ---- scoring ------------------------------------------------------------------------------------------
     def equalize_reference_data(self):
@@ -657,6 +707,13 @@ def main(argv=None):
             ap.error("--neighbors must be in 1..%d (got %d)" % (_lib.NEIGHBORS_MAX_K, args.neighbors))
         if (args.gpus and args.gpus > 1) or world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1":
             ap.error("--neighbors is not sharded: run it on one GPU (without --gpus)")
+    if hasattr(args, "hosts") or hasattr(args, "hosts_model"):
+        if not hasattr(args, "hosts"):
+            ap.error("--hosts_model needs --hosts K")
+        if not 1 <= args.hosts <= _lib.HOSTS_MAX_TOP:
+            ap.error("--hosts must be in 1..%d (got %d)" % (_lib.HOSTS_MAX_TOP, args.hosts))
+        if (args.gpus and args.gpus > 1) or world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1":
+            ap.error("--hosts is not sharded: run it on one GPU (without --gpus)")
     if (hasattr(args, "pseudocount") or hasattr(args, "per_kmer")) and (
             (args.gpus and args.gpus > 1) or world > 1 or os.environ.get("PHAMERS_FORCE_RANK_PATH") == "1"):
         ap.error("--pseudocount / --per_kmer (the likelihood method) are not sharded: run them on one GPU (without --gpus)")
@@ -707,6 +764,13 @@ def _parser():
                                            "by this pseudocount (the scorer's default: 0.5; one GPU only)")),
             (('--per_kmer',), dict(action='store_true', default=argparse.SUPPRESS,
                                    help="Score with the likelihood method, every score divided by its contig's k-mers")),
+            # (no defaults, as --neighbors: the stamped summary of phamer_scores.csv is what a run without them writes)
+            (('--hosts',), dict(type=int, default=argparse.SUPPRESS, metavar='K',
+                                help='Also write phamer_hosts.csv: the K negative reference rows (bacterial genomes) every '
+                                     'contig is most likely to come from, with z-score and p-value under a null fitted on '
+                                     'the positive rows (hosts.py; 1..16; one GPU only)')),
+            (('--hosts_model',), dict(choices=('markov', 'multinomial'), default=argparse.SUPPRESS,
+                                      help="Log table of --hosts (default: markov, a chain of order k - 1 per genome)")),
             (('-v', '--verbose'), dict(action='store_true')),
             (('--debug',), dict(action='store_true')),
             # the rest of the reference's command line (scripts/phamer.py:515-553), so that its launch scripts
@@ -756,6 +820,8 @@ def _run(ap, args):
     scorer.both_strands = args.both_strands
     _apply_k_options(scorer, args)
     _apply_likelihood_options(scorer, args)
+    hosts_top, hosts_model = getattr(args, "hosts", None), getattr(args, "hosts_model", "markov")
+    scorer.keep_reference_counts = hosts_top is not None
     scorer.input_directory, scorer.fasta_file, scorer.features_file = args.input_directory, args.fasta_file, args.features_file
     if args.data_directory:
         scorer.data_directory = args.data_directory
@@ -788,6 +854,9 @@ def _run(ap, args):
         neighbors = getattr(args, "neighbors", None)
         if neighbors is not None:      # the scores file is stamped as a run without the flag stamps it
             args = argparse.Namespace(**{k: v for k, v in vars(args).items() if k != "neighbors"})
+        if hosts_top is not None:
+            hosts_given = {k: v for k, v in vars(args).items() if k in ("hosts", "hosts_model")}
+            args = argparse.Namespace(**{k: v for k, v in vars(args).items() if k not in hosts_given})
         scorer.make_summary_file(args=args)
         lap("scores written")
         if neighbors is not None:
@@ -795,6 +864,11 @@ def _run(ap, args):
             lap("nearest references found")
             scorer.make_neighbors_file(args=argparse.Namespace(neighbors=neighbors, **vars(args)))
             lap("nearest references written")
+        if hosts_top is not None:
+            scorer.predict_hosts(hosts_top, hosts_model)
+            lap("hosts ranked")
+            scorer.make_hosts_file(args=argparse.Namespace(**dict(vars(args), **hosts_given)))
+            lap("hosts written")
     finally:
         scorer.finish_io()
         lap("features cache complete")
