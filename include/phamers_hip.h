@@ -487,6 +487,34 @@ int phk_batch_host_rank(phk_ctx *ctx, const phk_host_table *table, const phk_bat
 int phk_host_null_fit(phk_ctx *ctx, const phk_host_table *table, const uint32_t *counts, uint64_t P, uint64_t D,
                       uint64_t batch_rows, double *mu, double *sigma);
 
+/* ---- track segmentation: a two-state hidden Markov decode (this project's own) ----------------------
+ * Per record r, over its windows t = offsets[r] .. offsets[r + 1] - 1 of the flat evidence x[n] (nats; a tempered
+ * log-likelihood ratio): states 0 = host, 1 = phage, emission e_t = (1, exp(x_t)), transition trans = {A00, A01, A10, A11},
+ * initial distribution init.  Host pointers.  The library never takes a logarithm of a parameter: the caller passes the
+ * probabilities and their logarithms quantised to int64 units of 2^-PHK_SEG_QUANT_BITS nat (qlog_trans, qlog_init).
+ *   posterior[n]   P(state_t = 1 | all x of the record), float64: forward-backward in the probability domain, sums of
+ *                  products of positive numbers rescaled by powers of two only -- no cancellation; error bound in
+ *                  tests/segment_ref.py.  exp(x_t) enters as exp(-|x_t|) on the disfavoured state: no |x_t| overflows, and an
+ *                  underflow to 0 reads as "certain".
+ *   state[n]       the Viterbi path, uint8: the plain left-to-right max-plus recurrence on exact integers -- x_t is
+ *                  quantised to rint(clamp(x_t, -2^15, 2^15) 2^PHK_SEG_QUANT_BITS), so |x_t| beyond 2^15 nats counts as 2^15 --
+ *                  ties to the predecessor with the smaller state, a tie at the final step to the smaller state.  With at most
+ *                  2^31 windows per call no sum leaves int64.
+ *   log_odds[R]    log sum_paths P(path, x): the log evidence against the all-host chain, float64
+ *   path_score[R]  the Viterbi path's integer score (x 2^-PHK_SEG_QUANT_BITS = nats)
+ * A record is cut into tiles of PHK_SEG_TILE windows from its own start and the tiles are carried in tile order: the result
+ * of a record is a function of its x and the parameters alone -- not of the other records, its place among them, or the
+ * launch.  PHK_ERR_ARG, before any launch, for a parameter outside (0, 1), a row of trans or init that does not sum to 1
+ * within 4 ulp, offsets that do not run non-decreasing from 0 to n, n > 2^31; PHK_ERR_NAN for an x that is not finite.
+ * R == 0 or n == 0 is PHK_OK; a record without windows gets log_odds 0 and path_score 0. */
+#define PHK_SEG_TILE 64
+#define PHK_SEG_QUANT_BITS 16
+int phk_segment_decode(phk_ctx *ctx, const double *x, uint64_t n, const uint64_t *offsets, uint64_t R, const double trans[4],
+                       const double init[2], const int64_t qlog_trans[4], const int64_t qlog_init[2], double *posterior,
+                       uint8_t *state, double *log_odds, int64_t *path_score);
+/* tiles one launch of the per-tile kernels covers; beyond it they stride (for tests) */
+uint64_t phk_segment_grid_pass(void);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -103,6 +103,9 @@ SIGNATURES = {
     "phk_host_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_int, c_u64, c_void_p, c_void_p]),
     "phk_batch_host_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "phk_host_null_fit": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
+    "phk_segment_decode": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_segment_grid_pass": (c_u64, []),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1072,6 +1075,32 @@ class HostTable(_Resident):
         check_value(self.ctx.lib.phk_host_null_fit(self.ctx.handle, self.handle, ptr(c), c.shape[0], self.D, int(batch_rows),
                                                    ptr(mu), ptr(sigma)), nan=False)
         return mu, sigma
+
+
+SEG_TILE, SEG_QUANT_BITS = 64, 16   # PHK_SEG_TILE, PHK_SEG_QUANT_BITS
+
+
+def segment_decode(ctx, x, offsets, trans, init, qlog_trans, qlog_init):
+    """(posterior (n,) float64, state (n,) uint8, log_odds (R,) float64, path_score (R,) int64) of the two-state decode
+    of the flat evidence ``x`` (n,) cut into records by ``offsets`` (R + 1,) (phk_segment_decode; segment.py prepares the
+    arguments).  ValueError for the library's PHK_ERR_ARG and for an x that is not finite."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if x.ndim != 1 or off.ndim != 1 or off.shape[0] < 1:
+        raise ValueError("segment_decode: x must be (n,) and offsets (R + 1,)")
+    n, R = x.shape[0], off.shape[0] - 1
+    tr, pi = np.ascontiguousarray(trans, dtype=np.float64).ravel(), np.ascontiguousarray(init, dtype=np.float64).ravel()
+    qt, qp = np.ascontiguousarray(qlog_trans, dtype=np.int64).ravel(), np.ascontiguousarray(qlog_init, dtype=np.int64).ravel()
+    if tr.shape != (4,) or pi.shape != (2,) or qt.shape != (4,) or qp.shape != (2,):
+        raise ValueError("segment_decode: 4 transition and 2 initial parameters")
+    posterior, state = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.uint8)
+    log_odds, path_score = np.empty(R, dtype=np.float64), np.empty(R, dtype=np.int64)
+    rc = ctx.lib.phk_segment_decode(ctx.handle, ptr(x), n, ptr(off), R, ptr(tr), ptr(pi), ptr(qt), ptr(qp), ptr(posterior),
+                                    ptr(state), ptr(log_odds), ptr(path_score))
+    if rc == PHK_ERR_NAN:
+        raise ValueError(last_error())
+    check_value(rc, nan=False)
+    return posterior, state, log_odds, path_score
 
 
 class Batch(_Resident):

@@ -83,6 +83,7 @@ enum PhkSlot {
     WS_NN,          // neighbour lookup: a batch's merged candidate lists and its list of uncertified queries (neighbors.hip)
     WS_NNF,         // ... the gathered rows of the queries that fall back
     WS_NND,         // ... the kept details of a call (phk_neighbors_keep_details)
+    WS_SEG,         // track segmentation: a call's evidence, outputs, tile and record arrays (segment.hip)
     WS_SLOTS
 };
 
