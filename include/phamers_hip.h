@@ -515,6 +515,49 @@ int phk_segment_decode(phk_ctx *ctx, const double *x, uint64_t n, const uint64_t
 /* tiles one launch of the per-tile kernels covers; beyond it they stride (for tests) */
 uint64_t phk_segment_grid_pass(void);
 
+/* ---- fitting the chain's transition probabilities: Baum-Welch (this project's own) ------------------
+ * phk_segment_expect is one E-step of the chain above at (trans, init): per record
+ *   counts_rec[R][6]  xi(0->0), xi(0->1), xi(1->0), xi(1->1), gamma_0(0), gamma_0(1), with
+ *                     xi(i->j) = sum_{t >= 1} P(s_{t-1} = i, s_t = j | x) and gamma_0(s) = P(s_0 = s | x); may be NULL
+ *   log_odds[R]       bit for bit what phk_segment_decode returns; may be NULL
+ * and over the records totals[6] (the column sums of counts_rec) and *log_evidence (the sum of log_odds): up to a term
+ * that depends on no parameter, the log-likelihood of the tracks.  Every step's four terms alpha_{t-1}(i) A_ij e_t(j)
+ * beta_t(j) are normalised by their own sum and added in step order, tile partials in tile order: a record's row is a
+ * function of its x and the parameters alone.  The sums over records follow a tree fixed by the record index: blocks of 256
+ * consecutive rows (a row past the end counts as +0.0), within a block v[i] += v[i + s] for s = 128, 64, .. 1, and the block
+ * results reduced by the same rule until one is left -- a function of (R, the per-record values), not of the launch.  Error
+ * bound: tests/segment_fit_ref.py.  Argument checks and error codes are phk_segment_decode's.  R == 0 or n == 0 is PHK_OK
+ * with zeros; a record without windows contributes nothing, a record of one window only its gamma_0. */
+int phk_segment_expect(phk_ctx *ctx, const double *x, uint64_t n, const uint64_t *offsets, uint64_t R, const double trans[4],
+                       const double init[2], double *counts_rec, double totals[6], double *log_odds, double *log_evidence);
+
+/* phk_segment_fit iterates E-step and M-step from start = {a, b, p_start} (a = A01, b = A10).  x, the offsets and the tile
+ * lists go to the device once; an iteration brings back the six totals and the log evidence.  The M-step, in float64 and in
+ * this order of operations, with c = prior_counts = {c00, c01, c10, c11} (finite, >= 0) and N, G the totals:
+ *   a = (N01 + c01) / ((N00 + c00) + (N01 + c01)),  b = (N10 + c10) / ((N10 + c10) + (N11 + c11)),
+ *   each clamped to [1e-12, 1 - 1e-12] (PHK_SEG_FIT_CLAMPED); a row whose denominator is 0 keeps its parameter
+ *   (PHK_SEG_FIT_NO_TRANSITIONS);  trans = {1 - a, a, b, 1 - b}, init = {1 - p_start, p_start};
+ *   p_start: PHK_SEG_START_FIXED kept; PHK_SEG_START_FREE G1 / (G0 + G1), clamped (kept when G0 + G1 = 0);
+ *   PHK_SEG_START_STATIONARY a / (a + b) of the new a and b, clamped -- for the start parameters too: start[2] is not read.
+ * trace[(max_iter + 1)][PHK_SEG_TRACE_COLS]: row i = a, b, p_start of iterate i, the six totals and the log evidence L_i AT
+ * those parameters; rows 0 .. *n_iter are written (and possibly one more, to be ignored).  The loop stops when
+ * L_i - L_{i-1} <= tol max(1, |L_i|) (PHK_SEG_FIT_CONVERGED) or after max_iter M-steps.  Fixed and free starts are exact EM
+ * for prior_counts = 0: L never falls but by rounding.  The stationary start is a generalised step that may lower L: the loop
+ * stops there too, and the result is the iterate before it.  fitted = row *n_iter's parameters, the largest L of the trace.
+ * tol finite and >= 0, max_iter <= PHK_SEG_FIT_MAX_ITER, else PHK_ERR_ARG; the other checks as phk_segment_expect at the start
+ * parameters.  The tempering of the evidence is not fitted: the evidence grows without bound in it. */
+#define PHK_SEG_TRACE_COLS 10
+#define PHK_SEG_FIT_MAX_ITER 100000u
+#define PHK_SEG_START_FIXED 0
+#define PHK_SEG_START_FREE 1
+#define PHK_SEG_START_STATIONARY 2
+#define PHK_SEG_FIT_CONVERGED 1u
+#define PHK_SEG_FIT_CLAMPED 2u
+#define PHK_SEG_FIT_NO_TRANSITIONS 4u
+int phk_segment_fit(phk_ctx *ctx, const double *x, uint64_t n, const uint64_t *offsets, uint64_t R, const double start[3],
+                    int start_mode, const double prior_counts[4], uint32_t max_iter, double tol, double *trace,
+                    uint32_t *n_iter, uint32_t *status, double fitted[3]);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

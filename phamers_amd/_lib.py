@@ -106,6 +106,10 @@ SIGNATURES = {
     "phk_segment_decode": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_segment_grid_pass": (c_u64, []),
+    "phk_segment_expect": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "phk_segment_fit": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p, c_int, c_void_p, ctypes.c_uint32,
+                                ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1101,6 +1105,59 @@ def segment_decode(ctx, x, offsets, trans, init, qlog_trans, qlog_init):
         raise ValueError(last_error())
     check_value(rc, nan=False)
     return posterior, state, log_odds, path_score
+
+
+SEG_TRACE_COLS, SEG_FIT_MAX_ITER = 10, 100000                        # PHK_SEG_TRACE_COLS, PHK_SEG_FIT_MAX_ITER
+SEG_START_FIXED, SEG_START_FREE, SEG_START_STATIONARY = 0, 1, 2       # PHK_SEG_START_*
+SEG_FIT_CONVERGED, SEG_FIT_CLAMPED, SEG_FIT_NO_TRANSITIONS = 1, 2, 4  # PHK_SEG_FIT_*
+
+
+def _segment_records(who, x, offsets):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if x.ndim != 1 or off.ndim != 1 or off.shape[0] < 1:
+        raise ValueError("%s: x must be (n,) and offsets (R + 1,)" % who)
+    return x, off
+
+
+def _segment_rc(rc):
+    if rc == PHK_ERR_NAN:
+        raise ValueError(last_error())
+    check_value(rc, nan=False)
+
+
+def segment_expect(ctx, x, offsets, trans, init):
+    """(counts_rec (R, 6), totals (6,), log_odds (R,), log_evidence) of one E-step of the chain at ``trans`` (4,) and
+    ``init`` (2,) over the flat evidence ``x`` (n,) cut into records by ``offsets`` (R + 1,) (phk_segment_expect).  A row of
+    counts_rec: xi(0->0), xi(0->1), xi(1->0), xi(1->1), gamma_0(0), gamma_0(1).  ValueError as ``segment_decode``."""
+    x, off = _segment_records("segment_expect", x, offsets)
+    n, R = x.shape[0], off.shape[0] - 1
+    tr, pi = np.ascontiguousarray(trans, dtype=np.float64).ravel(), np.ascontiguousarray(init, dtype=np.float64).ravel()
+    if tr.shape != (4,) or pi.shape != (2,):
+        raise ValueError("segment_expect: 4 transition and 2 initial parameters")
+    counts, totals = np.empty((R, 6), dtype=np.float64), np.empty(6, dtype=np.float64)
+    log_odds, evidence = np.empty(R, dtype=np.float64), ctypes.c_double()
+    _segment_rc(ctx.lib.phk_segment_expect(ctx.handle, ptr(x), n, ptr(off), R, ptr(tr), ptr(pi), ptr(counts), ptr(totals),
+                                           ptr(log_odds), ctypes.byref(evidence)))
+    return counts, totals, log_odds, evidence.value
+
+
+def segment_fit(ctx, x, offsets, start, start_mode, prior_counts, max_iter, tol):
+    """(trace (n_iter + 1, 10), n_iter, status, fitted (3,)) of the Baum-Welch loop from ``start`` = (a, b, p_start)
+    (phk_segment_fit): a trace row is a, b, p_start, the six totals and the log evidence at those parameters; ``status`` is
+    the sum of the SEG_FIT_* bits.  ValueError as ``segment_decode``."""
+    x, off = _segment_records("segment_fit", x, offsets)
+    st, pc = np.ascontiguousarray(start, dtype=np.float64).ravel(), np.ascontiguousarray(prior_counts, dtype=np.float64).ravel()
+    if st.shape != (3,) or pc.shape != (4,):
+        raise ValueError("segment_fit: 3 start parameters and 4 prior counts")
+    if not 0 <= int(max_iter) <= SEG_FIT_MAX_ITER:
+        raise ValueError("segment_fit: max_iter must lie in [0, %d], got %r" % (SEG_FIT_MAX_ITER, max_iter))
+    trace = np.zeros((int(max_iter) + 1, SEG_TRACE_COLS), dtype=np.float64)
+    n_iter, status, fitted = ctypes.c_uint32(), ctypes.c_uint32(), np.empty(3, dtype=np.float64)
+    _segment_rc(ctx.lib.phk_segment_fit(ctx.handle, ptr(x), x.shape[0], ptr(off), off.shape[0] - 1, ptr(st), int(start_mode),
+                                        ptr(pc), int(max_iter), float(tol), ptr(trace), ctypes.byref(n_iter),
+                                        ctypes.byref(status), ptr(fitted)))
+    return trace[:n_iter.value + 1].copy(), int(n_iter.value), int(status.value), fitted
 
 
 class Batch(_Resident):

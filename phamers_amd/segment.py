@@ -19,10 +19,24 @@ posterior is float64 without cancellation, within the bound of tests/segment_ref
     Segmentation.regions(min_windows=1), save_segments(filename, regions)            phage_segments.csv
     python -m phamers_amd.windows ... --segment                                      writes that file beside the other two
 
+The two transition probabilities and the start need not be guessed: ``fit`` chooses them by maximum likelihood from the
+tracks themselves (Baum-Welch).  With e_t = (1, exp x_t) the sum of the records' log_odds is the
+log-likelihood of the tracks under the chain, up to a term no parameter enters; the E-step -- every window's pairwise
+posteriors, summed -- and the sums over the records run on the device, on a track that goes up once.
+
+    expected_counts(scores, owner_or_offsets, p_enter, p_leave, p_start=None, temper=1.0)   -> Expected (one E-step)
+    fit(scores, owner_or_offsets, p_enter, p_leave, p_start='stationary', ...)               -> Fit
+    fit_track(track, mean_region=30000, phage_fraction=0.05, temper=None, ...)               -> Fit
+    segment_track(track, ..., fit=True)                                                      fits, then decodes
+    python -m phamers_amd.windows ... --segment --fit                                        the same; writes segment_fit.csv
+
+``temper`` is NOT fitted, and cannot be: it is a factor on the evidence, not a parameter of the chain, and the evidence
+sum grows without bound in it.
+
 A score is the emission term of such a chain only when it is a log-likelihood ratio: the ``likelihood`` and ``density``
 methods' scores are, the others' are not -- the decode accepts any track and cannot tell.  The configuration the chain is
 meant for is non-overlapping short windows scored by the likelihood method (``-m likelihood -w 500 -s 500 --segment``).
-Not here: fitting a or b, more than two states, boundaries finer than a window, several GPUs.
+Not here: more than two states, one fit per record, boundaries finer than a window, several GPUs.
 """
 import collections
 
@@ -115,6 +129,92 @@ def _decode(x, offsets, trans, init, qlog_trans, qlog_init):
     return Decoded(post, state, lo, ps.astype(np.float64) * 2.0 ** -QUANT_BITS, ps)
 
 
+Expected = collections.namedtuple("Expected", "transitions start log_odds totals log_evidence")
+Expected.__doc__ = """transitions (R, 4) = xi(0->0), xi(0->1), xi(1->0), xi(1->1) per record, start (R, 2) = gamma_0(0),
+gamma_0(1), log_odds (R,), totals (6,) = the sums of the six columns over the records, log_evidence = the sum of log_odds."""
+
+
+def expected_counts(scores, owner_or_offsets, p_enter, p_leave, p_start=None, temper=1.0):
+    """One E-step of the chain of the module docstring, arguments as ``decode``: per record the expected number of each of
+    the four transitions, xi(i->j) = sum_{t >= 1} P(s_{t-1} = i, s_t = j | x), and the posterior of its first window's
+    state; their sums over the records by a tree fixed by the record index (so the totals are a function of the per-record
+    values alone), and the log evidence.  ``log_odds`` is bit for bit ``decode``'s.  -> Expected, computed on the device
+    within the bound of tests/segment_fit_ref.py."""
+    trans, init, _, _ = parameters(p_enter, p_leave, p_start)
+    x = evidence(scores, temper)
+    counts, totals, lo, ev = _lib.segment_expect(_lib.get_context(), x, _offsets(owner_or_offsets, x.shape[0]), trans, init)
+    return Expected(counts[:, :4].copy(), counts[:, 4:].copy(), lo, totals, ev)
+
+
+P_MIN, P_MAX = 1e-12, 1.0 - 1e-12     # what a fitted probability is clamped to
+TRACE_COLUMNS = ("p_enter", "p_leave", "p_start", "n00", "n01", "n10", "n11", "g0", "g1", "log_evidence")
+_START_MODES = {"stationary": _lib.SEG_START_STATIONARY, "free": _lib.SEG_START_FREE}
+
+
+class Fit(object):
+    """What ``fit`` returns: ``p_enter``, ``p_leave``, ``p_start`` (the fitted values); ``trace`` (n_iter + 1, 10), one row
+    per iterate with the columns TRACE_COLUMNS -- the parameters, the six expected-count totals and the log evidence AT
+    those parameters, the last row being the returned values'; ``log_evidence`` (the last row's); ``n_iter``; ``converged``,
+    ``clamped`` (some M-step left [1e-12, 1 - 1e-12] and was put back), ``no_transitions`` (some M-step found a row of the
+    transition matrix without expected counts and kept its parameter); ``temper``.  ``fit_track`` adds ``mean_region`` =
+    step / p_leave and ``phage_fraction`` = a / (a + b), per trace row too (``mean_regions``, ``phage_fractions``)."""
+
+    def __init__(self, trace, n_iter, status, fitted, temper, step=None):
+        self.p_enter, self.p_leave, self.p_start = (float(v) for v in fitted)
+        self.trace, self.n_iter, self.temper = trace, n_iter, temper
+        self.log_evidence = float(trace[-1, 9])
+        self.converged = bool(status & _lib.SEG_FIT_CONVERGED)
+        self.clamped = bool(status & _lib.SEG_FIT_CLAMPED)
+        self.no_transitions = bool(status & _lib.SEG_FIT_NO_TRANSITIONS)
+        self.step = step
+        if step is not None:
+            self.mean_regions = float(step) / trace[:, 1]
+            self.phage_fractions = trace[:, 0] / (trace[:, 0] + trace[:, 1])
+            self.mean_region = float(step) / self.p_leave
+            self.phage_fraction = self.p_enter / (self.p_enter + self.p_leave)
+
+
+def _fit(x, offsets, a, b, p_start, prior_counts, max_iter, tol, temper, step=None):
+    if isinstance(p_start, str):
+        if p_start not in _START_MODES:
+            raise ValueError("p_start must be 'stationary', 'free' or a probability, got %r" % (p_start,))
+        mode, s = _START_MODES[p_start], None
+    else:
+        mode, s = _lib.SEG_START_FIXED, float(p_start)
+    _, init, _, _ = parameters(a, b, s)
+    prior = np.asarray(prior_counts, dtype=np.float64)
+    if prior.shape != (4,) or not (np.isfinite(prior).all() and (prior >= 0).all()):
+        raise ValueError("prior_counts must be four finite pseudo-counts >= 0 (c00, c01, c10, c11), got %r" % (prior_counts,))
+    if int(max_iter) != max_iter or not 0 <= int(max_iter) <= _lib.SEG_FIT_MAX_ITER:
+        raise ValueError("max_iter must be an integer in [0, %d], got %r" % (_lib.SEG_FIT_MAX_ITER, max_iter))
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("tol must be finite and >= 0, got %r" % (tol,))
+    trace, n_iter, status, fitted = _lib.segment_fit(_lib.get_context(), x, offsets, [float(a), float(b), init[1]], mode, prior,
+                                                     int(max_iter), float(tol))
+    return Fit(trace, n_iter, status, fitted, temper, step)
+
+
+def fit(scores, owner_or_offsets, p_enter, p_leave, p_start='stationary', temper=1.0, prior_counts=(0, 0, 0, 0), max_iter=200,
+        tol=1e-8):
+    """Maximum-likelihood ``p_enter``, ``p_leave`` (and start) of the chain for these tracks by Baum-Welch, started at the
+    values given; the records share one chain.  The scores go to the device once; an iteration is one E-step there
+    (``expected_counts``) and the M-step on the host, in float64 and exactly
+
+        a = (N01 + c01) / ((N00 + c00) + (N01 + c01)),   b = (N10 + c10) / ((N10 + c10) + (N11 + c11))
+
+    with N the transition totals and c = ``prior_counts`` (c00, c01, c10, c11: pseudo-counts, a Dirichlet prior's exponents),
+    each clamped to [1e-12, 1 - 1e-12]; a row without expected counts keeps its parameter.  ``p_start``: a float is kept
+    fixed; 'free' starts at the stationary a / (a + b) and re-estimates it as G1 / (G0 + G1) (with one record that tends to 0
+    or 1: meant for many records); 'stationary' ties it to a / (a + b) of every new a and b.  The loop stops when the log
+    evidence L gains no more than ``tol`` max(1, |L|), or after ``max_iter`` M-steps.  A fixed or a free start is exact EM
+    and, without prior counts, L never falls by more than rounding (with them it is L plus the log prior that rises).  The
+    stationary start is a generalised step -- pi depends on a and b, which the M-step ignores -- and L need not be monotone:
+    the loop stops at the first step that lowers L and returns the iterate before it, so the result is always the trace's
+    best.  ``temper`` is not fitted (module docstring).  -> Fit."""
+    x = evidence(scores, temper)
+    return _fit(x, _offsets(owner_or_offsets, x.shape[0]), p_enter, p_leave, p_start, prior_counts, max_iter, tol, float(temper))
+
+
 def default_temper(window, step, kmer_length):
     """min(1, step / (window - k + 1)): overlapping windows repeat the same k-mers window / step times, and tempering the
     evidence by the inverse is the composite-likelihood correction; exactly 1 for windows that do not overlap."""
@@ -126,7 +226,8 @@ class Segmentation(object):
     ``x`` (n,); ``posterior``, ``state`` (n,); ``log_odds``, ``path_score`` (one per record id; 0 for a record without
     windows); and the parameters ``p_enter``, ``p_leave``, ``temper``."""
 
-    def __init__(self, track, x, decoded, p_enter, p_leave, temper):
+    def __init__(self, track, x, decoded, p_enter, p_leave, temper, fit=None):
+        self.fit = fit     # the Fit whose values were decoded with (segment_track(fit=True)), else None
         self.record_ids, self.owner, self.start = list(track.record_ids), track.owner, track.start
         self.window, self.step = track.window, track.step
         self.x, self.posterior, self.state = x, decoded.posterior, decoded.state
@@ -157,12 +258,8 @@ class Segmentation(object):
         return out
 
 
-def segment_track(track, mean_region=30000, phage_fraction=0.05, temper=None, kmer_length=4):
-    """Decodes a ``windows.WindowTrack``: p_leave = step / ``mean_region`` (the mean length of a phage region in bases;
-    must be < 1), p_enter = p_leave * f / (1 - f) with f = ``phage_fraction`` (the stationary share of phage windows), the
-    start distribution stationary.  ``temper=None``: ``default_temper(window, step, kmer_length)``.  The two defaults are
-    modelling choices -- a prophage of tens of kb, a few per cent of a bacterial genome -- not measurements.  The track may
-    come from any method, but only ``likelihood`` and ``density`` scores are log-likelihood ratios.  -> Segmentation."""
+def _track_chain(track, mean_region, phage_fraction, temper, kmer_length):
+    """(a, b, temper, x, offsets) of a track under ``segment_track``'s rules."""
     f = float(phage_fraction)
     if not 0.0 < f < 1.0:
         raise ValueError("phage_fraction must lie inside (0, 1), got %r" % (phage_fraction,))
@@ -173,12 +270,70 @@ def segment_track(track, mean_region=30000, phage_fraction=0.05, temper=None, km
         raise ValueError("mean_region = %r must exceed the step of %d bases" % (mean_region, track.step))
     a = b * f / (1.0 - f)
     t = default_temper(track.window, track.step, kmer_length) if temper is None else float(temper)
-    trans, init, qt, qp = parameters(a, b)
     x = evidence(track.scores, t)
     records = len(track.record_ids)
     off = np.concatenate(([0], np.cumsum(np.bincount(track.owner, minlength=records)))).astype(np.uint64) \
         if len(track.owner) else np.zeros(records + 1, dtype=np.uint64)
-    return Segmentation(track, x, _decode(x, off, trans, init, qt, qp), a, b, t)
+    return a, b, t, x, off
+
+
+def fit_track(track, mean_region=30000, phage_fraction=0.05, temper=None, kmer_length=4, p_start='stationary',
+              prior_counts=(0, 0, 0, 0), max_iter=200, tol=1e-8):
+    """``fit`` on a ``windows.WindowTrack``: ``mean_region`` and ``phage_fraction`` are the starting point, read as
+    ``segment_track`` reads them; the Fit also carries what the fitted chain says of them, ``mean_region`` = step / p_leave
+    and ``phage_fraction`` = a / (a + b).  ``temper`` as ``segment_track``; it is not fitted."""
+    a, b, t, x, off = _track_chain(track, mean_region, phage_fraction, temper, kmer_length)
+    return _fit(x, off, a, b, p_start, prior_counts, max_iter, tol, t, step=track.step)
+
+
+def segment_track(track, mean_region=30000, phage_fraction=0.05, temper=None, kmer_length=4, fit=False, **fit_options):
+    """Decodes a ``windows.WindowTrack``: p_leave = step / ``mean_region`` (the mean length of a phage region in bases;
+    must be < 1), p_enter = p_leave * f / (1 - f) with f = ``phage_fraction`` (the stationary share of phage windows), the
+    start distribution stationary.  ``temper=None``: ``default_temper(window, step, kmer_length)``.  The two defaults are
+    modelling choices -- a prophage of tens of kb, a few per cent of a bacterial genome -- not measurements; ``fit=True``
+    takes them as the starting point of ``fit_track`` (``fit_options``: its p_start, prior_counts, max_iter, tol) and decodes
+    with the fitted p_enter, p_leave and p_start instead (``Segmentation.fit`` keeps the Fit).  The track may come from any
+    method, but only ``likelihood`` and ``density`` scores are log-likelihood ratios.  -> Segmentation."""
+    a, b, t, x, off = _track_chain(track, mean_region, phage_fraction, temper, kmer_length)
+    if not fit:
+        if fit_options:
+            raise TypeError("%s only apply with fit=True" % sorted(fit_options))
+        trans, init, qt, qp = parameters(a, b)
+        return Segmentation(track, x, _decode(x, off, trans, init, qt, qp), a, b, t)
+    fitted = _fit(x, off, a, b, fit_options.pop("p_start", 'stationary'), fit_options.pop("prior_counts", (0, 0, 0, 0)),
+                  fit_options.pop("max_iter", 200), fit_options.pop("tol", 1e-8), t, step=track.step)
+    if fit_options:
+        raise TypeError("unknown fit options %s" % sorted(fit_options))
+    trans, init, qt, qp = parameters(fitted.p_enter, fitted.p_leave, fitted.p_start)
+    return Segmentation(track, x, _decode(x, off, trans, init, qt, qp), fitted.p_enter, fitted.p_leave, t, fit=fitted)
+
+
+FIT_COLUMNS = "iteration,p_enter,p_leave,p_start,mean_region,phage_fraction,log_evidence"
+
+
+def save_fit(filename, fitted, args=None):
+    """``segment_fit.csv`` of a ``fit_track`` result: the '# ' comment header as ``save_segments`` writes it, then one line
+    per trace row -- ``iteration,p_enter,p_leave,p_start,mean_region,phage_fraction,log_evidence``, floats by repr."""
+    from . import fileIO, windows
+    header = "PhaMers segment fit file"
+    if args is not None:
+        header = fileIO.generate_summary(args, header=header).rstrip('\n')
+    rows = ["%d,%r,%r,%r,%r,%r,%r\n" % (i, float(r[0]), float(r[1]), float(r[2]), float(fitted.mean_regions[i]),
+                                      float(fitted.phage_fractions[i]), float(r[9])) for i, r in enumerate(fitted.trace)]
+    windows._write_csv(filename, header, FIT_COLUMNS, rows)
+
+
+def read_fit(filename):
+    """The rows of a file ``save_fit`` wrote: a list of (iteration, p_enter, p_leave, p_start, mean_region, phage_fraction,
+    log_evidence)."""
+    out = []
+    with open(filename, 'r') as f:
+        for line in f:
+            if line.startswith('#') or not line.strip():
+                continue
+            v = line.rstrip('\n').split(',')
+            out.append((int(v[0]),) + tuple(float(t) for t in v[1:]))
+    return out
 
 
 COLUMNS = "record_id,start,end,n_windows,mean_posterior,max_posterior,sum_evidence"

@@ -6,7 +6,8 @@ regions the windows above a threshold merge to.
 
     python -m phamers_amd.windows -in genome.fasta -out DIR -data DATA_DIR [-w 5000 -s 500 -k 4 -m combo -t 0 -min 1]
                                   [--both_strands] [--pseudocount A]
-                                  [--segment [--mean_region N --phage_fraction F --temper T]]
+                                  [--segment [--mean_region N --phage_fraction F --temper T]
+                                             [--fit [--fit_iterations N --fit_tolerance T --fit_start stationary|free]]]
 
 The windows are the rows of ONE device-resident batch (``kmer.count_windows``' kernel: every base goes to the device once,
 whatever the overlap); normalisation and every scoring method then apply to it as to any batch of
@@ -15,7 +16,9 @@ contigs.  With ``both_strands`` the window rows are folded with their reverse co
 tool: the reference scores whole contigs only.  ``method='likelihood'`` scores the window's integer count rows against
 the reference COUNT rows (likelihood.py): windows are the short sequences that method was built
 for.  ``--segment`` decodes the track with a two-state hidden Markov chain on the device (segment.py, DESIGN.md section
-4.22) and writes phage_segments.csv beside the other two files.  Not here: sharding the windows over several GPUs, plots.
+4.22) and writes phage_segments.csv beside the other two files; with ``--fit`` the chain's transition probabilities are first
+fitted to the track itself (Baum-Welch; --mean_region and --phage_fraction are the starting point),
+the decode uses the fitted chain, and segment_fit.csv holds the fit's trace.  Not here: sharding the windows over several GPUs, plots.
 """
 import argparse
 import os
@@ -215,12 +218,20 @@ def _parser():
             (('--mean_region',), dict(type=float, default=30000, help='--segment: mean length of a phage region in bases')),
             (('--phage_fraction',), dict(type=float, default=0.05, help='--segment: stationary share of phage windows')),
             (('--temper',), dict(type=float, default=None,
-                                 help='--segment: factor on the scores (default: min(1, step / (window - k + 1)))'))):
+                                 help='--segment: factor on the scores (default: min(1, step / (window - k + 1)))')),
+            (('--fit',), dict(action='store_true',
+                              help='--segment: fit the transition probabilities to the track (Baum-Welch) from --mean_region '
+                                   'and --phage_fraction, decode with the fitted chain and write segment_fit.csv')),
+            (('--fit_iterations',), dict(type=int, default=200, help='--fit: most M-steps')),
+            (('--fit_tolerance',), dict(type=float, default=1e-8, help='--fit: relative gain of log evidence that ends the fit')),
+            (('--fit_start',), dict(choices=('stationary', 'free'), default='stationary',
+                                    help='--fit: the start distribution, tied to the stationary one or fitted freely'))):
         ap.add_argument(*flags, **kw)
     return ap
 
 
 _SEGMENT_FLAGS = ("segment", "mean_region", "phage_fraction", "temper")
+_FIT_FLAGS = ("fit", "fit_iterations", "fit_tolerance", "fit_start")
 
 
 def _without(args, names):
@@ -231,6 +242,8 @@ def _without(args, names):
 def main(argv=None):
     ap = _parser()
     args = ap.parse_args(argv)
+    if args.fit and not args.segment:
+        ap.error("--fit fits the chain of --segment: give both")
     from . import phamer
     scorer = phamer.phamer_scorer()
     scorer.both_strands = args.both_strands      # (_load_reference folds the reference counts it reads)
@@ -251,16 +264,20 @@ def main(argv=None):
     regions = call_regions(track, threshold=args.threshold, min_windows=args.min_windows)
     os.makedirs(args.output_directory, exist_ok=True)
     # the two existing files are byte for byte what they were: --segment adds nothing to them, and they name the
-    # pseudocount only where it is used
-    shown = _without(args, _SEGMENT_FLAGS + (() if likelihood else ("pseudocount",)))
+    # pseudocount only where it is used; --fit adds nothing to phage_segments.csv unless it is given
+    shown = _without(args, _SEGMENT_FLAGS + _FIT_FLAGS + (() if likelihood else ("pseudocount",)))
     save_track(os.path.join(args.output_directory, "window_scores.csv"), track, args=shown)
     save_regions(os.path.join(args.output_directory, "phage_regions.csv"), regions, args=shown)
     if args.segment:
         from . import segment
+        fit_options = dict(p_start=args.fit_start, max_iter=args.fit_iterations, tol=args.fit_tolerance) if args.fit else {}
         seg = segment.segment_track(track, mean_region=args.mean_region, phage_fraction=args.phage_fraction,
-                                    temper=args.temper, kmer_length=args.kmer_length)
+                                    temper=args.temper, kmer_length=args.kmer_length, fit=args.fit, **fit_options)
+        stamped = args if args.fit else _without(args, _FIT_FLAGS)
         segment.save_segments(os.path.join(args.output_directory, "phage_segments.csv"), seg.regions(args.min_windows),
-                              args=args)
+                              args=stamped)
+        if args.fit:
+            segment.save_fit(os.path.join(args.output_directory, "segment_fit.csv"), seg.fit, args=args)
     return track, regions
 
 
