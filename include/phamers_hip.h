@@ -558,6 +558,41 @@ int phk_segment_fit(phk_ctx *ctx, const double *x, uint64_t n, const uint64_t *o
                     int start_mode, const double prior_counts[4], uint32_t max_iter, double tol, double *trace,
                     uint32_t *n_iter, uint32_t *status, double fitted[3]);
 
+/* ---- mixtures of multinomials on count rows: the E-step (this project's own) -------------------------
+ * K components with HOST log profiles log_profiles[K][D] and log weights log_weights[K] (the library takes no logarithm of a
+ * profile or of a weight), uint32 count rows c_i:
+ *     S[i, k] = sum_j c_i[j] log_profiles[k][j] + log_weights[k]      l_i = logsumexp_k S[i, k]      r[i, k] = exp(S[i, k] - l_i)
+ *     T[k][j] = sum_i r[i, k] c_i[j]        Nk[k] = sum_i r[i, k]        L = sum_i l_i
+ * A log weight of -inf (weight 0) leaves its component out of every row: r = 0, its T row and Nk are exactly 0.  Everything
+ * is float64.  T, Nk and L are reduced in blocks of phk_mix_block_rows() rows anchored at the global row index, the blocks by
+ * the fixed tree of phk_segment_expect: they are a function of (rows, table) alone -- the same bits for any batch_rows, from
+ * host counts or a resident batch, run to run.
+ *
+ * phk_mix_table_create / _update: 1 <= K <= 256 and D >= 1, else PHK_ERR_ARG; a profile entry that is not finite, or a log
+ * weight that is NaN or +inf, is PHK_ERR_NAN; every weight 0 is PHK_ERR_ARG.  _update replaces the values of a table of the
+ * same shape (an EM iteration). */
+typedef struct phk_mix_table phk_mix_table;
+int phk_mix_table_create(phk_ctx *ctx, const double *log_profiles, const double *log_weights, uint64_t K, uint64_t D,
+                         phk_mix_table **out);
+int phk_mix_table_update(phk_ctx *ctx, phk_mix_table *table, const double *log_profiles, const double *log_weights, uint64_t K,
+                         uint64_t D);
+int phk_mix_table_destroy(phk_ctx *ctx, phk_mix_table *table);
+uint64_t phk_mix_block_rows(void);
+/* One E-step over the HOST count rows counts[N][D]: T[K][D], Nk[K], L[1] and, where asked for (NULL = not), per row l_i
+ * (row_ll[N]), the component of the largest r (argmax[N], lowest index on ties) and that r (max_resp[N]).  The N x K matrix
+ * stays on the device.  batch_rows: rows per device batch, 0 = the default (for tests; no result depends on it).
+ * PHK_ERR_ARG when D is not the table's; N == 0 is PHK_OK with zeros. */
+int phk_mix_expect(phk_ctx *ctx, const phk_mix_table *table, const uint32_t *counts, uint64_t N, uint64_t D,
+                   uint64_t batch_rows, double *T, double *Nk, double *L, double *row_ll, int32_t *argmax, double *max_resp);
+/* The same for the resident rows of a batch, read in place. */
+int phk_batch_mix_expect(phk_ctx *ctx, const phk_mix_table *table, const phk_batch *b, uint64_t batch_rows, double *T,
+                         double *Nk, double *L, double *row_ll, int32_t *argmax, double *max_resp);
+/* r itself, resp[N][K], to the host (and row_ll[N] unless NULL): for the caller who asks for it; no fit does. */
+int phk_mix_responsibilities(phk_ctx *ctx, const phk_mix_table *table, const uint32_t *counts, uint64_t N, uint64_t D,
+                             uint64_t batch_rows, double *resp, double *row_ll);
+int phk_batch_mix_responsibilities(phk_ctx *ctx, const phk_mix_table *table, const phk_batch *b, uint64_t batch_rows,
+                                   double *resp, double *row_ll);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -98,6 +98,16 @@ SIGNATURES = {
     "phk_lik_table_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_lik_score": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u64, c_void_p, c_void_p, c_void_p]),
     "phk_batch_lik_score": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_mix_table_create": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, P(c_void_p)]),
+    "phk_mix_table_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_u64]),
+    "phk_mix_table_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_mix_block_rows": (c_u64, []),
+    "phk_mix_expect": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
+    "phk_batch_mix_expect": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "phk_mix_responsibilities": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
+    "phk_batch_mix_responsibilities": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p]),
     "phk_host_table_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, P(c_void_p)]),
     "phk_host_table_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_host_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_int, c_u64, c_void_p, c_void_p]),
@@ -1020,6 +1030,72 @@ class LikelihoodTable(_Resident):
             c.shape[0], details)
 
 
+MIX_MAX_COMPONENTS = 256   # one row chunk of the Gram tile (mixture.hip)
+
+
+class MixtureTable(_Resident):
+    """The resident table of the mixture E-step (phk_mix_table): ``log_profiles`` (K, D) float64 and ``log_weights`` (K,),
+    both made on the host; a log weight of -inf switches its component off.  ValueError for a value the library refuses."""
+    _destroy = "phk_mix_table_destroy"
+
+    def __init__(self, ctx, log_profiles, log_weights):
+        lp, lw = self._arrays(log_profiles, log_weights)
+        self.ctx, self.K, self.D = ctx, lp.shape[0], lp.shape[1]
+        h = ctypes.c_void_p()
+        self._rc(ctx.lib.phk_mix_table_create(ctx.handle, ptr(lp), ptr(lw), self.K, self.D, ctypes.byref(h)))
+        self.handle = h
+
+    @staticmethod
+    def _arrays(log_profiles, log_weights):
+        lp = np.ascontiguousarray(log_profiles, dtype=np.float64)
+        lw = np.ascontiguousarray(log_weights, dtype=np.float64)
+        if lp.ndim != 2 or lw.shape != (lp.shape[0],):
+            raise ValueError("log_profiles must be (K, D) and log_weights (K,)")
+        return lp, lw
+
+    @staticmethod
+    def _rc(rc):
+        if rc == PHK_ERR_NAN:
+            raise ValueError(last_error())
+        check_value(rc, nan=False)
+
+    def update(self, log_profiles, log_weights):
+        """New values for a table of the same shape (phk_mix_table_update)."""
+        self._open()
+        lp, lw = self._arrays(log_profiles, log_weights)
+        self._rc(self.ctx.lib.phk_mix_table_update(self.ctx.handle, self.handle, ptr(lp), ptr(lw), lp.shape[0], lp.shape[1]))
+
+    def _expect(self, call, n, rows):
+        T, Nk, L = np.zeros((self.K, self.D)), np.zeros(self.K), np.zeros(1)
+        ll = np.zeros(n) if rows else None
+        am = np.zeros(n, dtype=np.int32) if rows else None
+        mr = np.zeros(n) if rows else None
+        check_value(call(ptr(T), ptr(Nk), ptr(L), ptr(ll), ptr(am), ptr(mr)), nan=False)
+        return (T, Nk, float(L[0])) + ((ll, am, mr) if rows else ())
+
+    def _counts(self, counts):
+        self._open()
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        if c.ndim != 2 or c.shape[1] != self.D:
+            raise ValueError("the counts must be (N, %d), got shape %r" % (self.D, c.shape))
+        return c
+
+    def expect(self, counts, batch_rows=0, rows=False):
+        """One E-step over the uint32 count rows ``counts`` (N, D) on the host (phk_mix_expect): (T (K, D), Nk (K,), L), and
+        with ``rows`` also (row_ll (N,), argmax (N,) int32, max_resp (N,))."""
+        c = self._counts(counts)
+        return self._expect(lambda *o: self.ctx.lib.phk_mix_expect(
+            self.ctx.handle, self.handle, ptr(c), c.shape[0], self.D, int(batch_rows), *o), c.shape[0], rows)
+
+    def responsibilities(self, counts, batch_rows=0):
+        """(r (N, K), row_ll (N,)) of host count rows (phk_mix_responsibilities): the one call that brings N x K back."""
+        c = self._counts(counts)
+        r, ll = np.zeros((c.shape[0], self.K)), np.zeros(c.shape[0])
+        check_value(self.ctx.lib.phk_mix_responsibilities(self.ctx.handle, self.handle, ptr(c), c.shape[0], self.D,
+                                                          int(batch_rows), ptr(r), ptr(ll)), nan=False)
+        return r, ll
+
+
 HOSTS_MAX_TOP = 16   # PHK_HOSTS_MAX_TOP
 
 
@@ -1301,6 +1377,23 @@ class Batch(_Resident):
         self._open()
         return table._score(lambda lp, ln, sc: self.ctx.lib.phk_batch_lik_score(
             self.ctx.handle, table.handle, self.handle, ptr(lp), ptr(ln), ptr(sc)), self.n, details)
+
+    def mixture_expect(self, table, batch_rows=0, rows=False):
+        """One E-step of a ``MixtureTable`` over the resident count rows (phk_batch_mix_expect): (T, Nk, L), and with ``rows``
+        also (row_ll, argmax, max_resp); see ``MixtureTable.expect``."""
+        self._open()
+        table._open()
+        return table._expect(lambda *o: self.ctx.lib.phk_batch_mix_expect(
+            self.ctx.handle, table.handle, self.handle, int(batch_rows), *o), self.n, rows)
+
+    def mixture_responsibilities(self, table, batch_rows=0):
+        """(r (n, K), row_ll (n,)) of the resident count rows (phk_batch_mix_responsibilities)."""
+        self._open()
+        table._open()
+        r, ll = np.zeros((self.n, table.K)), np.zeros(self.n)
+        check_value(self.ctx.lib.phk_batch_mix_responsibilities(self.ctx.handle, table.handle, self.handle, int(batch_rows),
+                                                                ptr(r), ptr(ll)), nan=False)
+        return r, ll
 
     def hosts(self, table, top):
         """(indices (n, top) int64, S (n, top) float64): the ``top`` most likely rows of a ``HostTable`` for every resident

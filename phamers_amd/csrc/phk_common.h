@@ -84,6 +84,7 @@ enum PhkSlot {
     WS_NNF,         // ... the gathered rows of the queries that fall back
     WS_NND,         // ... the kept details of a call (phk_neighbors_keep_details)
     WS_SEG,         // track segmentation: a call's evidence, outputs, tile and record arrays (segment.hip)
+    WS_MIX,         // mixture E-step: a batch's responsibilities, the row outputs, the blocks' partial vectors (mixture.hip)
     WS_SLOTS
 };
 
