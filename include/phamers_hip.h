@@ -593,6 +593,31 @@ int phk_mix_responsibilities(phk_ctx *ctx, const phk_mix_table *table, const uin
 int phk_batch_mix_responsibilities(phk_ctx *ctx, const phk_mix_table *table, const phk_batch *b, uint64_t batch_rows,
                                    double *resp, double *row_ll);
 
+/* ---- many mixture E-steps in one call ---------------------------------------------------------------
+ * A sweep object keeps count rows [N][D] (uploaded from the host, or a resident batch's rows, read where they lie: the batch
+ * must outlive the sweep) and n_sets row sets: set s is the strictly ascending row indices set_rows[set_offsets[s] ..
+ * set_offsets[s + 1]), gathered once into rows of its own (a set of all N rows is the source itself).  PHK_ERR_ARG for an empty
+ * set, an index >= N or not ascending, N == 0 or N >= 2^32.
+ *
+ * phk_mix_sweep_step runs n_jobs jobs; job j is (row set job_set[j], K_j = job_K[j] components, 1 <= K_j <= 256).  The jobs'
+ * log profiles [K_j][D] lie one after another in log_profiles, their log weights [K_j] one after another in log_weights.
+ * expect != 0: out receives per job T[K_j][D], Nk[K_j] and L (K_j D + K_j + 1 doubles), job after job.  rows != 0: after
+ * those (or, with expect == 0, alone) the row log-likelihoods l_i of every job's set, job after job.  Every job's values are
+ * the bits phk_mix_expect returns for that job's rows and table alone: the jobs are processed in groups whose device buffers
+ * stay within budget_bytes (0 = the default; a job larger than the budget forms a group of its own) and no result depends
+ * on the grouping, the order of the jobs or the other jobs of the call.  Two launches and the fold levels per group.
+ * n_jobs == 0 is PHK_OK with nothing launched.  PHK_ERR_NAN, naming the job, for a profile entry that is not finite or a log
+ * weight that is NaN or +inf; PHK_ERR_ARG for a job whose weights are all 0. */
+typedef struct phk_mix_sweep phk_mix_sweep;
+int phk_mix_sweep_create(phk_ctx *ctx, const uint32_t *counts, uint64_t N, uint64_t D, const uint32_t *set_rows,
+                         const uint64_t *set_offsets, uint64_t n_sets, phk_mix_sweep **out);
+int phk_batch_mix_sweep_create(phk_ctx *ctx, const phk_batch *b, const uint32_t *set_rows, const uint64_t *set_offsets,
+                               uint64_t n_sets, phk_mix_sweep **out);
+int phk_mix_sweep_step(phk_ctx *ctx, const phk_mix_sweep *sweep, const uint32_t *job_set, const uint32_t *job_K,
+                       uint64_t n_jobs, const double *log_profiles, const double *log_weights, int expect, int rows,
+                       uint64_t budget_bytes, double *out);
+int phk_mix_sweep_destroy(phk_ctx *ctx, phk_mix_sweep *sweep);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -108,6 +108,11 @@ SIGNATURES = {
                                      c_void_p]),
     "phk_mix_responsibilities": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_u64, c_void_p, c_void_p]),
     "phk_batch_mix_responsibilities": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p]),
+    "phk_mix_sweep_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u64, P(c_void_p)]),
+    "phk_batch_mix_sweep_create": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, P(c_void_p)]),
+    "phk_mix_sweep_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_int, c_int, c_u64,
+                                   c_void_p]),
+    "phk_mix_sweep_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_host_table_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, P(c_void_p)]),
     "phk_host_table_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_host_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_int, c_u64, c_void_p, c_void_p]),
@@ -1094,6 +1099,79 @@ class MixtureTable(_Resident):
         check_value(self.ctx.lib.phk_mix_responsibilities(self.ctx.handle, self.handle, ptr(c), c.shape[0], self.D,
                                                           int(batch_rows), ptr(r), ptr(ll)), nan=False)
         return r, ll
+
+
+class MixtureSweep(_Resident):
+    """Count rows and row sets resident for many mixture E-steps per call (phk_mix_sweep).
+    ``counts_or_batch``: uint32 count rows (N, D) on the host, or a ``Batch`` (kept alive here, read where it lies);
+    ``row_sets``: strictly ascending row indices per set, none empty.  ValueError for what the library refuses."""
+    _destroy = "phk_mix_sweep_destroy"
+
+    def __init__(self, ctx, counts_or_batch, row_sets):
+        sets = [np.ascontiguousarray(s, dtype=np.int64).ravel() for s in row_sets]
+        if isinstance(counts_or_batch, Batch):
+            counts_or_batch._open()
+            self.source, c, self.N, self.D = counts_or_batch, None, counts_or_batch.n, counts_or_batch.D
+        else:
+            c = np.ascontiguousarray(counts_or_batch, dtype=np.uint32)
+            if c.ndim != 2:
+                raise ValueError("the counts must be (N, D), got shape %r" % (c.shape,))
+            self.source, (self.N, self.D) = None, c.shape
+        for i, s in enumerate(sets):
+            if s.size and (s.min() < 0 or s.max() >= self.N):
+                raise ValueError("row set %d holds an index outside 0 .. %d" % (i, self.N - 1))
+        self.ctx, self.sizes = ctx, [int(s.size) for s in sets]
+        offsets = np.zeros(len(sets) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum(self.sizes, dtype=np.uint64)
+        flat = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), dtype=np.uint32)
+        flat = flat if flat.size else np.zeros(1, dtype=np.uint32)
+        h = ctypes.c_void_p()
+        if c is None:
+            rc = ctx.lib.phk_batch_mix_sweep_create(ctx.handle, self.source.handle, ptr(flat), ptr(offsets), len(sets),
+                                                    ctypes.byref(h))
+        else:
+            rc = ctx.lib.phk_mix_sweep_create(ctx.handle, ptr(c), self.N, self.D, ptr(flat), ptr(offsets), len(sets),
+                                              ctypes.byref(h))
+        MixtureTable._rc(rc)
+        self.handle = h
+
+    def step(self, jobs, rows=False, _budget_bytes=0, expect=True):
+        """One device call over ``jobs``, a list of (row set, log_profiles (K, D), log_weights (K,)): per job the tuple
+        (T (K, D), Nk (K,), L, l) -- l (n_set,) the rows' log-likelihoods with ``rows``, else None; ``expect=False``
+        (evaluation: needs ``rows``) leaves T, Nk and L None.  Every job's values are the bits of ``MixtureTable.expect`` on
+        that job's rows alone.  ``_budget_bytes`` (device bytes per group of jobs) is for the tests: no result depends on it."""
+        self._open()
+        if not (expect or rows):
+            raise ValueError("step: expect=False needs rows=True")
+        jobs = [(int(s),) + MixtureTable._arrays(lp, lw) for s, lp, lw in jobs]
+        if not jobs:
+            return []
+        for j, (s, lp, lw) in enumerate(jobs):
+            if not 0 <= s < len(self.sizes):
+                raise ValueError("job %d names row set %d of %d" % (j, s, len(self.sizes)))
+            if lp.shape[1] != self.D or not 1 <= lp.shape[0] <= MIX_MAX_COMPONENTS:
+                raise ValueError("job %d: log_profiles must be (1 to %d, %d), got %r" % (j, MIX_MAX_COMPONENTS, self.D, lp.shape))
+        sets = np.array([j[0] for j in jobs], dtype=np.uint32)
+        Ks = np.array([j[1].shape[0] for j in jobs], dtype=np.uint32)
+        logp = np.ascontiguousarray(np.concatenate([j[1].ravel() for j in jobs]))
+        logw = np.ascontiguousarray(np.concatenate([j[2] for j in jobs]))
+        E = [int(k) * self.D + int(k) + 1 for k in Ks] if expect else [0] * len(jobs)
+        n = [self.sizes[s] for s in sets] if rows else [0] * len(jobs)
+        out = np.zeros(sum(E) + sum(n))
+        MixtureTable._rc(self.ctx.lib.phk_mix_sweep_step(self.ctx.handle, self.handle, ptr(sets), ptr(Ks), len(jobs), ptr(logp),
+                                                        ptr(logw), int(bool(expect)), int(bool(rows)), int(_budget_bytes),
+                                                        ptr(out)))
+        got, at, row_at = [], 0, sum(E)
+        for j, K in enumerate(int(k) for k in Ks):
+            T = Nk = L = l = None
+            if expect:
+                T, Nk, L = out[at:at + K * self.D].reshape(K, self.D), out[at + K * self.D:at + E[j] - 1], float(out[at + E[j] - 1])
+                at += E[j]
+            if rows:
+                l = out[row_at:row_at + n[j]]
+                row_at += n[j]
+            got.append((T, Nk, L, l))
+        return got
 
 
 HOSTS_MAX_TOP = 16   # PHK_HOSTS_MAX_TOP

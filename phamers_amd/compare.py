@@ -256,6 +256,11 @@ def density_cells(log_densities):
     return np.array([up[a] - un[b] for a in range(len(up)) for b in range(len(un))], dtype=np.float64)
 
 
+def mixture_cells(result):
+    """(scores (Ks, n), n_pos) from a ``mixture.cross_validate``: the held-out scores l_+ - l_- of every K, positives first."""
+    return np.asarray(result.scores, dtype=np.float64), int(result.n_pos)
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------
 def save_cells(filename, k_neighbors, k_clusters, table, args=None):
     """One 'k_neighbors,k_clusters,<COLUMNS>' row per cell (the two k as integers, the floats as ``repr`` prints them)

@@ -21,6 +21,14 @@ keep their start order.
     score(query_counts, positive_mixture, negative_mixture)      l_+ - l_-, the compressed likelihood.score
     load(path)                                                   a Mixture saved with Mixture.save
     python -m phamers_amd.mixture -in FEATURES|FASTA -K n -out DIR
+
+Many fits side by side (mixture_sweep.hip): the rows go up once with their row sets, every
+(K, start, fold) cell advances one EM iteration per device call, and each cell is bit for bit what ``fit`` gives alone.
+
+    sweep(counts_or_batch, n_components, folds, ...)             a MixtureSweep: every cell, held-out evidence and BIC per K
+    cross_validate(positive_counts, negative_counts, n_components, folds, ...)
+                                                                 held-out l_+ - l_- per K (compare.mixture_cells), AUC, accuracy
+    python -m phamers_amd.mixture_grid                           the two as tables per K
 """
 import collections
 import os
@@ -273,6 +281,284 @@ def score(query_counts, positive_mixture, negative_mixture, per_kmer=False):
     q = _count_rows(query_counts, "query_counts")
     s = positive_mixture.log_likelihood(q) - negative_mixture.log_likelihood(q)
     return _per_kmer(s, q) if per_kmer else s
+
+
+# ---- many fits side by side ------------------------------------------------------------------------
+def _sweep_device(counts_or_batch, row_sets):
+    """The device half of a sweep: the rows and their row sets resident, ``step(jobs, rows, _budget_bytes, expect)`` and
+    ``close()`` (the tests put the statement in its place)."""
+    return _lib.MixtureSweep(_lib.get_context(), counts_or_batch, row_sets)
+
+
+def _evaluate(positive_scores, negative_scores):
+    """(ROC area, accuracy at threshold 0) of a scoring, on the device (the tests put NumPy in its place)."""
+    from .likelihood import evaluate
+    return evaluate(positive_scores, negative_scores)
+
+
+class _SetRows(object):
+    """What ``start`` asks of an E-step object, for one row set of host counts."""
+
+    def __init__(self, host, index):
+        self.host, self.index, self.n, self.D = host, index, len(index), host.shape[1]
+
+    def rows(self, index):
+        return self.host[self.index[index]]
+
+
+def _host_rows(counts_or_batch):
+    if isinstance(counts_or_batch, _lib.Batch):
+        return counts_or_batch.counts_u32()
+    return _count_rows(counts_or_batch, "counts")
+
+
+def _sweep_arguments(n_components, n_init, max_iter, tol, pseudocount):
+    a = _pseudocount(pseudocount)
+    Ks = [_components(K) for K in np.atleast_1d(np.asarray(n_components)).tolist()]
+    if not Ks or len(set(Ks)) != len(Ks):
+        raise ValueError("n_components must be a list of distinct component counts")
+    n_init, max_iter, tol = int(n_init), int(max_iter), float(tol)
+    if n_init < 1 or max_iter < 0 or not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("n_init >= 1, max_iter >= 0 and a finite tol >= 0 are required")
+    return a, Ks, n_init, max_iter, tol
+
+
+def _lockstep(dev, host, sets, cells, a, max_iter, tol):
+    """``_em`` for every cell (row set, K, seed) at once: one ``dev.step`` over the cells still running per iteration, then
+    ``m_step`` and ``_em``'s stopping rule per cell; a cell that stops leaves the job list.  A list of ``Fitted`` whose T
+    is sum_j T[k, j]."""
+    state = []
+    for s, K, seed in cells:
+        logp, w = start(_SetRows(host, sets[s]), K, a, None, seed)
+        state.append(dict(set=s, logp=logp, w=w, trace=[], F_prev=None, done=None))
+    running = list(range(len(cells)))
+    for it in range(max_iter + 1):
+        if not running:
+            break
+        out = dev.step([(state[c]["set"], state[c]["logp"], log_weights(state[c]["w"])) for c in running])
+        still = []
+        for c, (T, Nk, L, _) in zip(running, out):
+            st = state[c]
+            F = evidence(L, st["logp"], a)
+            st["trace"].append((L, F, float(st["w"].min()), int((st["w"] == 0).sum())))
+            converged = st["F_prev"] is not None and F - st["F_prev"] <= tol * max(1.0, abs(F))
+            if converged or it == max_iter:
+                trace = np.array(st["trace"], dtype=np.float64).reshape(-1, len(TRACE_COLUMNS))
+                st["done"] = Fitted(st["logp"], st["w"], trace, len(trace) - 1, bool(converged), T.sum(axis=1))
+                continue
+            st["F_prev"] = F
+            st["logp"], st["w"] = m_step(T, Nk, a)
+            still.append(c)
+        running = still
+    return [st["done"] for st in state]
+
+
+def _best_start(fits):
+    """The index of the largest final evidence F, the lowest on ties (``fit``'s rule)."""
+    best = 0
+    for i in range(1, len(fits)):
+        if fits[i].trace[-1, 1] > fits[best].trace[-1, 1]:
+            best = i
+    return best
+
+
+def _as_mixture(fitted, a):
+    return Mixture(fitted.log_profiles, fitted.weights, a, fitted.n_iter, fitted.converged, fitted.trace, fitted.T)
+
+
+def _bic(fitted, n_rows):
+    """-2 L + (live (D - 1) + live - 1) ln N of a fit on ``n_rows`` rows; live: the components that are not dead."""
+    live = int((fitted.weights != 0).sum())
+    return -2.0 * float(fitted.trace[-1, 0]) + (live * (fitted.log_profiles.shape[1] - 1) + live - 1) * float(np.log(n_rows))
+
+
+class MixtureSweep(object):
+    """What ``sweep`` returns.  ``n_components`` (the K values), ``n_init``, ``n_folds``, ``fold_of`` (N,); over (K, init,
+    fold) with the all-rows fit as the last fold: ``F``, ``L`` (final evidence and log-likelihood of the training rows),
+    ``n_iter``, ``converged``, ``dead`` (components of weight 0); ``held_out_log_likelihood`` (K, N), NaN where a row is
+    never held out; ``held_out_per_kmer`` (K,): sum l_i / sum k-mers over the held-out rows; ``bic`` (K,)."""
+
+    def __init__(self, Ks, n_init, n_folds, fold_of, fits, pseudocount):
+        self.n_components, self.n_init, self.n_folds, self.fold_of = list(Ks), n_init, n_folds, fold_of
+        self.pseudocount, self._fits = pseudocount, fits            # fits[a][i][f]: a Fitted
+        shape = (len(Ks), n_init, n_folds + 1)
+        cell = lambda get, dtype: np.array([[[get(fits[a][i][f]) for f in range(shape[2])] for i in range(shape[1])]
+                                            for a in range(shape[0])], dtype=dtype).reshape(shape)
+        self.F, self.L = cell(lambda g: g.trace[-1, 1], np.float64), cell(lambda g: g.trace[-1, 0], np.float64)
+        self.n_iter, self.converged = cell(lambda g: g.n_iter, np.int64), cell(lambda g: g.converged, bool)
+        self.dead = cell(lambda g: int((g.weights == 0).sum()), np.int64)
+
+    def _k(self, K):
+        if int(K) not in self.n_components:
+            raise ValueError("K = %r is not one of %r" % (K, self.n_components))
+        return self.n_components.index(int(K))
+
+    def _fold(self, fold):
+        if fold is not None and not 0 <= int(fold) < self.n_folds:
+            raise ValueError("fold must be 0 to %d, or None" % (self.n_folds - 1))
+        return self.n_folds if fold is None else int(fold)
+
+    def best_init(self, K, fold=None):
+        """The start ``mixture(K, None, fold)`` returns: the largest training F, the lowest seed on ties."""
+        f = self._fold(fold)
+        return _best_start([self._fits[self._k(K)][i][f] for i in range(self.n_init)])
+
+    def mixture(self, K, init=None, fold=None):
+        """The ``Mixture`` of cell (K, init, fold): ``init=None`` the best start, ``fold=None`` the fit on all rows."""
+        f = self._fold(fold)
+        i = self.best_init(K, fold) if init is None else int(init)
+        if not 0 <= i < self.n_init:
+            raise ValueError("init must be 0 to %d, or None" % (self.n_init - 1))
+        return _as_mixture(self._fits[self._k(K)][i][f], self.pseudocount)
+
+    def best(self, criterion='held_out'):
+        """The K of the largest held-out evidence per k-mer, or of the smallest BIC (the first such K on a tie)."""
+        if criterion == 'held_out':
+            if self.n_folds == 0:
+                raise ValueError("held-out evidence needs folds")
+            return self.n_components[int(np.argmax(self.held_out_per_kmer))]
+        if criterion == 'bic':
+            return self.n_components[int(np.argmin(self.bic))]
+        raise ValueError("criterion must be 'held_out' or 'bic'")
+
+    def table(self):
+        """One dict per K: K, held_out_per_kmer, bic, mean_iterations (over every cell of the K), dead (components of weight
+        0 in the all-rows best start)."""
+        return [dict(K=K, held_out_per_kmer=float(self.held_out_per_kmer[a]), bic=float(self.bic[a]),
+                     mean_iterations=float(self.n_iter[a].mean()), dead=int(self.dead[a, self.best_init(K), self.n_folds]))
+                for a, K in enumerate(self.n_components)]
+
+
+def _fold_sets(fold_of, n_folds, offset=0):
+    """(training rows, held-out rows) per fold, as ascending row indices shifted by ``offset``."""
+    return ([offset + np.flatnonzero(fold_of != f) for f in range(n_folds)],
+            [offset + np.flatnonzero(fold_of == f) for f in range(n_folds)])
+
+
+def _check_training(Ks, sets):
+    smallest = min(len(s) for s in sets)
+    if max(Ks) > smallest:
+        raise ValueError("n_components = %d exceeds the %d rows of the smallest training set" % (max(Ks), smallest))
+
+
+def sweep(counts_or_batch, n_components, folds=0, fold_seed=None, seed=0, n_init=1, pseudocount=0.5, max_iter=100, tol=1e-6,
+          groups=None):
+    """Every cell (K, start i, fold f) of a grid fitted in lock step: cell (K, i, f) is ``fit(rows outside fold f, K,
+    seed=seed + i, ...)`` field by field, and every K also has the fit on all rows.  The fold of row i is ``groups[i]`` (an
+    integer >= 0, or -1 for a row that is never held out), else cross_validate.FoldPlan(N, 0, folds, fold_seed).positive;
+    ``folds=0`` without ``groups``: no folds.  One device call per EM iteration over the cells still running, one more for
+    the held-out rows under every fold's best start.  A ``MixtureSweep``.  ValueError for K outside 1..256 or above the
+    smallest training set, ``folds`` of 1 or above N, frequencies, and what ``fit`` refuses."""
+    a, Ks, n_init, max_iter, tol = _sweep_arguments(n_components, n_init, max_iter, tol, pseudocount)
+    host = _host_rows(counts_or_batch)
+    N = len(host)
+    if groups is not None:
+        fold_of = np.asarray(groups)
+        if fold_of.shape != (N,) or not np.issubdtype(fold_of.dtype, np.integer) or fold_of.min() < -1:
+            raise ValueError("groups: one integer >= -1 per row (%d)" % N)
+        fold_of = fold_of.astype(np.int64)
+        n_folds = int(fold_of.max()) + 1
+        if n_folds and np.bincount(fold_of[fold_of >= 0], minlength=n_folds).min() == 0:
+            raise ValueError("groups: every fold 0 .. %d needs a row" % (n_folds - 1))
+    else:
+        n_folds = int(folds)
+        if n_folds == 1 or n_folds < 0 or n_folds > N:
+            raise ValueError("folds must be 0 or 2 to the %d rows, got %r" % (N, folds))
+        from .cross_validate import FoldPlan
+        fold_of = FoldPlan(N, 0, n_folds, fold_seed).positive.astype(np.int64) if n_folds else np.full(N, -1, dtype=np.int64)
+    if N == 0:
+        raise ValueError("n_components = %d exceeds the 0 rows" % max(Ks))
+    train, held = _fold_sets(fold_of, n_folds)
+    sets = train + [np.arange(N)] + held               # set f: fold f's training rows; n_folds: all rows; then the held-out rows
+    _check_training(Ks, sets[:n_folds + 1])
+    cells = [(f, K, int(seed) + i) for K in Ks for i in range(n_init) for f in range(n_folds + 1)]
+    dev = _sweep_device(counts_or_batch if isinstance(counts_or_batch, _lib.Batch) else host, sets)
+    try:
+        done = _lockstep(dev, host, sets, cells, a, max_iter, tol)
+        fits = [[[done[(b * n_init + i) * (n_folds + 1) + f] for f in range(n_folds + 1)] for i in range(n_init)]
+                for b in range(len(Ks))]
+        out = MixtureSweep(Ks, n_init, n_folds, fold_of, fits, a)
+        out.held_out_log_likelihood = np.full((len(Ks), N), np.nan)
+        jobs, where = [], []
+        for b, K in enumerate(Ks):
+            for f in range(n_folds):
+                g = fits[b][out.best_init(K, f)][f]
+                jobs.append((n_folds + 1 + f, g.log_profiles, log_weights(g.weights)))
+                where.append((b, held[f]))
+        for (b, index), got in zip(where, dev.step(jobs, rows=True, expect=False) if jobs else []):
+            out.held_out_log_likelihood[b, index] = got[3]
+    finally:
+        dev.close()
+    kmers = float(host[fold_of >= 0].sum(dtype=np.uint64))
+    out.held_out_per_kmer = np.nansum(out.held_out_log_likelihood, axis=1) / kmers if n_folds else np.full(len(Ks), np.nan)
+    out.bic = np.array([_bic(fits[b][out.best_init(K)][n_folds], N) for b, K in enumerate(Ks)])
+    return out
+
+
+CrossValidated = collections.namedtuple(
+    "CrossValidated", "n_components n_pos scores auc accuracy held_out_per_kmer_positive held_out_per_kmer_negative "
+                      "bic_positive bic_negative mean_iterations dead")
+
+
+def cross_validate(positive_counts, negative_counts, n_components, folds, seed=None, fit_seed=0, n_init=1, pseudocount=0.5,
+                   max_iter=100, tol=1e-6, bic=False):
+    """Held-out scores l_+ - l_- of every row per K, under the two mixtures fitted to its fold's training rows: the split
+    is cross_validate.FoldPlan(n_pos, n_neg, folds, seed), both classes' training sets and the joint held-out sets are row
+    sets of one sweep object over vstack(positive, negative), and all 2 folds len(Ks) n_init fits run in lock step (start
+    i of a fit has seed fit_seed + i; the best start is ``fit``'s).  Row K of ``scores`` (len(Ks), n_pos + n_neg),
+    positives first, equals the loop of ``fit`` on each fold's training rows and ``score`` on its held-out rows.  A
+    ``CrossValidated``: also ``auc`` and ``accuracy`` at 0 per K, the held-out evidence per k-mer of each class under its
+    own mixtures, ``mean_iterations`` and ``dead`` (components of weight 0, summed over the folds' best starts); ``bic``:
+    also fit each whole class per K for ``bic_positive`` / ``bic_negative`` (NaN otherwise)."""
+    a, Ks, n_init, max_iter, tol = _sweep_arguments(n_components, n_init, max_iter, tol, pseudocount)
+    pos, neg = _count_rows(positive_counts, "positive_counts"), _count_rows(negative_counts, "negative_counts")
+    if pos.ndim != 2 or neg.ndim != 2 or pos.shape[1] != neg.shape[1]:
+        raise ValueError("the two classes must have the same number of columns")
+    n_pos, n_neg, n_folds = len(pos), len(neg), int(folds)
+    if n_folds < 2 or n_folds > min(n_pos, n_neg):
+        raise ValueError("folds must be 2 to the rows of the smaller class (%d), got %r" % (min(n_pos, n_neg), folds))
+    from .cross_validate import FoldPlan
+    plan = FoldPlan(n_pos, n_neg, n_folds, seed)
+    host = np.vstack((pos, neg))
+    train_p, held_p = _fold_sets(plan.positive, n_folds)
+    train_n, held_n = _fold_sets(plan.negative, n_folds, n_pos)
+    whole = [np.arange(n_pos), n_pos + np.arange(n_neg)] if bic else []
+    held = [np.concatenate((hp, hn)) for hp, hn in zip(held_p, held_n)]
+    sets = train_p + train_n + held + whole      # set f / n_folds + f: the classes' training rows; 2 n_folds + f: held out
+    _check_training(Ks, train_p + train_n)
+    fitted_sets = list(range(2 * n_folds)) + [3 * n_folds + c for c in range(len(whole))]
+    cells = [(s, K, int(fit_seed) + i) for K in Ks for s in fitted_sets for i in range(n_init)]
+    dev = _sweep_device(host, sets)
+    try:
+        done = _lockstep(dev, host, sets, cells, a, max_iter, tol)
+        best, at = {}, 0
+        for K in Ks:
+            for s in fitted_sets:
+                best[K, s] = done[at + _best_start(done[at:at + n_init])]
+                at += n_init
+        jobs = [(2 * n_folds + f, best[K, c * n_folds + f].log_profiles, log_weights(best[K, c * n_folds + f].weights))
+                for K in Ks for f in range(n_folds) for c in (0, 1)]
+        got = iter(dev.step(jobs, rows=True, expect=False))
+        scores = np.full((len(Ks), n_pos + n_neg), np.nan)
+        evidence_p, evidence_n = np.zeros(len(Ks)), np.zeros(len(Ks))
+        for b, K in enumerate(Ks):
+            for f in range(n_folds):
+                lp, ln = next(got)[3], next(got)[3]
+                scores[b, held[f]] = lp - ln
+                evidence_p[b] += lp[:len(held_p[f])].sum()
+                evidence_n[b] += ln[len(held_p[f]):].sum()
+    finally:
+        dev.close()
+    ev = [_evaluate(s[:n_pos], s[n_pos:]) for s in scores]
+    per_K = len(fitted_sets) * n_init
+    nan = np.full(len(Ks), np.nan)
+    return CrossValidated(
+        Ks, n_pos, scores, np.array([e[0] for e in ev], dtype=np.float64), np.array([e[1] for e in ev], dtype=np.float64),
+        evidence_p / float(pos.sum(dtype=np.uint64)), evidence_n / float(neg.sum(dtype=np.uint64)),
+        np.array([_bic(best[K, 3 * n_folds], n_pos) for K in Ks]) if bic else nan,
+        np.array([_bic(best[K, 3 * n_folds + 1], n_neg) for K in Ks]) if bic else nan,
+        np.array([np.mean([g.n_iter for g in done[b * per_K:(b + 1) * per_K]]) for b in range(len(Ks))]),
+        np.array([sum(int((best[K, s].weights == 0).sum()) for s in range(2 * n_folds)) for K in Ks], dtype=np.int64))
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------
