@@ -1,8 +1,11 @@
 """Shared test helpers: golden loaders and a NumPy statement of the packed-base
 format (include/phamers_hip.h, "Packed base stream") used to cross-check the
 device packer.  Test-only code."""
+import contextlib
+import functools
 import json
 import os
+import time
 
 import numpy as np
 
@@ -57,3 +60,20 @@ def rel_err(a, b):
     a = np.asarray(a, dtype=float)
     b = np.asarray(b, dtype=float)
     return np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)) if a.size else 0.0
+
+
+@contextlib.contextmanager
+def wall_time(what):
+    """Prints the wall time of the block: the new tests of the large shapes report what they cost."""
+    start = time.perf_counter()
+    yield
+    print("%s: %.2f s" % (what, time.perf_counter() - start))
+
+
+def timed(test):
+    """Decorator: the test prints its own wall time (the parameters' values with it)."""
+    @functools.wraps(test)
+    def run(*args, **kwargs):
+        with wall_time("%s %r" % (test.__name__, {k: v for k, v in kwargs.items() if isinstance(v, (int, str))})):
+            return test(*args, **kwargs)
+    return run

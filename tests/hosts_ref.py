@@ -76,6 +76,19 @@ def excluded(query_groups, reference_groups, N, M):
     return (qg[:, None] >= 0) & (qg[:, None] == rg[None, :])
 
 
+def random_groups(seed, n):
+    """n group ids drawn from -1 .. 5 (-1: no group), not periodic in the index: what one device batch sees is not what
+    the next one sees, so a batch that read another batch's ids gives other results."""
+    return np.random.default_rng(seed).integers(-1, 6, n)
+
+
+def groups_of_the_first_batch(groups, batch_rows=128):
+    """The ids a call split into batches of ``batch_rows`` would use if every batch read the first batch's: the mistake the
+    tests of groups across batches are there to catch."""
+    g = np.asarray(groups)
+    return g[np.arange(len(g)) % batch_rows]
+
+
 def ranking(S, top, out=None):
     """(indices (N, top), values (N, top)) of the statement: rows by (S descending, index ascending), ``out`` (N, M) bool
     left out."""

@@ -32,6 +32,19 @@ def log_table(counts, pseudocount=0.5, dtype=np.float64):
     return np.log((x + a) / (x.sum(axis=1, keepdims=True) + dtype(x.shape[1]) * a))
 
 
+def random_groups(seed, n):
+    """n group ids drawn from -1 .. 5 (-1: no group), not periodic in the index: what one device batch sees is not what
+    the next one sees, so a batch that read another batch's ids gives other results."""
+    return np.random.default_rng(seed).integers(-1, 6, n)
+
+
+def groups_of_the_first_batch(groups, batch_rows=128):
+    """The ids a call split into batches of ``batch_rows`` would use if every batch read the first batch's: the mistake the
+    tests of groups across batches are there to catch."""
+    g = np.asarray(groups)
+    return g[np.arange(len(g)) % batch_rows]
+
+
 def _class_term(c, table, qg, g, dtype):
     """l_C of the count rows c (N, D) under the float64 log table (M, D), in ``dtype``."""
     S = c.astype(dtype) @ table.astype(dtype).T

@@ -46,6 +46,45 @@ def tree_sum(values):
             return v[0]
 
 
+def block_sums(values):
+    """One partial per block of BLOCK_ROWS rows of ``values`` (N, ...) float64, anchored at row 0, in the order of
+    ``mix_expect_body``'s N_k and L: lane group kk = 0 .. 3 of the wave (row slot s) starts from +0.0 and adds rows
+    b * BLOCK_ROWS + s, + 4, + 8, ... in row order, a row past N as +0.0; the two ``__shfl_xor`` steps (16, then 32) join the
+    slots as (0 + 1) + (2 + 3).  ``tree_sum(block_sums(x))`` is the device's N_k for x = r (N, K) and its L for x = l (N,)."""
+    v = np.asarray(values, dtype=np.float64)
+    n = v.shape[0]
+    blocks = max(1, -(-n // BLOCK_ROWS))
+    padded = np.zeros((blocks * BLOCK_ROWS,) + v.shape[1:])
+    padded[:n] = v
+    steps = padded.reshape((blocks, BLOCK_ROWS // 4, 4) + v.shape[1:])
+    slots = np.zeros((blocks, 4) + v.shape[1:])
+    for i in range(BLOCK_ROWS // 4):
+        slots += steps[:, i]
+    return (slots[:, 0] + slots[:, 1]) + (slots[:, 2] + slots[:, 3])
+
+
+def device_order(r, l):
+    """(N_k, L) of the device from its own r (N, K) and l (N,): both are plain float64 adds, so this is exact."""
+    return tree_sum(block_sums(r)), float(tree_sum(block_sums(l)))
+
+
+def two_profile_case(n_rows, K, seed=4):
+    """(counts (n_rows, 4) uint32, log_profiles (K, 4), log_w (K,)): the inputs of the two-level tests, shared by the GPU
+    tests and the host's discrimination checks.  Rows of 30 k-mers from two planted profiles, each row's profile a fair coin;
+    the table is the same profiles lightly perturbed (K = 1: the first alone), so that neither component starves.  Seed 4 is
+    the first at which every order tests/test_mixture_host.py sets against the device's gives other bits on the float64
+    statement's r and l (at seeds 1 to 3 one of the two plain sums of l happens to round to the device's L)."""
+    rng = np.random.RandomState(seed)
+    planted_profiles = np.array([[0.40, 0.30, 0.20, 0.10], [0.10, 0.20, 0.30, 0.40]])
+    label = rng.randint(0, 2, n_rows).astype(bool)
+    counts = np.where(label[:, None], rng.multinomial(30, planted_profiles[1], n_rows),
+                      rng.multinomial(30, planted_profiles[0], n_rows)).astype(np.uint32)
+    table = planted_profiles[:K] * (1.0 + 0.05 * rng.uniform(-1.0, 1.0, (K, 4)))
+    table /= table.sum(axis=1, keepdims=True)
+    weights = np.array([0.45, 0.55])[:K]
+    return counts, np.log(table), np.log(weights / weights.sum())
+
+
 def e_step(counts, log_profiles, log_w, dtype=np.longdouble):
     """dict(l, r, T, Nk, L, argmax, max_resp) of one E-step in ``dtype``; float64: T, N_k and L by blocks and tree."""
     c = np.asarray(counts).astype(dtype)

@@ -44,7 +44,7 @@ def _bound(absum, n, m, D=256):
 
 
 # ---- 1. query and row shapes -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("top", [1, 5, 16])
+@pytest.mark.parametrize("top", [1, 5, 8, 9, 15, 16])         # 8 fills the short list, 9 is the first top of the long one
 @pytest.mark.parametrize("m", [16, 255, 257, 513])
 @pytest.mark.parametrize("n", [1, 127, 128, 129])
 def test_shapes_against_extended_statement(shapes, n, m, top):
@@ -57,6 +57,19 @@ def test_shapes_against_extended_statement(shapes, n, m, top):
                                   what="%s N=%d M=%d top=%d" % (model, n, m, top))
         assert exact >= 0.9
         assert np.array_equal(r.per_kmer, r.log_likelihood / 4997.0)
+
+
+@pytest.mark.parametrize("m", [8, 9])
+@helpers.timed
+def test_lists_as_long_as_the_table(shapes, m):
+    """top = M = 8: every row returned from a full short list; top = M = 9: the long list's first use, with nothing left out."""
+    from phamers_amd import hosts
+    q, x, S, absum = shapes
+    for model in MODELS:
+        r = hosts.rank(q[:129], x[:m], top=m, model=model)
+        assert (np.sort(r.indices, axis=1) == np.arange(m)).all()
+        assert ref.check_ranking(r.indices, r.log_likelihood, S[model][:129, :m], _bound(absum[model], 129, m), m,
+                                 what="%s M=top=%d" % (model, m)) >= 0.9
 
 
 def test_one_row_one_hit(shapes):
@@ -85,6 +98,28 @@ def test_batch_splits_do_not_change_a_bit(shapes, top):
             assert np.array_equal(whole.log_likelihood[lo:hi], part.log_likelihood)
         again = hosts.rank(q, x, top=top, model=model)              # run to run
         assert np.array_equal(whole.indices, again.indices) and np.array_equal(whole.log_likelihood, again.log_likelihood)
+
+
+@pytest.mark.parametrize("top", [5, 16])
+@helpers.timed
+def test_groups_across_batches_do_not_change_a_bit(shapes, top):
+    """Random group ids on both sides and three device batches: every batch must read its own queries' ids.
+    (tests/test_hosts_host.py: with the first batch's ids in every batch most later queries get rows of their own group.)"""
+    from phamers_amd import hosts
+    q, x, S, absum = shapes
+    gq, gr = ref.random_groups(4, 300), ref.random_groups(5, 513)
+    out = ref.excluded(gq, gr, 300, 513)
+    for model in MODELS:
+        whole = hosts.rank(q, x, top, model, query_groups=gq, reference_groups=gr, _batch_rows=0)
+        assert not out[np.arange(300)[:, None], whole.indices].any()     # never a row of its own group
+        assert ref.check_ranking(whole.indices, whole.log_likelihood, S[model], _bound(absum[model], 300, 513), top, out=out,
+                                 what="%s groups top=%d" % (model, top)) >= 0.9
+        for rows in (128, 1):
+            split = hosts.rank(q, x, top, model, query_groups=gq, reference_groups=gr, _batch_rows=rows)
+            assert np.array_equal(whole.indices, split.indices) and np.array_equal(whole.log_likelihood, split.log_likelihood)
+        part = hosts.rank(q[127:300], x, top, model, query_groups=gq[127:300], reference_groups=gr, _batch_rows=128)
+        assert np.array_equal(whole.indices[127:300], part.indices)
+        assert np.array_equal(whole.log_likelihood[127:300], part.log_likelihood)
 
 
 # ---- 3. other widths ---------------------------------------------------------------------------------------------------------
@@ -122,13 +157,44 @@ def test_identical_rows_tie_exactly_across_chunk_borders(shapes):
     x[256], x[512] = x[255], x[0]                  # twins in chunks 0 | 1 and 0 | 2
     queries = likelihood.thin(x[[255, 0, 256, 512]], 2000, np.random.RandomState(5))
     for model in MODELS:
-        for top in (2, 5, 16):
+        for top in (2, 5, 8, 9, 16):
             r = hosts.rank(queries, x, top=top, model=model)
             for row, (lo, hi) in enumerate(((255, 256), (0, 512), (255, 256), (0, 512))):
                 i, s = r.indices[row].tolist(), r.log_likelihood[row]
                 assert i[:2] == [lo, hi] and s[0] == s[1], (model, top, row, i, s)       # its own profile first, the twin next
             L = ref.table(x, model)
             ref.check_ranking(r.indices, r.log_likelihood, ref.products(queries, L), ref.bound(queries, L), top)
+
+
+@helpers.timed
+def test_twins_at_the_edge_of_the_short_list(shapes):
+    """A query whose ranks 8 and 9 are one profile held by two rows in different chunks: with top = 8 the list ends with the
+    lower index of the pair, with top = 9 both come, in index order and with equal S.  Query and pair come from the longdouble
+    products: the first query whose first ten gaps all exceed 4 e, its rank-8 row, copied over its least likely row of
+    another chunk."""
+    from phamers_amd import hosts
+    q, x, S, absum = shapes
+    for model in MODELS:
+        e = _bound(absum[model], 300, 513)
+        order = ref.ranking(S[model], 10)[0]
+        first = np.take_along_axis(S[model], order, axis=1)
+        clear = np.flatnonzero((first[:, :-1] - first[:, 1:]).min(axis=1).astype(np.float64) > 4.0 * e)
+        qi = int(clear[0])
+        row = int(order[qi, 7])
+        elsewhere = np.setdiff1d(np.flatnonzero(np.arange(513) // 256 != row // 256), order[qi])
+        victim = int(elsewhere[np.argmin(S[model][qi, elsewhere])])
+        y = x.copy()
+        y[victim] = x[row]
+        lo, hi = min(row, victim), max(row, victim)
+        L = ref.table(y, model)
+        for top in (8, 9):
+            r = hosts.rank(q[qi:qi + 1], y, top=top, model=model)
+            i, s = r.indices[0].tolist(), r.log_likelihood[0]
+            assert i[:7] == order[qi, :7].tolist() and i[7] == lo, (model, top, i, lo, hi)
+            if top == 9:
+                assert i[8] == hi and s[7] == s[8], (model, i, s)
+            # (its exact-indices statement steps back at the pair's tie; the lines above are that statement here)
+            ref.check_ranking(r.indices, r.log_likelihood, ref.products(q[qi:qi + 1], L), ref.bound(q[qi:qi + 1], L), top)
 
 
 def test_duplicate_genomes_of_the_reference_come_in_index_order(golden):

@@ -67,6 +67,34 @@ def test_batch_splits_do_not_change_a_bit(shapes):
     assert all(np.array_equal(a, b) for a, b in zip(whole, again))
 
 
+@pytest.mark.parametrize("classes", [2, 1])
+@helpers.timed
+def test_groups_across_batches_do_not_change_a_bit(shapes, classes):
+    """Random group ids on both sides and more than one device batch: each batch must read its own queries' ids and its own
+    effective row counts.  (tests/test_likelihood_host.py: with the first batch's ids in every batch most queries leave the bound.)"""
+    from phamers_amd import _lib
+    q, pos, neg = shapes
+    lp, ln = ref.log_table(pos), (ref.log_table(neg) if classes == 2 else None)
+    gq, gp, gn = ref.random_groups(1, 300), ref.random_groups(2, 513), (ref.random_groups(3, 257) if classes == 2 else None)
+    table = _lib.LikelihoodTable(_lib.get_context(), lp, ln, gp, gn)
+
+    def score(rows, groups, batch_rows):
+        d = {}
+        s = table.score(rows, groups, batch_rows, d)
+        return d["l_pos"], d["l_neg"], s
+
+    try:
+        whole = score(q, gq, 0)
+        ref.check(whole, q, lp, ln, gq, gp, gn, what="groups, %d classes" % classes)
+        for batch_rows in (128, 1):                                      # three batches: 128 + 128 + 44
+            assert all(np.array_equal(a, b) for a, b in zip(whole, score(q, gq, batch_rows)))
+        part = score(q[127:300], gq[127:300], 128)                       # the ids travel with their queries
+        assert all(np.array_equal(a[127:300], b) for a, b in zip(whole, part))
+        assert not np.array_equal(whole[2], score(q, None, 0)[2])        # and they exclude something
+    finally:
+        table.close()
+
+
 # ---- 2. other D ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("D", [4, 16, 64, 1024])
 def test_other_widths_through_a_resident_batch(D):

@@ -2,6 +2,8 @@
 equality: every job of a step call is ``array_equal`` to ``MixtureTable.expect`` on that job's rows alone, for any grouping
 under the byte budget, source, order of the jobs and run; every cell of ``mixture.sweep`` equals ``mixture.fit`` field by
 field.  Shapes are the smallest that cross the kernels' boundaries (row tile 128, component step 64, row block 1024)."""
+import time
+
 import numpy as np
 import pytest
 
@@ -109,8 +111,10 @@ def test_resident_batch_repeated_runs_and_job_order(rows, mixed):
 
 
 # ---- 3. widths -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,resident", [(4, True), (64, True), (30, False)])
+@pytest.mark.parametrize("D,resident", [(4, True), (64, True), (30, False), (1024, True), (320, False), (258, False)])
 def test_other_widths(D, resident):
+    """D > 256: more than one column group per row block (the descriptor's y).  1024: four groups; 320: two, and three
+    waves of the second leave at once; 258: the scalar loaders, two live columns in the second group."""
     rng = np.random.RandomState(D)
     counts = np.stack([rng.multinomial(2500, rng.dirichlet(np.full(D, 0.7))) for _ in range(131)]).astype(np.uint32)
     sets = [np.arange(131), np.sort(rng.choice(131, 77, replace=False))]
@@ -119,6 +123,72 @@ def test_other_widths(D, resident):
     for (s, lp, lw), g in zip(jobs, got):
         assert same([g], [single(counts[sets[s]], lp, lw)])
         mref.check_e_step(dict(T=g[0], Nk=g[1], L=g[2], l=g[3]), counts[sets[s]], lp, lw)
+
+
+# ---- 3b. a job of two fold levels beside jobs of one ---------------------------------------------------------------------------
+TWO_LEVELS = 256 * RB + 1
+
+
+@pytest.fixture(scope="module")
+def levels():
+    """dict(counts, sets, jobs, want, got): 256 RB + 3 rows at D = 4; set 0 all rows (aliases the source), set 1 all but two
+    interior rows (257 blocks, gathered), set 2 129 scattered rows.  Fold descriptors of the default call (one group), from
+    phk_mix_sweep_step: level 0 holds 2 + 2 + 2 + 1 (two blocks of vectors for each big job, two element blocks for
+    K = 65), level 1 one per big job, which writes into the result area while the small jobs have left the list."""
+    started = time.perf_counter()
+    counts, logp, logw = mref.two_profile_case(TWO_LEVELS + 2, 2)
+    rng = np.random.RandomState(11)
+    sets = [np.arange(len(counts)), np.delete(np.arange(len(counts)), [1000, 200 * RB + 7]),
+            np.sort(rng.choice(len(counts), 129, replace=False))]
+    assert len(sets[1]) == TWO_LEVELS and (np.diff(sets[2]) > 1).any()
+    small = counts[sets[2]]
+    jobs = [(1, logp, logw), (2,) + table_of(small, 65, seed=1), (0,) + mref.two_profile_case(TWO_LEVELS + 2, 1)[1:],
+            (2,) + table_of(small, 2, seed=2)]
+    want = [single(counts[sets[s]], lp, lw) for s, lp, lw in jobs]
+    got = step(counts, sets, jobs, rows=True)
+    print("levels fixture: %.2f s" % (time.perf_counter() - started))
+    return dict(counts=counts, sets=sets, jobs=jobs, want=want, got=got)
+
+
+def test_a_two_level_job_beside_one_level_jobs_is_the_single_call(levels):
+    started = time.perf_counter()
+    assert same(levels["got"], levels["want"])
+    counts, sets = levels["counts"], levels["sets"]
+    # the gathered job: N_k and L in the device's order over its own r and l, everything inside the bound
+    _, lp, lw = levels["jobs"][0]
+    T, Nk, L, l = levels["got"][0]
+    from phamers_amd import _lib
+    table = _lib.MixtureTable(_lib.get_context(), lp, lw)
+    try:
+        r, l_single = table.responsibilities(counts[sets[1]])
+    finally:
+        table.close()
+    Nk_want, L_want = mref.device_order(r, l_single)
+    assert np.array_equal(l, l_single) and np.array_equal(Nk, Nk_want) and L == L_want and (Nk >= TWO_LEVELS / 8.0).all()
+    print("worst error / bound: %.4f" % mref.check_e_step(dict(T=T, Nk=Nk, L=L, l=l), counts[sets[1]], lp, lw))
+    # the aliasing job, K = 1: exact
+    T, Nk, L, l = levels["got"][2]
+    assert np.array_equal(T[0], counts.sum(axis=0, dtype=np.uint64).astype(np.float64)) and Nk[0] == float(len(counts))
+    assert L == mref.device_order(np.ones((len(counts), 1)), l)[1]
+    print("two-level sweep job: %.2f s" % (time.perf_counter() - started))
+
+
+@pytest.mark.parametrize("variant", ["own_groups", "mixed_levels_per_group", "reversed", "resident"])
+def test_two_level_jobs_do_not_depend_on_grouping_order_or_source(levels, variant):
+    """own_groups: a budget of 1 byte, every job alone; mixed_levels_per_group: 200 MiB lies between one big job's buffers
+    (128 MiB of R) and two, so each group holds a two-level job and a one-level job."""
+    started = time.perf_counter()
+    counts, sets, jobs, want = (levels[k] for k in ("counts", "sets", "jobs", "want"))
+    if variant == "own_groups":
+        got = step(counts, sets, jobs, rows=True, _budget_bytes=1)
+    elif variant == "mixed_levels_per_group":
+        got = step(counts, sets, jobs, rows=True, _budget_bytes=200 << 20)
+    elif variant == "reversed":
+        got = step(counts, sets, jobs[::-1], rows=True)[::-1]
+    else:
+        got = step(counts, sets, jobs, resident=True, rows=True)
+    assert same(got, want)
+    print("%s: %.2f s" % (variant, time.perf_counter() - started))
 
 
 # ---- 4. edge cases -------------------------------------------------------------------------------------------------------------

@@ -213,3 +213,32 @@ def test_hosts_file_round_trips(tmp_path):
     with pytest.raises(ValueError, match="hits"):
         fileIO.save_phamer_hosts(str(tmp_path / "bad.csv"), sc.data_ids[:1], sc.host_ids, sc.host_log_likelihood,
                                  sc.host_per_kmer, sc.host_z, sc.host_p_value)
+
+
+def test_the_first_batch_s_groups_in_every_batch_return_rows_of_the_query_s_group():
+    """The inputs of test_groups_across_batches_do_not_change_a_bit (tests/test_gpu_hosts.py): had batches 2 and 3 read batch
+    1's group ids, at least half of their queries would get another list than the statement's -- by more than the bound: a row
+    of the query's own group comes back, or a row is missing whose S exceeds the last returned one's by more than 2 e.  So
+    that test can fail."""
+    from tests import test_gpu_hosts as gpu
+    rng = np.random.default_rng(21)                                      # the GPU tests' ``shapes`` fixture
+    q, x = gpu._contigs(rng, 300, 256), gpu._genomes(rng, 513, 256)
+    gq, gr = ref.random_groups(4, 300), ref.random_groups(5, 513)
+    wrong = ref.groups_of_the_first_batch(gq)
+    assert np.array_equal(wrong[:128], gq[:128]) and (wrong[128:] != gq[128:]).mean() > 0.5
+    out = ref.excluded(gq, gr, 300, 513)
+    assert (~out).sum(axis=1).min() >= 16
+    for model in gpu.MODELS:
+        L = ref.table(x, model)
+        S, e = ref.products(q, L), ref.bound(q, L)
+        for top in (5, 16):
+            right, _ = ref.ranking(S, top, out)
+            mistaken, _ = ref.ranking(S, top, ref.excluded(wrong, gr, 300, 513))
+            assert np.array_equal(mistaken[:128], right[:128])
+            caught = np.zeros(300, dtype=bool)
+            for i in range(128, 300):
+                own = out[i, mistaken[i]].any()
+                rest = ~out[i]
+                rest[mistaken[i]] = False
+                caught[i] = own or float(S[i, rest].max() - S[i, mistaken[i, -1]]) > 2.0 * e[i]
+            assert caught[128:].mean() >= 0.5, (model, top, caught[128:].mean())

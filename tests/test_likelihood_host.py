@@ -189,3 +189,24 @@ def test_validator_routes_and_keeps_its_method_list():
     v.positive_data = v.negative_data = np.full((4, 16), 1.0 / 16)
     with pytest.raises(ValueError, match="'likelihood' needs the integer count rows"):
         v.cross_validate()
+
+
+def test_the_first_batch_s_groups_in_every_batch_leave_the_bound():
+    """The inputs of test_groups_across_batches_do_not_change_a_bit (tests/test_gpu_likelihood.py): had batches 2 and 3 read
+    batch 1's group ids (and with them its effective row counts), at least half of their queries would miss the bound, with
+    one class and with two.  So that test can fail."""
+    from tests import test_gpu_likelihood as gpu
+    rng = np.random.default_rng(20)                                      # the GPU tests' ``shapes`` fixture
+    q, pos, neg = gpu._contigs(rng, 300, 256), gpu._genomes(rng, 513, 256), gpu._genomes(rng, 257, 256)
+    gq, gp, gn = ref.random_groups(1, 300), ref.random_groups(2, 513), ref.random_groups(3, 257)
+    wrong = ref.groups_of_the_first_batch(gq)
+    assert np.array_equal(wrong[:128], gq[:128]) and (wrong[128:] != gq[128:]).mean() > 0.5
+    for lp, ln, n in ((ref.log_table(pos), ref.log_table(neg), gn), (ref.log_table(pos), None, None)):
+        right = ref.statement(q, lp, ln, gq, gp, n)
+        want, tol = ref.check(right, q, lp, ln, gq, gp, n)
+        mistaken = ref.statement(q, lp, ln, wrong, gp, n)
+        for got, exact in zip(mistaken, want):
+            if ln is None and not np.any(exact):
+                continue                                                 # l_neg of one class: 0 either way
+            off = np.abs(got.astype(np.longdouble) - exact).astype(np.float64) > tol
+            assert not off[:128].any() and off[128:].mean() >= 0.5, off[128:].mean()

@@ -313,3 +313,96 @@ def test_float64_statement_on_the_inputs_of_the_gpu_tests(golden):
     for counts, logp, logw in cases:
         worst = max(worst, mref.check_e_step(mref.e_step(counts, logp, logw, np.float64), counts, logp, logw))
     assert worst < 0.5, worst
+
+
+# ---- the device's order of N_k and L, written out (mix_expect_body) ------------------------------------------------
+@pytest.mark.parametrize("K", [1, 3])
+@pytest.mark.parametrize("N", [1, 3, 4, 5, 1023, 1024, 1025, 2049])
+def test_block_sums_is_the_slot_rule_written_out(N, K):
+    rng = np.random.default_rng(N + K)
+    for v in (rng.random((N, K)) * 10.0 ** rng.integers(-3, 4, (N, 1)), -rng.random(N) * 1e3):
+        want = []
+        for b in range(0, N, mref.BLOCK_ROWS):
+            slots = [np.zeros(v.shape[1:]) for _ in range(4)]
+            for i in range(b, min(b + mref.BLOCK_ROWS, N)):
+                slots[(i - b) % 4] = slots[(i - b) % 4] + v[i]
+            want.append((slots[0] + slots[1]) + (slots[2] + slots[3]))
+        got = mref.block_sums(v)
+        assert got.shape == (len(want),) + v.shape[1:] and np.array_equal(got, np.array(want))
+    assert np.array_equal(mref.block_sums(np.zeros((0, K))), np.zeros((1, K)))
+
+
+@pytest.mark.parametrize("D,kmers,K,N", [(256, 200, 3, 300), (16, 50, 17, 2 * mref.BLOCK_ROWS + 1)])
+def test_device_order_is_inside_the_bound(D, kmers, K, N):
+    rng = np.random.RandomState(D + K + N)
+    counts = rng.multinomial(kmers, rng.dirichlet(np.ones(D)), N).astype(np.uint32)
+    logp, logw = random_table(rng, K, D)
+    got = mref.e_step(counts, logp, logw, np.float64)
+    Nk, L = mref.device_order(got["r"], got["l"])
+    assert mref.check_e_step(dict(Nk=Nk, L=L), counts, logp, logw) < 0.5
+
+
+@pytest.fixture(scope="module")
+def two_levels():
+    """The K = 2 case of tests/test_gpu_mixture_levels.py at 257 blocks, with the float64 statement's r and l."""
+    N = 256 * mref.BLOCK_ROWS + 1
+    counts, logp, logw = mref.two_profile_case(N, 2)
+    got = mref.e_step(counts, logp, logw, np.float64)
+    return dict(N=N, counts=counts, logp=logp, logw=logw, r=got["r"], l=got["l"], Nk=got["Nk"], L=got["L"])
+
+
+def test_two_level_inputs_keep_both_components_alive_and_inside_the_bound(two_levels):
+    c = two_levels
+    Nk, L = mref.device_order(c["r"], c["l"])
+    assert (Nk >= c["N"] / 8.0).all(), Nk
+    assert mref.tree_levels(-(-c["N"] // mref.BLOCK_ROWS)) == 2 and mref.tree_levels(256) == 1
+    assert mref.check_e_step(dict(Nk=Nk, L=L), c["counts"], c["logp"], c["logw"]) < 0.5
+    one = mref.two_profile_case(c["N"], 1)                                   # the K = 1 case: the same rows
+    assert np.array_equal(one[0], c["counts"]) and one[2][0] == 0.0 and one[1].shape == (1, 4)
+
+
+def test_device_order_differs_from_every_other_order_on_the_two_level_inputs(two_levels):
+    """What shows that the exact equalities of the GPU tests can fail: on their inputs the device's order gives other bits
+    than each order a wrong kernel or a wrong statement would give.  (The tree with the two second-level inputs swapped is
+    left out: the second level of 257 blocks is the one addition v[0] + v[1], and a + b == b + a in IEEE arithmetic.)"""
+    c = two_levels
+    r, l = c["r"], c["l"]
+    Nk, L = mref.device_order(r, l)
+    for k in range(2):
+        assert Nk[k] != r[:, k].sum() and Nk[k] != r.sum(axis=0)[k]           # NumPy's own order
+        assert Nk[k] != c["Nk"][k]                                            # the float64 statement's block sums
+    assert L != l.sum() and L != c["L"]
+    first = 256 * mref.BLOCK_ROWS                                             # one level only / the 257th block dropped
+    Nk_first, L_first = mref.device_order(r[:first], l[:first])
+    assert (Nk != Nk_first).all() and L != L_first
+    parts_r, parts_l = mref.block_sums(r), mref.block_sums(l)
+    assert len(parts_r) == 257 and np.array_equal(mref.tree_sum(parts_r[:256]), Nk_first)
+    assert mref.tree_sum(parts_l[:256]) == L_first
+    # blocks anchored one row late move bits too
+    assert (Nk != mref.tree_sum(mref.block_sums(np.vstack((np.zeros((1, 2)), r))))).any()
+
+
+def test_device_order_differs_from_other_joins_on_the_golden_rows(golden):
+    """The order statement at the GPU tests' D = 256 shapes (K = 17): the statement's block sums, NumPy's sums and the four
+    slots joined in slot order ((0 + 1) + 2) + 3 each give other bits in some component at every N; L, one number, differs
+    from at least one of the two plain sums of l."""
+    from tests import test_gpu_mixture as gpu
+    pos, neg = golden
+    n = gpu.RB + 1
+    rows = np.empty((2 * n, 256), dtype=np.uint32)
+    rows[0::2], rows[1::2] = pos[:n], neg[:n]
+    logp, logw = gpu.table_of(rows[:2 * gpu.RB + 1], 17)
+    for N in (gpu.RB - 1, gpu.RB, gpu.RB + 1, 2 * gpu.RB + 1):
+        got = mref.e_step(rows[:N], logp, logw, np.float64)
+        r, l = got["r"], got["l"]
+        Nk, L = mref.device_order(r, l)
+        blocks = -(-N // gpu.RB)
+        steps = np.zeros((blocks * gpu.RB, 17))
+        steps[:N] = r
+        steps = steps.reshape(blocks, gpu.RB // 4, 4, 17)
+        slots = np.zeros((blocks, 4, 17))
+        for i in range(gpu.RB // 4):
+            slots += steps[:, i]
+        in_slot_order = mref.tree_sum(((slots[:, 0] + slots[:, 1]) + slots[:, 2]) + slots[:, 3])
+        assert (Nk != in_slot_order).any() and (Nk != got["Nk"]).any() and (Nk != r.sum(axis=0)).any(), N
+        assert L != l.sum() or L != got["L"], N
