@@ -618,6 +618,56 @@ int phk_mix_sweep_step(phk_ctx *ctx, const phk_mix_sweep *sweep, const uint32_t 
                        uint64_t budget_bytes, double *out);
 int phk_mix_sweep_destroy(phk_ctx *ctx, phk_mix_sweep *sweep);
 
+/* ---- S-state chain over the count rows of windows (chain.hip) ---------------------------------------
+ * Records r have windows t = offsets[r] .. offsets[r + 1] - 1 (offsets[R + 1], non-decreasing from 0 to n) with uint32 count
+ * rows [n][D]; S states, 2 <= S <= PHK_CHAIN_MAX_STATES.  A chain keeps the rows (uploaded once by phk_chain_create, or a
+ * resident batch's rows read where they lie: the batch must outlive the chain), the offsets and every device buffer of its
+ * calls.  phk_chain_create_from_emissions takes host emissions E[n][S] instead of rows: a general S-state decoder.
+ *
+ * phk_chain_set(log_profiles[S][D], trans[S][S], init[S], qlog_trans, qlog_init, temper) forms on the device
+ *     E[t][s] = temper * sum_j c_t[j] log_profiles[s][j]       float64 on the matrix pipe, one multiply by temper afterwards
+ * (a chain made from emissions takes log_profiles == NULL and keeps its E; temper is checked and not used).  The logarithms are
+ * the caller's; qlog_* are log trans and log init in int64 units of 2^-PHK_SEG_QUANT_BITS nat, each in [-2^31, 0].  With
+ * d[t][s] = E[t][s] - max_s' E[t][s'] <= 0:
+ *   phk_chain_emissions  E[n][S] to the host.
+ *   phk_chain_expect     one E-step.  xi[S][S] = sum_t P(s_{t-1} = i, s_t = j | rows), each step's S^2 terms normalised by
+ *                        their own sum and added in step order per record; gamma0[S]; *log_evidence; the three summed over the
+ *                        records by the fixed 256-row tree of phk_segment_expect; log_evidence_rec[R] unless NULL.
+ *                        T[S][D] = sum_t gamma_t(s) c_t[j] and Ns[S] = sum_t gamma_t(s), reduced in blocks of
+ *                        phk_mix_block_rows() rows anchored at the global row index and that tree (both NULL: not computed;
+ *                        a chain made from emissions has none).  The posteriors and E stay on the device.
+ *   phk_chain_decode     state[n] uint8: the path of the plain left-to-right max-plus recurrence on exact integers over
+ *                        q[t][s] = rint(max(d[t][s], -2^15) 2^PHK_SEG_QUANT_BITS), ties to the smallest predecessor and, at the
+ *                        end, to the smallest state; path_score[R] int64 unless NULL; posterior[n][S] and
+ *                        log_evidence_rec[R] unless NULL (forward-backward in the probability domain on exp(d), rescaled by
+ *                        powers of two; an exp that underflows to 0 reads as "certain").
+ * Every result of a record is a function of its own rows and the parameters alone: the same bits for any batch_rows (rows per
+ * device batch, 0 = the default), from host rows and from a batch, whatever the other records, the launch or the run.  At most
+ * 2^30 windows per chain: with |q| and |qlog| <= 2^31 every integer sum stays inside 2^62.
+ * PHK_ERR_ARG, before any launch: S outside 2..8, bad offsets (create); a parameter outside (0, 1), a row of trans or init
+ * that does not sum to 1 within 4 ulp, a qlog outside [-2^31, 0], D not the rows', temper not finite and > 0 (set); a call
+ * before a successful set.  PHK_ERR_NAN: a profile entry (set) or a host emission (create) that is not finite.  n == 0 or
+ * R == 0 is PHK_OK with zeros; a record without windows contributes nothing, a record of one window only its gamma0 and
+ * evidence.  phk_chain_grid_pass(): the most records one launch of the per-record kernels covers (further ones by grid
+ * stride; for the tests). */
+#define PHK_CHAIN_MAX_STATES 8
+typedef struct phk_chain phk_chain;
+int phk_chain_create(phk_ctx *ctx, const uint32_t *counts, uint64_t n, uint64_t D, const uint64_t *offsets, uint64_t R,
+                     uint32_t S, uint64_t batch_rows, phk_chain **out);
+int phk_batch_chain_create(phk_ctx *ctx, const phk_batch *b, const uint64_t *offsets, uint64_t R, uint32_t S,
+                           uint64_t batch_rows, phk_chain **out);
+int phk_chain_create_from_emissions(phk_ctx *ctx, const double *E, uint64_t n, const uint64_t *offsets, uint64_t R, uint32_t S,
+                                    phk_chain **out);
+int phk_chain_set(phk_ctx *ctx, phk_chain *chain, const double *log_profiles, uint64_t D, const double *trans,
+                  const double *init, const int64_t *qlog_trans, const int64_t *qlog_init, double temper);
+int phk_chain_emissions(phk_ctx *ctx, const phk_chain *chain, double *E);
+int phk_chain_expect(phk_ctx *ctx, const phk_chain *chain, double *T, double *Ns, double *xi, double *gamma0,
+                     double *log_evidence, double *log_evidence_rec);
+int phk_chain_decode(phk_ctx *ctx, const phk_chain *chain, uint8_t *state, double *posterior, double *log_evidence_rec,
+                     int64_t *path_score);
+uint64_t phk_chain_grid_pass(void);
+int phk_chain_destroy(phk_ctx *ctx, phk_chain *chain);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -125,6 +125,15 @@ SIGNATURES = {
                                    c_void_p]),
     "phk_segment_fit": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_void_p, c_int, c_void_p, ctypes.c_uint32,
                                 ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_chain_create": (c_int, [c_void_p, c_void_p, c_u64, c_u64, c_void_p, c_u64, ctypes.c_uint32, c_u64, P(c_void_p)]),
+    "phk_batch_chain_create": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, ctypes.c_uint32, c_u64, P(c_void_p)]),
+    "phk_chain_create_from_emissions": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, ctypes.c_uint32, P(c_void_p)]),
+    "phk_chain_set": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double]),
+    "phk_chain_emissions": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "phk_chain_expect": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_chain_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_chain_grid_pass": (c_u64, []),
+    "phk_chain_destroy": (c_int, [c_void_p, c_void_p]),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1312,6 +1321,96 @@ def segment_fit(ctx, x, offsets, start, start_mode, prior_counts, max_iter, tol)
                                         ptr(pc), int(max_iter), float(tol), ptr(trace), ctypes.byref(n_iter),
                                         ctypes.byref(status), ptr(fitted)))
     return trace[:n_iter.value + 1].copy(), int(n_iter.value), int(status.value), fitted
+
+
+CHAIN_MAX_STATES = 8   # PHK_CHAIN_MAX_STATES
+
+
+class Chain(_Resident):
+    """An S-state chain over window rows (phk_chain): ``rows`` is an integer count matrix (n, D)
+    (uploaded once), a ``Batch`` (read where it lies; it must outlive the chain) or, with ``emissions=True``, float64
+    emissions (n, S); ``offsets`` (R + 1,) cuts the rows into records.  ``set`` then ``expect`` / ``decode`` /
+    ``emissions``.  ValueError for what the library refuses as an argument or as not finite."""
+    _destroy = "phk_chain_destroy"
+
+    def __init__(self, ctx, rows, offsets, n_states, batch_rows=0, emissions=False):
+        self.ctx, self.S = ctx, int(n_states)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.ndim != 1 or off.shape[0] < 1:
+            raise ValueError("offsets must be (R + 1,)")
+        self.R = off.shape[0] - 1
+        if not 0 <= self.S < 2 ** 32:
+            raise ValueError("n_states = %r" % (n_states,))
+        h = ctypes.c_void_p()
+        if emissions:
+            E = np.ascontiguousarray(rows, dtype=np.float64)
+            if E.ndim != 2 or E.shape[1] != self.S:
+                raise ValueError("the emissions must be (n, %d), got shape %r" % (self.S, E.shape))
+            self.n, self.D, self.from_counts = E.shape[0], 0, False
+            rc = ctx.lib.phk_chain_create_from_emissions(ctx.handle, ptr(E), self.n, ptr(off), self.R, self.S, ctypes.byref(h))
+        elif isinstance(rows, Batch):
+            rows._open()
+            self.n, self.D, self.from_counts = rows.n, rows.D, True
+            self._batch = rows
+            rc = ctx.lib.phk_batch_chain_create(ctx.handle, rows.handle, ptr(off), self.R, self.S, int(batch_rows), ctypes.byref(h))
+        else:
+            c = np.ascontiguousarray(rows, dtype=np.uint32)
+            if c.ndim != 2:
+                raise ValueError("the counts must be (n, D)")
+            self.n, self.D, self.from_counts = c.shape[0], c.shape[1], True
+            rc = ctx.lib.phk_chain_create(ctx.handle, ptr(c), self.n, self.D, ptr(off), self.R, self.S, int(batch_rows),
+                                          ctypes.byref(h))
+        self._rc(rc)
+        self.handle = h
+
+    @staticmethod
+    def _rc(rc):
+        if rc == PHK_ERR_NAN:
+            raise ValueError(last_error())
+        check_value(rc, nan=False)
+
+    def set(self, log_profiles, trans, init, qlog_trans, qlog_init, temper=1.0):
+        """The parameters of the calls that follow (phk_chain_set); forms the emissions on the device.  ``log_profiles``
+        (S, D), None for a chain made from emissions; ``qlog_*``: the quantised logarithms (segment.quantise)."""
+        self._open()
+        S = self.S
+        lp = None if log_profiles is None else np.ascontiguousarray(log_profiles, dtype=np.float64)
+        if lp is not None and (lp.ndim != 2 or lp.shape[0] != S):
+            raise ValueError("log_profiles must be (%d, D)" % S)
+        tr, pi = np.ascontiguousarray(trans, dtype=np.float64), np.ascontiguousarray(init, dtype=np.float64)
+        qt, qp = np.ascontiguousarray(qlog_trans, dtype=np.int64), np.ascontiguousarray(qlog_init, dtype=np.int64)
+        if tr.shape != (S, S) or pi.shape != (S,) or qt.shape != (S, S) or qp.shape != (S,):
+            raise ValueError("trans must be (%d, %d) and init (%d,), with their quantised logarithms" % (S, S, S))
+        self._rc(self.ctx.lib.phk_chain_set(self.ctx.handle, self.handle, ptr(lp), 0 if lp is None else lp.shape[1], ptr(tr),
+                                            ptr(pi), ptr(qt), ptr(qp), float(temper)))
+
+    def emissions(self):
+        """E (n, S) float64 as the device holds it (phk_chain_emissions)."""
+        self._open()
+        E = np.zeros((self.n, self.S), dtype=np.float64)
+        self._rc(self.ctx.lib.phk_chain_emissions(self.ctx.handle, self.handle, ptr(E)))
+        return E
+
+    def expect(self, records=False):
+        """One E-step (phk_chain_expect): (T (S, D), Ns (S,), xi (S, S), gamma0 (S,), log_evidence), and with ``records`` also
+        the log evidence per record (R,).  T and Ns are None for a chain made from emissions."""
+        self._open()
+        S = self.S
+        want = self.from_counts
+        T, Ns = (np.zeros((S, self.D)), np.zeros(S)) if want else (None, None)
+        xi, g0, L = np.zeros((S, S)), np.zeros(S), np.zeros(1)
+        rec = np.zeros(self.R) if records else None
+        self._rc(self.ctx.lib.phk_chain_expect(self.ctx.handle, self.handle, ptr(T), ptr(Ns), ptr(xi), ptr(g0), ptr(L), ptr(rec)))
+        return (T, Ns, xi, g0, float(L[0])) + ((rec,) if records else ())
+
+    def decode(self, posterior=True):
+        """(state (n,) uint8, posterior (n, S) or None, log_evidence (R,), path_score (R,) int64) (phk_chain_decode)."""
+        self._open()
+        state = np.zeros(self.n, dtype=np.uint8)
+        post = np.zeros((self.n, self.S)) if posterior else None
+        le, ps = np.zeros(self.R), np.zeros(self.R, dtype=np.int64)
+        self._rc(self.ctx.lib.phk_chain_decode(self.ctx.handle, self.handle, ptr(state), ptr(post), ptr(le), ptr(ps)))
+        return state, post, le, ps
 
 
 class Batch(_Resident):

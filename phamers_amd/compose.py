@@ -1,0 +1,440 @@
+"""
+compose.py -- reference-free segmentation of sequences by composition: an S-state hidden Markov chain whose states emit the
+k-mer count rows of windows, fitted to the sequence itself by Baum-Welch (this project's own).
+
+``windows`` scores windows against two references and ``segment`` decodes a two-state chain over such scores; ``mixture``
+fits multinomial profiles to count rows but treats the rows as exchangeable.  Here neighbouring windows share a state:
+
+    E[t][s]   = temper * sum_j c_t[j] log theta_s[j]              the emission of window t in state s (device, chain.hip)
+    gamma, xi = the posteriors of the chain (A, pi) over E          forward-backward per record (device)
+    T[s][j]   = sum_t gamma_t(s) c_t[j]     N_s = sum_t gamma_t(s)                          (device)
+    theta_s   = (T_s + a) / (sum_j T_s[j] + D a)     A_ij = xi_ij / sum_j xi_ij             (``m_step``, NumPy)
+    F         = L + a sum_s sum_j log theta_s[j]     L = the log evidence of the records    (what the loop raises)
+
+The classic compositional segmentation of a genome (Churchill 1989; Nicolas et al. 2002): prophages, islands and chimeric
+joins of a scaffold show as runs of another state, without a reference.  window = step (windows that do not overlap) is the
+intended configuration; overlapping windows are tempered as ``segment.default_temper`` says.
+
+Two findings of the CPU study this module was built after:
+  * Starting from single random window rows (what ``mixture.start`` does) fails: on a 120 kb sequence of four pieces and
+    three compositions every one of four seeds ended about 2300 nats below the right optimum with dozens of spurious
+    regions.  ``start`` therefore pools blocks of consecutive windows and picks them farthest-first; it is the default.
+  * A state too many does not stay empty: on a sequence of two compositions S = 3 splits off windows by sampling noise,
+    because overlapping k-mers are over-dispersed against a multinomial.  S is the caller's choice; the evidence and a BIC
+    are reported per fit and promise nothing, as in ``mixture.sweep``.
+
+    start(counts, offsets, n_states, block, pseudocount)        (log_profiles (S, D), block indices)
+    m_step(T, xi, gamma0, pseudocount, prior_counts, p_start)   (log_profiles, trans, init)
+    fit(counts_or_batch, owner_or_offsets, n_states, ...)       a Composition
+    segment_sequences(fasta_or_sequences, n_states, ...)        a ComposedSequences (fit + decode of the windows)
+    load(path)                                                  a Composition saved with Composition.save
+    python -m phamers_amd.compose -in FASTA -out DIR -S n
+"""
+import collections
+import os
+
+import numpy as np
+
+from . import _lib
+from .likelihood import _count_rows, _pseudocount
+from .segment import QUANT_BITS, _offsets, default_temper, quantise
+
+MAX_STATES = _lib.CHAIN_MAX_STATES
+P_MIN = 1e-12
+TRACE_COLUMNS = ("L", "F")
+
+Decoded = collections.namedtuple("Decoded", "state posterior log_evidence path_score path_score_q")
+Decoded.__doc__ = """state (n,) uint8, posterior (n, S) float64, log_evidence (R,) float64, path_score (R,) float64 nats
+= path_score_q (R,) int64 * 2^-16."""
+
+
+def _states(n_states):
+    S = int(n_states)
+    if not 2 <= S <= MAX_STATES:
+        raise ValueError("n_states must be 2 to %d, got %r" % (MAX_STATES, n_states))
+    return S
+
+
+def _temper(temper):
+    t = float(temper)
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError("temper must be finite and > 0, got %r" % (temper,))
+    return t
+
+
+def _blocks(counts, offsets, block):
+    """Pooled counts (n_blocks, D) int64 of every record's blocks of ``block`` consecutive windows."""
+    block = int(block)
+    if block < 1:
+        raise ValueError("block must be >= 1, got %r" % (block,))
+    off = [int(o) for o in np.asarray(offsets)]
+    c = np.asarray(counts).astype(np.int64)
+    rows = [c[s:min(s + block, b)].sum(axis=0) for a, b in zip(off[:-1], off[1:]) for s in range(a, b, block)]
+    return np.array(rows, dtype=np.int64).reshape(len(rows), c.shape[1])
+
+
+def _smooth(rows, a):
+    rows = np.asarray(rows, dtype=np.float64)
+    return np.log((rows + a) / (rows.sum(axis=1, keepdims=True) + rows.shape[1] * a))
+
+
+def start(counts, offsets, n_states, block=20, pseudocount=0.5):
+    """The deterministic start: every record is cut into blocks of ``block`` consecutive windows (never across records),
+    their counts pooled, blocks without k-mers left out.  The first block is chosen; then, S - 1 times, the block whose
+    best per-k-mer log-likelihood under the smoothed profiles of the chosen blocks is lowest (ties: the lowest index).
+    (log_profiles (S, D) of the chosen blocks, their indices).  NumPy on the host."""
+    c = _count_rows(counts, "counts")
+    return _start(c, _offsets(offsets, len(c)), n_states, block, pseudocount)
+
+
+def _start(c, offsets, n_states, block, pseudocount):
+    S, a = _states(n_states), _pseudocount(pseudocount)
+    P = _blocks(c, offsets, block)
+    tot = P.sum(axis=1)
+    live = np.flatnonzero(tot > 0)
+    if len(live) < S:
+        raise ValueError("n_states = %d exceeds the %d blocks of %d windows with k-mers" % (S, len(live), int(block)))
+    Pl = P[live].astype(np.float64)
+    chosen = [0]
+    while len(chosen) < S:
+        best = (Pl @ _smooth(Pl[chosen], a).T).max(axis=1) / tot[live]
+        best[chosen] = np.inf
+        chosen.append(int(np.argmin(best)))
+    return _smooth(P[live[chosen]], a), [int(live[i]) for i in chosen]
+
+
+def _normalised(v, keep):
+    s = v.sum()
+    if not s > 0:
+        if keep is None:
+            raise ValueError("a row without expected counts needs the values it keeps (trans= / init=)")
+        return np.array(keep, dtype=np.float64)
+    p = np.maximum(v / s, P_MIN)
+    return p / p.sum()
+
+
+def m_step(T, xi, gamma0, pseudocount, prior_counts=0.0, p_start='fixed', trans=None, init=None):
+    """(log_profiles (S, D), trans (S, S), init) from the expected counts.  Profiles: ``mixture.m_step``'s formula.
+    A_ij = (xi_ij + c_ij) / sum_j (xi_ij + c_ij) with c = ``prior_counts`` (a scalar or (S, S)), every entry raised to
+    >= 1e-12 and the row divided by its sum again; a row whose denominator is 0 keeps ``trans``'s.  ``p_start='fixed'``
+    returns ``init`` as it is, ``'free'`` gamma0 normalised and clamped the same way.  One NumPy operation per sign."""
+    a = _pseudocount(pseudocount)
+    T, xi = np.asarray(T, dtype=np.float64), np.asarray(xi, dtype=np.float64)
+    if T.ndim != 2 or xi.shape != (T.shape[0], T.shape[0]):
+        raise ValueError("T must be (S, D) and xi (S, S)")
+    if p_start not in ('fixed', 'free'):
+        raise ValueError("p_start must be 'fixed' or 'free'")
+    S = T.shape[0]
+    logp = np.log((T + a) / (T.sum(axis=1, keepdims=True) + T.shape[1] * a))
+    x = xi + np.broadcast_to(np.asarray(prior_counts, dtype=np.float64), (S, S))
+    A = np.array([_normalised(x[i], None if trans is None else np.asarray(trans)[i]) for i in range(S)])
+    pi = init if p_start == 'fixed' else _normalised(np.asarray(gamma0, dtype=np.float64), init)
+    return logp, A, pi
+
+
+def start_chain(n_states, mean_region=30000, step=500):
+    """(trans, init): 1 - step / mean_region on the diagonal, the rest shared equally; pi uniform."""
+    S = _states(n_states)
+    stay = 1.0 - float(step) / float(mean_region)
+    if not 0.0 < stay < 1.0:
+        raise ValueError("mean_region must exceed step")
+    A = np.full((S, S), (1.0 - stay) / (S - 1))
+    np.fill_diagonal(A, stay)
+    return A, np.full(S, 1.0 / S)
+
+
+class _DeviceEStep(object):
+    """The device half of a fit or of a decode: the rows resident once in a ``_lib.Chain``."""
+
+    def __init__(self, counts_or_batch, offsets, n_states, batch_rows=0):
+        self.ctx = _lib.get_context()
+        self.batch = counts_or_batch if isinstance(counts_or_batch, _lib.Batch) else None
+        self.host = None if self.batch is not None else _count_rows(counts_or_batch, "counts")
+        self.n = self.batch.n if self.batch is not None else len(self.host)
+        self.D = self.batch.D if self.batch is not None else self.host.shape[1]
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)      # (resolved by the caller: _record_offsets)
+        self.chain = _lib.Chain(self.ctx, self.batch if self.batch is not None else self.host, self.offsets, n_states, batch_rows)
+
+    def counts(self):
+        """uint32 count rows on the host (the start rule)."""
+        if self.host is None:
+            self.host = self.batch.counts_u32()
+        return self.host
+
+    def _set(self, log_profiles, trans, init, temper):
+        self.chain.set(log_profiles, trans, init, quantise(np.log(trans)), quantise(np.log(init)), temper)
+
+    def __call__(self, log_profiles, trans, init, temper):
+        """(T, Ns, xi, gamma0, L) of one E-step."""
+        self._set(log_profiles, trans, init, temper)
+        return self.chain.expect()
+
+    def decode(self, log_profiles, trans, init, temper):
+        self._set(log_profiles, trans, init, temper)
+        return self.chain.decode()
+
+    def close(self):
+        self.chain.close()
+
+
+def _estep(counts_or_batch, offsets, n_states, batch_rows=0):
+    """The E-step object of the rows (the tests put the statement in its place)."""
+    return _DeviceEStep(counts_or_batch, offsets, n_states, batch_rows)
+
+
+class _KnownOffsets(object):
+    """Offsets (R + 1,) that are not to be read as owners whatever their length (segment_sequences)."""
+
+    def __init__(self, offsets):
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+
+
+def _record_offsets(counts_or_batch, owner_or_offsets):
+    if isinstance(owner_or_offsets, _KnownOffsets):
+        return owner_or_offsets.offsets
+    n = counts_or_batch.n if isinstance(counts_or_batch, _lib.Batch) else len(_count_rows(counts_or_batch, "counts"))
+    return _offsets(owner_or_offsets, n)
+
+
+class Composition(object):
+    """A fitted chain: ``log_profiles`` (S, D), ``trans`` (S, S), ``init`` (S,), ``temper``, ``pseudocount``; of the last
+    E-step ``occupancy`` (N_s) and ``expected_counts`` (T); ``trace`` (iterates, 2): L and F; ``n_iter`` (M-steps),
+    ``converged``, ``bic``.  A state with N_s = 0 has the uniform profile: ``empty`` (S,) bool reports it."""
+
+    def __init__(self, log_profiles, trans, init, temper=1.0, pseudocount=0.5, occupancy=None, expected_counts=None, trace=None,
+                 n_iter=0, converged=False, bic=np.nan):
+        self.log_profiles = np.ascontiguousarray(log_profiles, dtype=np.float64)
+        self.trans = np.ascontiguousarray(trans, dtype=np.float64)
+        self.init = np.ascontiguousarray(init, dtype=np.float64)
+        S = self.log_profiles.shape[0]
+        if self.log_profiles.ndim != 2 or self.trans.shape != (S, S) or self.init.shape != (S,):
+            raise ValueError("log_profiles must be (S, D), trans (S, S) and init (S,)")
+        _states(S)
+        self.temper, self.pseudocount = _temper(temper), float(pseudocount)
+        self.occupancy = np.full(S, np.nan) if occupancy is None else np.asarray(occupancy, dtype=np.float64)
+        self.expected_counts = (np.full(self.log_profiles.shape, np.nan) if expected_counts is None
+                                else np.asarray(expected_counts, dtype=np.float64))
+        self.trace = np.zeros((0, 2)) if trace is None else np.asarray(trace, dtype=np.float64).reshape(-1, 2)
+        self.n_iter, self.converged, self.bic = int(n_iter), bool(converged), float(bic)
+
+    @property
+    def n_states(self):
+        return self.log_profiles.shape[0]
+
+    @property
+    def empty(self):
+        return self.occupancy == 0
+
+    def decode(self, counts_or_batch, owner_or_offsets):
+        """The Viterbi path, the posteriors (n, S), the log evidence per record and the path score of count rows (or a
+        resident batch) cut into records by ``owner_or_offsets`` (see ``segment.decode``): a ``Decoded``."""
+        offsets = _record_offsets(counts_or_batch, owner_or_offsets)
+        estep = _estep(counts_or_batch, offsets, self.n_states)
+        try:
+            if estep.D != self.log_profiles.shape[1]:
+                raise ValueError("the counts have %d columns, the composition %d" % (estep.D, self.log_profiles.shape[1]))
+            state, post, le, ps = estep.decode(self.log_profiles, self.trans, self.init, self.temper)
+        finally:
+            estep.close()
+        return Decoded(state, post, le, ps.astype(np.float64) * 2.0 ** -QUANT_BITS, ps)
+
+    def label(self, positive_counts, negative_counts):
+        """(S,) float64: ``likelihood.score(..., per_kmer=True)`` of every state's rint(T_s) row against the two
+        references -- positive for a state whose composition is the positive class's (nan for an empty state)."""
+        from . import likelihood
+        rows = np.rint(self.expected_counts)
+        if not np.isfinite(rows).all():
+            raise ValueError("this composition has no expected counts (it was not fitted)")
+        return likelihood.score(rows.astype(np.uint32), positive_counts, negative_counts, self.pseudocount, per_kmer=True)
+
+    def save(self, path):
+        """A ``.npz`` file that ``load`` reads back."""
+        with open(path, 'wb') as f:
+            np.savez(f, log_profiles=self.log_profiles, trans=self.trans, init=self.init, temper=self.temper,
+                     pseudocount=self.pseudocount, occupancy=self.occupancy, expected_counts=self.expected_counts,
+                     trace=self.trace, n_iter=self.n_iter, converged=self.converged, bic=self.bic)
+
+
+def load(path):
+    """The Composition of a file written by ``Composition.save``."""
+    with np.load(path) as z:
+        return Composition(z["log_profiles"], z["trans"], z["init"], float(z["temper"]), float(z["pseudocount"]), z["occupancy"],
+                           z["expected_counts"], z["trace"], int(z["n_iter"]), bool(z["converged"]), float(z["bic"]))
+
+
+def _initial_profiles(estep, S, init, block, a):
+    if init is None:
+        return _start(estep.counts(), estep.offsets, S, block, a)[0]
+    init = np.asarray(init)
+    if init.ndim == 2:
+        p = np.asarray(init, dtype=np.float64)
+        if p.shape != (S, estep.D) or not (np.isfinite(p).all() and (p > 0).all()):
+            raise ValueError("init profiles must be (%d, %d), finite and > 0" % (S, estep.D))
+        return np.log(p / p.sum(axis=1, keepdims=True))
+    P = _blocks(estep.counts(), estep.offsets, block)
+    if init.shape != (S,) or not np.issubdtype(init.dtype, np.integer) or init.min() < 0 or init.max() >= len(P):
+        raise ValueError("init must be %d block indices below %d, or (S, D) profiles" % (S, len(P)))
+    return _smooth(P[init], a)
+
+
+def fit(counts_or_batch, owner_or_offsets, n_states, mean_region=30000, step=500, temper=1.0, pseudocount=0.5, init=None,
+        block=20, prior_counts=0, fit_transitions=True, p_start='fixed', max_iter=100, tol=1e-6):
+    """An S-state chain fitted by Baum-Welch to the count rows ``counts_or_batch`` ((n, D) integers, made resident once, or
+    a ``_lib.Batch``, read where it lies) cut into records by ``owner_or_offsets`` (see ``segment.decode``).  The profiles
+    start from ``start`` (``init``: S block indices or (S, D) profiles instead), the chain from ``start_chain``.  The loop
+    is ``mixture``'s: it stops at the first iterate with F_i - F_{i-1} <= tol max(1, |F_i|) or after ``max_iter`` M-steps.
+    ``fit_transitions=False`` keeps the start chain.  gamma and E never leave the device.  A ``Composition``."""
+    S, a, t = _states(n_states), _pseudocount(pseudocount), _temper(temper)
+    max_iter, tol = int(max_iter), float(tol)
+    if max_iter < 0 or not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("max_iter >= 0 and a finite tol >= 0 are required")
+    if p_start not in ('fixed', 'free'):
+        raise ValueError("p_start must be 'fixed' or 'free'")
+    A, pi = start_chain(S, mean_region, step)
+    offsets = _record_offsets(counts_or_batch, owner_or_offsets)
+    estep = _estep(counts_or_batch, offsets, S)
+    try:
+        logp = _initial_profiles(estep, S, init, block, a)
+        trace, F_prev, converged = [], None, False
+        for it in range(max_iter + 1):
+            T, Ns, xi, g0, L = estep(logp, A, pi, t)
+            F = float(L) + a * float(np.sum(logp))
+            trace.append((L, F))
+            if F_prev is not None and F - F_prev <= tol * max(1.0, abs(F)):
+                converged = True
+                break
+            if it == max_iter:
+                break
+            F_prev = F
+            logp, A2, pi2 = m_step(T, xi, g0, a, prior_counts, p_start, A, pi)
+            if fit_transitions:
+                A, pi = A2, pi2
+        n = estep.n
+    finally:
+        estep.close()
+    free = S * (logp.shape[1] - 1) + (S * (S - 1) if fit_transitions else 0) + (S - 1 if p_start == 'free' else 0)
+    bic = -2.0 * float(trace[-1][0]) + free * float(np.log(max(n, 1)))
+    return Composition(logp, A, pi, t, a, Ns, T, np.array(trace, dtype=np.float64), len(trace) - 1, converged, bic)
+
+
+class ComposedSequences(object):
+    """What ``segment_sequences`` returns: ``composition``; the windows' ``record_ids``, ``owner``, ``start``, ``window``,
+    ``step``; ``state`` (n,), ``posterior`` (n, S); ``log_evidence`` and ``path_score`` per record."""
+
+    def __init__(self, composition, record_ids, owner, start, window, step, decoded):
+        self.composition, self.record_ids, self.owner, self.start = composition, list(record_ids), owner, start
+        self.window, self.step = int(window), int(step)
+        self.state, self.posterior = decoded.state, decoded.posterior
+        self.log_evidence, self.path_score = decoded.log_evidence, decoded.path_score
+
+    def __len__(self):
+        return self.state.shape[0]
+
+    def regions(self):
+        """Per run of consecutive windows of one record in one state: ``(record id, start of the first window, start of the
+        last + window, state, n_windows, mean posterior of that state)``, ordered by record and start."""
+        n = len(self)
+        if n == 0:
+            return []
+        joined = (self.state[1:] == self.state[:-1]) & (self.owner[1:] == self.owner[:-1])
+        first = np.flatnonzero(np.concatenate(([True], ~joined)))
+        last = np.flatnonzero(np.concatenate((~joined, [True])))
+        return [(self.record_ids[int(self.owner[a])], int(self.start[a]), int(self.start[b]) + self.window, int(self.state[a]),
+                 int(b - a + 1), float(self.posterior[a:b + 1, int(self.state[a])].mean())) for a, b in zip(first, last)]
+
+
+def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_length=4, both_strands=False, **fit_options):
+    """Counts the windows of a FASTA file (or a list of strings) as one resident batch, fits ``n_states`` compositions to
+    them and decodes: a ``ComposedSequences``.  ``temper`` defaults to ``segment.default_temper(window, step, k)``; the other
+    ``fit_options`` are ``fit``'s (``step`` is passed on).  ValueError when no sequence holds a window."""
+    from . import kmer
+    both_strands = kmer._check_strands(kmer.DNA, both_strands)
+    record_ids, lengths, batch = kmer._windows_batch(fasta_or_sequences, kmer_length, window, step)
+    if batch is None:
+        raise ValueError("no sequence is as long as the window (%d)" % int(window))
+    try:
+        if both_strands:
+            batch.fold_strands()
+        owner, first = kmer.window_plan(lengths, window, step)
+        fit_options.setdefault("temper", default_temper(window, step, kmer_length))
+        offsets = _KnownOffsets(np.concatenate(([0], np.cumsum(np.bincount(owner, minlength=len(record_ids))))))
+        comp = fit(batch, offsets, n_states, step=step, **fit_options)
+        decoded = comp.decode(batch, offsets)
+    finally:
+        batch.close()
+    return ComposedSequences(comp, record_ids, owner, first, window, step, decoded)
+
+
+# ---- command line ---------------------------------------------------------------------------------------------------------
+def _parser():
+    import argparse
+    ap = argparse.ArgumentParser(description="Segment sequences by composition: an S-state chain fitted to their windows",
+                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ap.add_argument('-in', '--input_file', required=True, help="FASTA file")
+    ap.add_argument('-out', '--output_directory', required=True, help="Directory of the four CSV files")
+    ap.add_argument('-S', '--states', type=int, required=True, help="States of the chain (2 to 8)")
+    ap.add_argument('-w', '--window', type=int, default=500, help="Window length in bases")
+    ap.add_argument('-s', '--step', type=int, default=500, help="Bases between window starts (window = step is intended)")
+    ap.add_argument('-k', '--kmer_length', type=int, default=4, help="k-mer length")
+    ap.add_argument('--both_strands', action='store_true', help="Count every window with its reverse complement")
+    ap.add_argument('--mean_region', type=float, default=30000, help="Mean region length in bases of the start chain")
+    ap.add_argument('--temper', type=float, default=None, help="Exponent of the emissions (default: by window and step)")
+    ap.add_argument('--block', type=int, default=20, help="Windows per block of the start rule")
+    ap.add_argument('--max_iter', type=int, default=100, help="Most M-steps")
+    ap.add_argument('--tol', type=float, default=1e-6, help="Relative gain of the evidence below which the loop stops")
+    ap.add_argument('--keep_transitions', action='store_true', help="Do not fit the transition probabilities")
+    ap.add_argument('-pf', '--positive_features', default=None, help="Count file of the positive reference (labels the states)")
+    ap.add_argument('-nf', '--negative_features', default=None, help="Count file of the negative reference")
+    return ap
+
+
+def write_files(directory, result, phage_score=None):
+    """compose_windows.csv, compose_segments.csv, compose_profiles.csv and compose_trace.csv of a ``ComposedSequences``."""
+    os.makedirs(directory, exist_ok=True)
+    comp = result.composition
+    S, D = comp.log_profiles.shape
+    with open(os.path.join(directory, "compose_windows.csv"), 'w') as f:
+        f.write("record_id,start,state," + ",".join("posterior%d" % s for s in range(S)) + "\n")
+        for i in range(len(result)):
+            f.write("%s,%d,%d,%s\n" % (result.record_ids[int(result.owner[i])], int(result.start[i]), int(result.state[i]),
+                                       ",".join(repr(float(v)) for v in result.posterior[i])))
+    with open(os.path.join(directory, "compose_segments.csv"), 'w') as f:
+        f.write("record_id,start,end,state,n_windows,mean_posterior\n")
+        for rid, a, b, s, nw, mp in result.regions():
+            f.write("%s,%d,%d,%d,%d,%r\n" % (rid, a, b, s, nw, mp))
+    with open(os.path.join(directory, "compose_profiles.csv"), 'w') as f:
+        f.write("state,occupancy,self_transition,mean_region," + ("phage_score," if phage_score is not None else "")
+                + ",".join("p%d" % j for j in range(D)) + "\n")
+        for s in range(S):
+            stay = float(comp.trans[s, s])
+            f.write("%d,%r,%r,%r,%s%s\n" % (s, float(comp.occupancy[s]), stay, result.step / (1.0 - stay),
+                                            ("%r," % float(phage_score[s])) if phage_score is not None else "",
+                                            ",".join(repr(float(v)) for v in np.exp(comp.log_profiles[s]))))
+    with open(os.path.join(directory, "compose_trace.csv"), 'w') as f:
+        f.write("iteration," + ",".join(TRACE_COLUMNS) + "\n")
+        for i, (L, F) in enumerate(comp.trace):
+            f.write("%d,%r,%r\n" % (i, float(L), float(F)))
+
+
+def main(argv=None):
+    args = _parser().parse_args(argv)
+    if (args.positive_features is None) != (args.negative_features is None):
+        raise SystemExit("-pf and -nf go together")
+    options = dict(mean_region=args.mean_region, block=args.block, max_iter=args.max_iter, tol=args.tol,
+                   fit_transitions=not args.keep_transitions)
+    if args.temper is not None:
+        options["temper"] = args.temper
+    result = segment_sequences(args.input_file, args.states, args.window, args.step, args.kmer_length, args.both_strands,
+                               **options)
+    score = None
+    if args.positive_features is not None:
+        from . import fileIO
+        pos = fileIO.read_feature_file(args.positive_features, normalize=False)[1]
+        neg = fileIO.read_feature_file(args.negative_features, normalize=False)[1]
+        score = result.composition.label(pos, neg)
+    write_files(args.output_directory, result, score)
+    return result
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,668 @@
+// chain.hip -- S-state hidden Markov chain over the count rows of windows (gfx950): this project's own, DESIGN.md 4.26.
+//
+// Records r have windows t = offsets[r] .. offsets[r + 1] - 1 with uint32 count rows c_t[D]; S states (2 .. PHK_CHAIN_MAX_STATES)
+// with log profiles log theta_s[D] (host logarithms), transition A[S][S], start pi[S]:
+//     E[t][s] = temper * sum_j c_t[j] log theta_s[j]        (gram_tile on the fp64 matrix pipe, one multiply afterwards)
+//     d[t][s] = E[t][s] - max_s' E[t][s']  <= 0             (the relative emission; a window without k-mers has d = 0)
+// Every result of a record is a function of its own rows and the parameters: not of the call's other records, its place
+// among them, batch_rows, the entry point, the launch or the run.
+//
+// A record is carried by a GROUP of SP lanes (SP = S padded to 2, 4 or 8; 64 / SP records per wave), lane j = state j; a padded
+// state has A = 0, pi = 0 and emission 0, which adds exact zeros.  Cross-lane traffic is __shfl within the group; sums over
+// the states run in state order 0 .. SP - 1 in every lane alike.  No LDS, no barrier.
+//   phk_chain_emit_kernel      E and the row maximum M from the count rows (the shape of phk_mix_resp_kernel's first half)
+//   phk_chain_rowmax_kernel    M of emissions that came from the host (phk_chain_create_from_emissions)
+//   phk_chain_backward_kernel  beta_t of every step, right to left, rescaled by powers of two (exact), into B[n][S]
+//   phk_chain_forward_kernel   alpha left to right (rescaled likewise, the exponent kept as an integer); in step order: the
+//                              step's S^2 terms w_ij = alpha_{t-1}(i) A_ij e_t(j) beta_t(j) normalised by their own sum, added
+//                              to xi; gamma_t(j) = the column sum over that sum (step 0: pi_j e_0(j) beta_0(j) normalised);
+//                              the record's vector (xi, gamma_0, log evidence) into V[R][S^2 + S + 1]
+//   phk_chain_viterbi_kernel   max-plus on int64 over q[t][s] = rint(max(d, -2^15) 2^16), ties to the smallest predecessor; the
+//                              backpointers of a step as the bytes of one 64-bit word; path_score and the last state (a tie to
+//                              the smallest state)
+//   phk_chain_trace_kernel     lane per record: the path, right to left through the words
+//   phk_chain_spread_kernel    gamma [rows][S] -> [rows][64] (zeros past S): the R operand of mix_expect_body
+//   phk_chain_expect_kernel    T = gamma^T C and N_s: mix_expect_body (mixture_body.h), blocks of MIX_RB rows anchored at the
+//                              global row index
+//   phk_chain_fold_kernel      mix_fold_body: the fixed 256-row tree, over the row blocks' partial vectors and over the records'
+//                              vectors alike
+// The integer sums: |q| <= 2^31 and |qlog| <= 2^31 (checked), so a path over n <= 2^30 windows stays inside 2^62.
+// The float sums stay away from 0 / 0 as long as the ratio of two entries of a row or column of A stays inside the format
+// (entries of 1e-12 are tested): the largest entry of a rescaled vector is in [1/2, 1) and the state of the largest emission
+// has e = 1, so every normalising sum is at least min(A) / 2 times a positive normal number.
+#include <algorithm>
+#include <cmath>
+
+#include "mixture_body.h"
+
+#define CH_BLOCKS_MAX 1024      // 64-lane workgroups per launch of the per-record kernels
+#define CH_CLAMP 32768.0
+#define CH_LN2 0.693147180559945309417232121458
+#define CH_KP MIX_CT            // row stride of the spread gamma
+#define CH_QMAX (1ll << 31)
+#define CH_NMAX (1ull << 30)
+
+static_assert(PHK_CHAIN_MAX_STATES == 8, "a step's backpointers are the bytes of one 64-bit word");
+
+template <bool FULL>
+__global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_chain_emit_kernel(const uint32_t *__restrict__ C, uint64_t nq,
+                                                                        const double *__restrict__ L, uint32_t S, uint64_t D,
+                                                                        double temper, double *__restrict__ E,
+                                                                        double *__restrict__ M) {
+    const int li = threadIdx.x & 15, wave = threadIdx.x >> 6;
+    const uint64_t q0 = (uint64_t)blockIdx.x * GT_QB + (uint64_t)wave * (GT_QT * 16);
+    f64x4 acc[GT_QT][GT_RT];
+    gram_tile<FULL, GT_QT, uint32_t>(C, nq, q0, L, S, 0, D, acc);   // S <= 8: the states are rows 0 .. S - 1 of row tile 0
+#pragma unroll
+    for (int a = 0; a < GT_QT; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double e = acc[a][0][r] * temper;
+            double m = (uint32_t)li < S ? e : -__builtin_inf();
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) m = fmax(m, __shfl_xor(m, o));
+            const uint64_t q = gram_query(q0, a, r);
+            if (q < nq) {
+                if ((uint32_t)li < S) E[q * S + li] = e;
+                if (li == 0) M[q] = m;
+            }
+        }
+}
+
+__global__ __launch_bounds__(256) void phk_chain_rowmax_kernel(const double *__restrict__ E, uint64_t n, uint32_t S,
+                                                               double *__restrict__ M) {
+    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (uint64_t)gridDim.x * 256) {
+        double m = E[t * S];
+        for (uint32_t s = 1; s < S; ++s) m = fmax(m, E[t * S + s]);
+        M[t] = m;
+    }
+}
+
+// the sum of v over the group's lanes in state order; every lane gets the same bits
+template <int SP>
+__device__ __forceinline__ double chain_sum(double v) {
+    double s = __shfl(v, 0, SP);
+#pragma unroll
+    for (int i = 1; i < SP; ++i) s += __shfl(v, i, SP);
+    return s;
+}
+
+// v / 2^e with e the exponent of the group's largest v: exact; returns e
+template <int SP>
+__device__ __forceinline__ int chain_scale2(double &v) {
+    double m = v;
+#pragma unroll
+    for (int o = 1; o < SP; o <<= 1) m = fmax(m, __shfl_xor(m, o, SP));
+    int e;
+    (void)frexp(m, &e);
+    v = ldexp(v, -e);
+    return e;
+}
+
+// par = A[S][S] then pi[S].  B[w][j] = beta_w(j) up to a power of two: beta of the record's last step is 1,
+// beta_{t-1}(i) = sum_j A_ij e_t(j) beta_t(j).
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_backward_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                                const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
+                                                                const double *__restrict__ par, double *__restrict__ B) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    double arow[SP];
+#pragma unroll
+    for (int i = 0; i < SP; ++i) arow[i] = (live && (uint32_t)i < S) ? par[j * S + i] : 0.0;
+    for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
+        const uint64_t w0 = off[r], w1 = off[r + 1];
+        if (w1 == w0) continue;
+        double b = live ? 1.0 : 0.0;
+        uint64_t w = w1 - 1;
+        double x = live ? E[w * S + j] - M[w] : 0.0;
+        for (;;) {
+            if (live) B[w * S + j] = b;
+            if (w == w0) break;
+            const double e = live ? exp(x) : 0.0;
+            --w;
+            x = live ? E[w * S + j] - M[w] : 0.0;   // the next step's load, issued ahead of this step's chain
+            const double u = e * b;
+            double nb = 0.0;
+#pragma unroll
+            for (int i = 0; i < SP; ++i) nb += arow[i] * __shfl(u, i, SP);
+            (void)chain_scale2<SP>(nb);
+            b = nb;
+        }
+    }
+}
+
+// G[w][j] = gamma_w(j); V[r] = xi[S][S], gamma_0[S], log evidence.
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_forward_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                               const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
+                                                               const double *__restrict__ par, const double *__restrict__ B,
+                                                               double *__restrict__ G, double *__restrict__ V) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    const uint64_t Ev = (uint64_t)S * S + S + 1;
+    double acol[SP];
+#pragma unroll
+    for (int i = 0; i < SP; ++i) acol[i] = (live && (uint32_t)i < S) ? par[(uint32_t)i * S + j] : 0.0;
+    const double pj = live ? par[S * S + j] : 0.0;
+    for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
+        const uint64_t w0 = off[r], w1 = off[r + 1];
+        double *out = V + r * Ev;
+        double xi[SP];
+#pragma unroll
+        for (int i = 0; i < SP; ++i) xi[i] = 0.0;
+        double g0 = 0.0, le = 0.0;
+        if (w1 > w0) {
+            double mw = M[w0];
+            double x = live ? E[w0 * S + j] - mw : 0.0, bw = live ? B[w0 * S + j] : 0.0;
+            double e = live ? exp(x) : 0.0;
+            double sm = mw;
+            int64_t ex = 0;
+            {
+                const double p = pj * (e * bw);
+                g0 = p / chain_sum<SP>(p);
+                if (live) G[w0 * S + j] = g0;
+            }
+            double a = pj * e;
+            ex += chain_scale2<SP>(a);
+            uint64_t w = w0 + 1;
+            if (w < w1) {
+                mw = M[w];
+                x = live ? E[w * S + j] - mw : 0.0, bw = live ? B[w * S + j] : 0.0;
+            }
+            while (w < w1) {
+                e = live ? exp(x) : 0.0;
+                const double c = e * bw;
+                sm += mw;
+                const uint64_t wn = w + 1;
+                if (wn < w1) {   // the next step's loads, issued ahead of this step's chain
+                    mw = M[wn];
+                    x = live ? E[wn * S + j] - mw : 0.0, bw = live ? B[wn * S + j] : 0.0;
+                }
+                double wv[SP], g = 0.0, col = 0.0;
+#pragma unroll
+                for (int i = 0; i < SP; ++i) {
+                    const double pr = __shfl(a, i, SP) * acol[i];
+                    g += pr;
+                    wv[i] = pr * c;
+                    col += wv[i];
+                }
+                const double inv = 1.0 / chain_sum<SP>(col);
+#pragma unroll
+                for (int i = 0; i < SP; ++i) xi[i] += wv[i] * inv;
+                if (live) G[w * S + j] = col * inv;
+                a = g * e;
+                ex += chain_scale2<SP>(a);
+                w = wn;
+            }
+            int e2;
+            const double m = frexp(chain_sum<SP>(a), &e2);
+            le = ((double)(ex + e2) * CH_LN2 + log(m)) + sm;
+        }
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < SP; ++i)
+                if ((uint32_t)i < S) out[(uint32_t)i * S + j] = xi[i];
+            out[S * S + j] = g0;
+            if (j == 0) out[S * S + S] = le;
+        }
+    }
+}
+
+__device__ __forceinline__ int64_t chain_quant(double d) { return (int64_t)rint(fmax(d, -CH_CLAMP) * 65536.0); }
+
+// qpar = qlog A[S][S] then qlog pi[S].  BP[8 w + j] = the predecessor of state j at step w (w > the record's first).
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_viterbi_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                               const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
+                                                               const int64_t *__restrict__ qpar, uint8_t *__restrict__ BP,
+                                                               int64_t *__restrict__ score, uint8_t *__restrict__ last) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    long long qcol[SP];
+#pragma unroll
+    for (int i = 0; i < SP; ++i) qcol[i] = (live && (uint32_t)i < S) ? (long long)qpar[(uint32_t)i * S + j] : 0ll;
+    const long long qp = live ? (long long)qpar[S * S + j] : 0ll;
+    for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
+        const uint64_t w0 = off[r], w1 = off[r + 1];
+        if (w1 == w0) {
+            if (j == 0) score[r] = 0, last[r] = 0;
+            continue;
+        }
+        long long d = qp + (live ? (long long)chain_quant(E[w0 * S + j] - M[w0]) : 0ll);
+        uint64_t w = w0 + 1;
+        double x = (live && w < w1) ? E[w * S + j] - M[w] : 0.0;
+        while (w < w1) {
+            const long long q = (long long)chain_quant(x);
+            const uint64_t wn = w + 1;
+            x = (live && wn < w1) ? E[wn * S + j] - M[wn] : 0.0;
+            long long best = __shfl(d, 0, SP) + qcol[0];
+            uint32_t k = 0;
+#pragma unroll
+            for (int i = 1; i < SP; ++i) {
+                const long long c = __shfl(d, i, SP) + qcol[i];
+                if ((uint32_t)i < S && c > best) best = c, k = (uint32_t)i;   // a tie stays with the smaller predecessor
+            }
+            d = best + q;
+            BP[8 * w + j] = (uint8_t)k;
+            w = wn;
+        }
+        long long best = __shfl(d, 0, SP);
+        uint32_t k = 0;
+#pragma unroll
+        for (int i = 1; i < SP; ++i) {
+            const long long c = __shfl(d, i, SP);
+            if ((uint32_t)i < S && c > best) best = c, k = (uint32_t)i;
+        }
+        if (j == 0) score[r] = (int64_t)best, last[r] = (uint8_t)k;
+    }
+}
+
+__global__ __launch_bounds__(64) void phk_chain_trace_kernel(const uint64_t *__restrict__ off, uint64_t R,
+                                                             const uint8_t *__restrict__ last, const uint64_t *__restrict__ BP,
+                                                             uint8_t *__restrict__ state) {
+    for (uint64_t r = (uint64_t)blockIdx.x * 64 + threadIdx.x; r < R; r += (uint64_t)gridDim.x * 64) {
+        const uint64_t w0 = off[r];
+        uint32_t s = last[r];
+#pragma unroll 8
+        for (uint64_t w = off[r + 1]; w > w0; --w) {
+            state[w - 1] = (uint8_t)s;
+            s = (uint32_t)(BP[w - 1] >> (8 * s)) & 0xffu;   // (the word of the record's first step is not followed)
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void phk_chain_spread_kernel(const double *__restrict__ G, uint64_t nb, uint32_t S,
+                                                               double *__restrict__ Rx) {
+    const uint64_t total = nb * CH_KP;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t c = (uint32_t)(i % CH_KP);
+        Rx[i] = c < S ? G[(i / CH_KP) * S + c] : 0.0;
+    }
+}
+
+// grid: x = row block of the batch, y = group of four column tiles; see phk_mix_expect_kernel
+template <bool VEC>
+__global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_chain_expect_kernel(const double *__restrict__ Rx,
+                                                                          const uint32_t *__restrict__ C, uint64_t D, uint64_t nb,
+                                                                          const double *__restrict__ M, uint32_t S, uint64_t Em,
+                                                                          double *__restrict__ part) {
+    mix_expect_body<VEC>(Rx, CH_KP, C, D, nb, M, S, blockIdx.x, blockIdx.y, 0, part + (uint64_t)blockIdx.x * Em);
+}
+
+__global__ __launch_bounds__(256) void phk_chain_fold_kernel(const double *__restrict__ in, uint64_t m, uint64_t Ev,
+                                                             double *__restrict__ out) {
+    mix_fold_body(in, m, Ev, blockIdx.x, blockIdx.y, out + (uint64_t)blockIdx.y * Ev);
+}
+
+extern "C" uint64_t phk_chain_grid_pass(void) { return (uint64_t)CH_BLOCKS_MAX * 32; }
+
+// ---- the resident chain ------------------------------------------------------------------------------------------------
+struct phk_chain {
+    uint64_t n = 0, R = 0, D = 0, B = 0;   // B: rows per batch of the emission and expectation passes
+    uint32_t S = 0;
+    bool from_counts = false, ready = false;
+    const uint32_t *counts = nullptr;      // the batch's rows, or own_counts
+    PhkDevMem own_counts, off, E, M, Bt, G, BP, state, par, qpar, logp, V, last, score, Rx, part, fold[2];
+};
+
+static unsigned chain_grid(uint64_t items, uint64_t per_block, uint64_t cap) {
+    const uint64_t b = phk_div_up(items, per_block);
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+static int chain_check_shape(const char *who, uint64_t n, const uint64_t *offsets, uint64_t R, uint32_t S) {
+    PHK_REQUIRE(S >= 2 && S <= PHK_CHAIN_MAX_STATES, "%s: %u states (2 to %d)", who, S, PHK_CHAIN_MAX_STATES);
+    PHK_REQUIRE(n <= CH_NMAX && R < (1ull << 32), "%s: more than 2^30 windows or 2^32 records", who);
+    if (R == 0) {
+        PHK_REQUIRE(n == 0, "%s: %llu windows and no record", who, (unsigned long long)n);
+        return PHK_OK;
+    }
+    PHK_REQUIRE(offsets, "%s: NULL offsets", who);
+    PHK_REQUIRE(offsets[0] == 0 && offsets[R] == n, "%s: the offsets do not run from 0 to n", who);
+    for (uint64_t r = 0; r < R; ++r)
+        PHK_REQUIRE(offsets[r] <= offsets[r + 1], "%s: the offsets decrease at record %llu", who, (unsigned long long)r);
+    return PHK_OK;
+}
+
+static int chain_alloc(phk_ctx *ctx, const char *who, phk_chain *c, const uint64_t *offsets, uint64_t batch_rows) {
+    const uint64_t n = c->n, R = c->R, S = c->S, D = c->D, Ev = S * S + S + 1, Em = S * D + S + 1;
+    uint64_t B = (512ull << 20) / (CH_KP * sizeof(double));
+    B = B / MIX_RB * MIX_RB;
+    if (batch_rows) B = phk_div_up(batch_rows, MIX_RB) * MIX_RB;
+    c->B = B;
+    const uint64_t Brows = B > n ? n : B, nblocks = phk_div_up(n, MIX_RB);
+    const uint64_t fold_v = phk_div_up(R, 256) * Ev, fold_t = c->from_counts ? phk_div_up(nblocks, 256) * Em : 0;
+    PHK_TRY(c->off.alloc(who, "offsets", (R + 1) * 8));
+    PHK_TRY(c->E.alloc(who, "emissions", n * S * 8));
+    PHK_TRY(c->M.alloc(who, "row maxima", n * 8));
+    PHK_TRY(c->Bt.alloc(who, "backward vectors", n * S * 8));
+    PHK_TRY(c->G.alloc(who, "posteriors", n * S * 8));
+    PHK_TRY(c->BP.alloc(who, "backpointers", n * 8));
+    PHK_TRY(c->state.alloc(who, "states", n));
+    PHK_TRY(c->par.alloc(who, "parameters", (S * S + S) * 8));
+    PHK_TRY(c->qpar.alloc(who, "parameters", (S * S + S) * 8));
+    PHK_TRY(c->V.alloc(who, "record vectors", R * Ev * 8));
+    PHK_TRY(c->last.alloc(who, "last states", R));
+    PHK_TRY(c->score.alloc(who, "path scores", R * 8));
+    PHK_TRY(c->fold[0].alloc(who, "fold vectors", std::max(fold_v, fold_t) * 8));
+    PHK_TRY(c->fold[1].alloc(who, "fold vectors", std::max(fold_v, fold_t) * 8));
+    if (c->from_counts) {
+        PHK_TRY(c->logp.alloc(who, "log profiles", S * D * 8));
+        PHK_TRY(c->Rx.alloc(who, "spread posteriors", Brows * CH_KP * 8));
+        PHK_TRY(c->part.alloc(who, "partial vectors", nblocks * Em * 8));
+    }
+    if (R) PHK_TRY(phk_copy_to_device(ctx, c->off.ptr, offsets, (R + 1) * 8));
+    return PHK_OK;
+}
+
+static int chain_finish_create(phk_ctx *ctx, phk_chain *c, int rc, phk_chain **out) {
+    if (rc == PHK_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        phk_set_error("phk_chain_create: the uploads failed");
+        rc = PHK_ERR_HIP;
+    }
+    if (rc != PHK_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return PHK_OK;
+}
+
+extern "C" int phk_chain_create(phk_ctx *ctx, const uint32_t *counts, uint64_t n, uint64_t D, const uint64_t *offsets, uint64_t R,
+                                uint32_t S, uint64_t batch_rows, phk_chain **out) {
+    PHK_ENTER(ctx, "phk_chain_create");
+    PHK_REQUIRE(out, "phk_chain_create: NULL out");
+    *out = nullptr;
+    PHK_TRY(chain_check_shape("phk_chain_create", n, offsets, R, S));
+    PHK_REQUIRE(D > 0 && D < (1ull << 32), "phk_chain_create: %llu columns", (unsigned long long)D);
+    PHK_REQUIRE(n == 0 || counts, "phk_chain_create: NULL counts");
+    phk_chain *c = new phk_chain();
+    c->n = n, c->R = R, c->D = D, c->S = S, c->from_counts = true;
+    int rc = c->own_counts.alloc("phk_chain_create", "count rows", n * D * 4);
+    if (rc == PHK_OK && n) rc = phk_copy_to_device(ctx, c->own_counts.ptr, counts, n * D * 4);
+    c->counts = c->own_counts.as<uint32_t>();
+    if (rc == PHK_OK) rc = chain_alloc(ctx, "phk_chain_create", c, offsets, batch_rows);
+    return chain_finish_create(ctx, c, rc, out);
+}
+
+extern "C" int phk_batch_chain_create(phk_ctx *ctx, const phk_batch *b, const uint64_t *offsets, uint64_t R, uint32_t S,
+                                      uint64_t batch_rows, phk_chain **out) {
+    PHK_ENTER(ctx, "phk_batch_chain_create");
+    PHK_REQUIRE(out, "phk_batch_chain_create: NULL out");
+    *out = nullptr;
+    PHK_REQUIRE(b, "phk_batch_chain_create: NULL batch");
+    PHK_TRY(chain_check_shape("phk_batch_chain_create", b->n, offsets, R, S));
+    PHK_REQUIRE(b->D > 0, "phk_batch_chain_create: a batch without columns");
+    phk_chain *c = new phk_chain();
+    c->n = b->n, c->R = R, c->D = b->D, c->S = S, c->from_counts = true;
+    c->counts = b->d_counts;   // read where they lie: the batch outlives the chain
+    return chain_finish_create(ctx, c, chain_alloc(ctx, "phk_batch_chain_create", c, offsets, batch_rows), out);
+}
+
+extern "C" int phk_chain_create_from_emissions(phk_ctx *ctx, const double *E, uint64_t n, const uint64_t *offsets, uint64_t R,
+                                               uint32_t S, phk_chain **out) {
+    PHK_ENTER(ctx, "phk_chain_create_from_emissions");
+    PHK_REQUIRE(out, "phk_chain_create_from_emissions: NULL out");
+    *out = nullptr;
+    PHK_TRY(chain_check_shape("phk_chain_create_from_emissions", n, offsets, R, S));
+    PHK_REQUIRE(n == 0 || E, "phk_chain_create_from_emissions: NULL emissions");
+    if (n && !phk_rows_finite(E, n * S)) {
+        phk_set_error("phk_chain_create_from_emissions: an emission is not finite");
+        return PHK_ERR_NAN;
+    }
+    phk_chain *c = new phk_chain();
+    c->n = n, c->R = R, c->D = 0, c->S = S, c->from_counts = false;
+    int rc = chain_alloc(ctx, "phk_chain_create_from_emissions", c, offsets, 0);
+    if (rc == PHK_OK && n) rc = phk_copy_to_device(ctx, c->E.ptr, E, n * S * 8);
+    if (rc == PHK_OK && n) {
+        rc = [&]() -> int {
+            PHK_LAUNCH(ctx, "phk_chain_rowmax_kernel",
+                       phk_chain_rowmax_kernel<<<dim3(chain_grid(n, 256, 4096)), dim3(256), 0, ctx->stream>>>(
+                           c->E.as<double>(), n, S, c->M.as<double>()));
+            return PHK_OK;
+        }();
+    }
+    return chain_finish_create(ctx, c, rc, out);
+}
+
+extern "C" int phk_chain_destroy(phk_ctx *ctx, phk_chain *c) {
+    if (!c) return PHK_OK;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    delete c;
+    return PHK_OK;
+}
+
+static int chain_emit(phk_ctx *ctx, phk_chain *c, double temper) {
+    const uint64_t n = c->n, D = c->D;
+    const bool full = D % GT_KC == 0;
+    for (uint64_t s = 0; s < n; s += c->B) {
+        const uint64_t nb = n - s < c->B ? n - s : c->B;
+        const dim3 grid((unsigned)phk_div_up(nb, GT_QB)), blk(GT_WAVES * 64);
+        double *E = c->E.as<double>() + s * c->S, *M = c->M.as<double>() + s;
+        if (full) {
+            PHK_LAUNCH(ctx, "phk_chain_emit_kernel", phk_chain_emit_kernel<true><<<grid, blk, 0, ctx->stream>>>(
+                                                         c->counts + s * D, nb, c->logp.as<double>(), c->S, D, temper, E, M));
+        } else {
+            PHK_LAUNCH(ctx, "phk_chain_emit_kernel", phk_chain_emit_kernel<false><<<grid, blk, 0, ctx->stream>>>(
+                                                         c->counts + s * D, nb, c->logp.as<double>(), c->S, D, temper, E, M));
+        }
+    }
+    return PHK_OK;
+}
+
+extern "C" int phk_chain_set(phk_ctx *ctx, phk_chain *c, const double *log_profiles, uint64_t D, const double *trans,
+                             const double *init, const int64_t *qlog_trans, const int64_t *qlog_init, double temper) {
+    PHK_ENTER(ctx, "phk_chain_set");
+    PHK_REQUIRE(c, "phk_chain_set: NULL chain");
+    PHK_REQUIRE(trans && init && qlog_trans && qlog_init, "phk_chain_set: NULL parameters");
+    const uint32_t S = c->S;
+    for (uint32_t i = 0; i < S * S; ++i)
+        PHK_REQUIRE(trans[i] > 0.0 && trans[i] < 1.0, "phk_chain_set: transition probability %u = %g is not in (0, 1)", i, trans[i]);
+    for (uint32_t i = 0; i < S; ++i)
+        PHK_REQUIRE(init[i] > 0.0 && init[i] < 1.0, "phk_chain_set: initial probability %u = %g is not in (0, 1)", i, init[i]);
+    for (uint32_t i = 0; i <= S; ++i) {
+        const double *row = i < S ? trans + i * S : init;
+        double sum = 0.0;
+        for (uint32_t j = 0; j < S; ++j) sum += row[j];
+        PHK_REQUIRE(fabs(sum - 1.0) <= 4.0 * 0x1p-52, "phk_chain_set: row %u of the transition matrix (row %u: the initial "
+                                                      "distribution) does not sum to 1", i, S);
+    }
+    for (uint32_t i = 0; i < S * S + S; ++i) {
+        const int64_t q = i < S * S ? qlog_trans[i] : qlog_init[i - S * S];
+        PHK_REQUIRE(q <= 0 && q >= -CH_QMAX, "phk_chain_set: quantised logarithm %u = %lld is not in [-2^31, 0]", i, (long long)q);
+    }
+    PHK_REQUIRE(temper > 0.0 && temper - temper == 0.0, "phk_chain_set: temper = %g is not finite and > 0", temper);
+    if (c->from_counts) {
+        PHK_REQUIRE(log_profiles, "phk_chain_set: NULL log profiles");
+        PHK_REQUIRE(D == c->D, "phk_chain_set: the profiles have %llu columns, the count rows %llu", (unsigned long long)D,
+                    (unsigned long long)c->D);
+        if (!phk_rows_finite(log_profiles, (uint64_t)S * D)) {
+            phk_set_error("phk_chain_set: the log profiles hold a value that is not finite (a zero profile entry?)");
+            return PHK_ERR_NAN;
+        }
+    } else {
+        PHK_REQUIRE(!log_profiles, "phk_chain_set: a chain made from emissions takes no profiles");
+    }
+    c->ready = false;
+    double par[PHK_CHAIN_MAX_STATES * PHK_CHAIN_MAX_STATES + PHK_CHAIN_MAX_STATES];
+    int64_t qpar[PHK_CHAIN_MAX_STATES * PHK_CHAIN_MAX_STATES + PHK_CHAIN_MAX_STATES];
+    std::copy(trans, trans + S * S, par), std::copy(init, init + S, par + S * S);
+    std::copy(qlog_trans, qlog_trans + S * S, qpar), std::copy(qlog_init, qlog_init + S, qpar + S * S);
+    int rc = phk_copy_to_device(ctx, c->par.ptr, par, (S * S + S) * 8);
+    if (rc == PHK_OK) rc = phk_copy_to_device(ctx, c->qpar.ptr, qpar, (S * S + S) * 8);
+    if (rc == PHK_OK && c->from_counts) rc = phk_copy_to_device(ctx, c->logp.ptr, log_profiles, (uint64_t)S * D * 8);
+    if (rc == PHK_OK && c->from_counts && c->n) rc = chain_emit(ctx, c, temper);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PHK_OK) {   // par and qpar leave scope
+        phk_set_error("phk_chain_set: the stream failed");
+        rc = PHK_ERR_HIP;
+    }
+    c->ready = rc == PHK_OK;
+    return rc;
+}
+
+extern "C" int phk_chain_emissions(phk_ctx *ctx, const phk_chain *c, double *E) {
+    PHK_ENTER(ctx, "phk_chain_emissions");
+    PHK_REQUIRE(c && c->ready, "phk_chain_emissions: no chain, or phk_chain_set has not succeeded on it");
+    if (c->n == 0) return PHK_OK;
+    PHK_REQUIRE(E, "phk_chain_emissions: NULL pointer");
+    return phk_copy_to_host(ctx, E, c->E.ptr, c->n * c->S * 8);
+}
+
+#define CHAIN_BY_SP(S, CALL)  \
+    do {                      \
+        if ((S) <= 2) {       \
+            CALL(2);          \
+        } else if ((S) <= 4) {\
+            CALL(4);          \
+        } else {              \
+            CALL(8);          \
+        }                     \
+    } while (0)
+
+// backward then forward over every record: B, G and the records' vectors V
+static int chain_forward_backward(phk_ctx *ctx, const phk_chain *c) {
+    const double *E = c->E.as<double>(), *M = c->M.as<double>(), *par = c->par.as<double>();
+    const uint64_t *off = c->off.as<uint64_t>();
+#define CH_FB(SP)                                                                                                             \
+    {                                                                                                                         \
+        const dim3 grid(chain_grid(c->R, 64 / SP, CH_BLOCKS_MAX));                                                            \
+        PHK_LAUNCH(ctx, "phk_chain_backward_kernel", phk_chain_backward_kernel<SP><<<grid, dim3(64), 0, ctx->stream>>>(       \
+                                                         E, M, off, c->R, c->S, par, c->Bt.as<double>()));                    \
+        PHK_LAUNCH(ctx, "phk_chain_forward_kernel",                                                                           \
+                   phk_chain_forward_kernel<SP><<<grid, dim3(64), 0, ctx->stream>>>(E, M, off, c->R, c->S, par,               \
+                                                                                    c->Bt.as<double>(), c->G.as<double>(),    \
+                                                                                    c->V.as<double>()));                      \
+    }
+    CHAIN_BY_SP(c->S, CH_FB);
+#undef CH_FB
+    return PHK_OK;
+}
+
+// the fixed tree over m vectors of Ev doubles, level after level; *out = the one vector left (in a fold buffer)
+static int chain_fold(phk_ctx *ctx, const phk_chain *c, const double *in, uint64_t m, uint64_t Ev, const double **out) {
+    for (int level = 0;; ++level) {
+        const uint64_t blocks = phk_div_up(m, 256);
+        double *dst = c->fold[level & 1].as<double>();
+        PHK_LAUNCH(ctx, "phk_chain_fold_kernel",
+                   phk_chain_fold_kernel<<<dim3((unsigned)phk_div_up(Ev, 256), (unsigned)blocks), dim3(256), 0, ctx->stream>>>(
+                       in, m, Ev, dst));
+        in = dst, m = blocks;
+        if (blocks == 1) break;
+    }
+    *out = in;
+    return PHK_OK;
+}
+
+static int chain_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, double *Ns, double *xi, double *gamma0,
+                            double *log_evidence, double *log_evidence_rec) {
+    const uint64_t S = c->S, D = c->D, R = c->R, n = c->n, Ev = S * S + S + 1, Em = S * D + S + 1;
+    PHK_TRY(chain_forward_backward(ctx, c));
+    const double *tot;
+    PHK_TRY(chain_fold(ctx, c, c->V.as<double>(), R, Ev, &tot));
+    std::vector<double> v(Ev);
+    PHK_TRY(phk_copy_to_host(ctx, v.data(), tot, Ev * 8));
+    std::copy(v.begin(), v.begin() + S * S, xi);
+    std::copy(v.begin() + S * S, v.begin() + S * S + S, gamma0);
+    *log_evidence = v[S * S + S];
+    if (log_evidence_rec) {
+        std::vector<double> rec(R * Ev);
+        PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
+        for (uint64_t r = 0; r < R; ++r) log_evidence_rec[r] = rec[r * Ev + S * S + S];
+    }
+    if (!T) return PHK_OK;
+    const bool vec = D % 4 == 0;
+    for (uint64_t s = 0; s < n; s += c->B) {
+        const uint64_t nb = n - s < c->B ? n - s : c->B;
+        PHK_LAUNCH(ctx, "phk_chain_spread_kernel",
+                   phk_chain_spread_kernel<<<dim3(chain_grid(nb * CH_KP, 256, 4096)), dim3(256), 0, ctx->stream>>>(
+                       c->G.as<double>() + s * S, nb, (uint32_t)S, c->Rx.as<double>()));
+        const dim3 grid((unsigned)phk_div_up(nb, MIX_RB), (unsigned)phk_div_up(D, GT_WAVES * MIX_CT)), blk(GT_WAVES * 64);
+        double *part = c->part.as<double>() + (s / MIX_RB) * Em;
+        if (vec) {
+            PHK_LAUNCH(ctx, "phk_chain_expect_kernel", phk_chain_expect_kernel<true><<<grid, blk, 0, ctx->stream>>>(
+                                                           c->Rx.as<double>(), c->counts + s * D, D, nb, c->M.as<double>() + s,
+                                                           (uint32_t)S, Em, part));
+        } else {
+            PHK_LAUNCH(ctx, "phk_chain_expect_kernel", phk_chain_expect_kernel<false><<<grid, blk, 0, ctx->stream>>>(
+                                                           c->Rx.as<double>(), c->counts + s * D, D, nb, c->M.as<double>() + s,
+                                                           (uint32_t)S, Em, part));
+        }
+    }
+    PHK_TRY(chain_fold(ctx, c, c->part.as<double>(), phk_div_up(n, MIX_RB), Em, &tot));
+    std::vector<double> t(Em);
+    PHK_TRY(phk_copy_to_host(ctx, t.data(), tot, Em * 8));
+    std::copy(t.begin(), t.begin() + S * D, T);
+    std::copy(t.begin() + S * D, t.begin() + S * D + S, Ns);
+    return PHK_OK;
+}
+
+extern "C" int phk_chain_expect(phk_ctx *ctx, const phk_chain *c, double *T, double *Ns, double *xi, double *gamma0,
+                                double *log_evidence, double *log_evidence_rec) {
+    PHK_ENTER(ctx, "phk_chain_expect");
+    PHK_REQUIRE(c && c->ready, "phk_chain_expect: no chain, or phk_chain_set has not succeeded on it");
+    PHK_REQUIRE(xi && gamma0 && log_evidence, "phk_chain_expect: NULL pointer");
+    PHK_REQUIRE(!T == !Ns, "phk_chain_expect: T and Ns go together");
+    PHK_REQUIRE(!T || c->from_counts, "phk_chain_expect: a chain made from emissions has no T");
+    const uint64_t S = c->S;
+    if (c->n == 0) {
+        std::fill(xi, xi + S * S, 0.0), std::fill(gamma0, gamma0 + S, 0.0);
+        *log_evidence = 0.0;
+        if (T) std::fill(T, T + S * c->D, 0.0), std::fill(Ns, Ns + S, 0.0);
+        for (uint64_t r = 0; log_evidence_rec && r < c->R; ++r) log_evidence_rec[r] = 0.0;
+        return PHK_OK;
+    }
+    const int rc = chain_expect_run(ctx, c, T, Ns, xi, gamma0, log_evidence, log_evidence_rec);
+    if (rc != PHK_OK) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+static int chain_decode_run(phk_ctx *ctx, const phk_chain *c, uint8_t *state, double *posterior, double *log_evidence_rec,
+                            int64_t *path_score) {
+    const uint64_t S = c->S, R = c->R, n = c->n, Ev = S * S + S + 1;
+    const uint64_t *off = c->off.as<uint64_t>();
+    if (posterior || log_evidence_rec) PHK_TRY(chain_forward_backward(ctx, c));
+#define CH_VIT(SP)                                                                                                        \
+    PHK_LAUNCH(ctx, "phk_chain_viterbi_kernel",                                                                           \
+               phk_chain_viterbi_kernel<SP><<<dim3(chain_grid(R, 64 / SP, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(   \
+                   c->E.as<double>(), c->M.as<double>(), off, R, c->S, c->qpar.as<int64_t>(), c->BP.as<uint8_t>(),        \
+                   c->score.as<int64_t>(), c->last.as<uint8_t>()))
+    CHAIN_BY_SP(c->S, CH_VIT);
+#undef CH_VIT
+    PHK_LAUNCH(ctx, "phk_chain_trace_kernel",
+               phk_chain_trace_kernel<<<dim3(chain_grid(R, 64, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(
+                   off, R, c->last.as<uint8_t>(), c->BP.as<uint64_t>(), c->state.as<uint8_t>()));
+    PHK_TRY(phk_copy_to_host(ctx, state, c->state.ptr, n));
+    if (path_score) PHK_TRY(phk_copy_to_host(ctx, path_score, c->score.ptr, R * 8));
+    if (posterior) PHK_TRY(phk_copy_to_host(ctx, posterior, c->G.ptr, n * S * 8));
+    if (log_evidence_rec) {
+        std::vector<double> rec(R * Ev);
+        PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
+        for (uint64_t r = 0; r < R; ++r) log_evidence_rec[r] = rec[r * Ev + S * S + S];
+    }
+    return PHK_OK;
+}
+
+extern "C" int phk_chain_decode(phk_ctx *ctx, const phk_chain *c, uint8_t *state, double *posterior, double *log_evidence_rec,
+                                int64_t *path_score) {
+    PHK_ENTER(ctx, "phk_chain_decode");
+    PHK_REQUIRE(c && c->ready, "phk_chain_decode: no chain, or phk_chain_set has not succeeded on it");
+    if (c->n == 0) {
+        for (uint64_t r = 0; r < c->R; ++r) {
+            if (log_evidence_rec) log_evidence_rec[r] = 0.0;
+            if (path_score) path_score[r] = 0;
+        }
+        return PHK_OK;
+    }
+    PHK_REQUIRE(state, "phk_chain_decode: NULL state");
+    const int rc = chain_decode_run(ctx, c, state, posterior, log_evidence_rec, path_score);
+    if (rc != PHK_OK) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
