@@ -668,6 +668,24 @@ int phk_chain_decode(phk_ctx *ctx, const phk_chain *chain, uint8_t *state, doubl
 uint64_t phk_chain_grid_pass(void);
 int phk_chain_destroy(phk_ctx *ctx, phk_chain *chain);
 
+/* The tile scan of the chain: an opt-in route on which a long record is worked on in parallel.
+ * phk_chain_set_scan(chain, scan_from): in every later phk_chain_expect and phk_chain_decode the records of at least scan_from
+ * windows are cut into tiles of PHK_CHAIN_TILE consecutive windows counted from the record's own start (the last may be
+ * partial); 0, the state after create, means no record.  A tile's transfer matrices (the ordered product of its steps' A diag(e)
+ * in float64 rescaled by powers of two, and of its max-plus steps on int64) are formed in parallel over the tiles, carried
+ * through the record's tiles in tile order, and the tiles then run the per-step recurrences from the vectors that enter them.
+ * state and path_score of a scanned record are bit for bit those of the other route (integer max-plus is associative); its
+ * posteriors, xi, gamma0, evidence, T and Ns lie within the bound of section 4.27 of the exact values, and are a function of its
+ * own rows, the parameters and PHK_CHAIN_TILE alone.  A record below scan_from gives the bits it gives with the route off.
+ * The call may come before or after phk_chain_set; it builds the tile tables and allocates the tile buffers.  PHK_ERR_ARG for a
+ * NULL chain; PHK_OK with nothing allocated when no record reaches scan_from.  phk_chain_tile() returns PHK_CHAIN_TILE,
+ * phk_chain_scan_grid_pass() the most tiles one launch of the per-tile kernels covers (further ones by grid stride; for the
+ * tests). */
+#define PHK_CHAIN_TILE 64
+int phk_chain_set_scan(phk_ctx *ctx, phk_chain *chain, uint64_t scan_from);
+uint64_t phk_chain_tile(void);
+uint64_t phk_chain_scan_grid_pass(void);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

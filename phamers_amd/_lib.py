@@ -134,6 +134,9 @@ SIGNATURES = {
     "phk_chain_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_chain_grid_pass": (c_u64, []),
     "phk_chain_destroy": (c_int, [c_void_p, c_void_p]),
+    "phk_chain_set_scan": (c_int, [c_void_p, c_void_p, c_u64]),
+    "phk_chain_tile": (c_u64, []),
+    "phk_chain_scan_grid_pass": (c_u64, []),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1383,6 +1386,15 @@ class Chain(_Resident):
             raise ValueError("trans must be (%d, %d) and init (%d,), with their quantised logarithms" % (S, S, S))
         self._rc(self.ctx.lib.phk_chain_set(self.ctx.handle, self.handle, ptr(lp), 0 if lp is None else lp.shape[1], ptr(tr),
                                             ptr(pi), ptr(qt), ptr(qp), float(temper)))
+
+    def set_scan(self, scan_from):
+        """Records of at least ``scan_from`` windows take the tile scan in every later ``expect`` and
+        ``decode`` (phk_chain_set_scan); 0: none, the state after create.  Before or after ``set``."""
+        self._open()
+        scan_from = int(scan_from)
+        if not 0 <= scan_from < 2 ** 64:
+            raise ValueError("scan_from = %r" % (scan_from,))
+        self._rc(self.ctx.lib.phk_chain_set_scan(self.ctx.handle, self.handle, scan_from))
 
     def emissions(self):
         """E (n, S) float64 as the device holds it (phk_chain_emissions)."""

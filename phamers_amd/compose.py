@@ -28,7 +28,7 @@ Two findings of the CPU study this module was built after:
     fit(counts_or_batch, owner_or_offsets, n_states, ...)       a Composition
     segment_sequences(fasta_or_sequences, n_states, ...)        a ComposedSequences (fit + decode of the windows)
     load(path)                                                  a Composition saved with Composition.save
-    python -m phamers_amd.compose -in FASTA -out DIR -S n
+    python -m phamers_amd.compose -in FASTA -out DIR -S n [--scan [N]]
 """
 import collections
 import os
@@ -41,6 +41,8 @@ from .segment import QUANT_BITS, _offsets, default_temper, quantise
 
 MAX_STATES = _lib.CHAIN_MAX_STATES
 P_MIN = 1e-12
+SCAN_FROM = 256    # ``scan=True``: records of at least this many windows take the tile scan (measured:
+                   # profiles/compose_scan/README.md)
 TRACE_COLUMNS = ("L", "F")
 
 Decoded = collections.namedtuple("Decoded", "state posterior log_evidence path_score path_score_q")
@@ -53,6 +55,18 @@ def _states(n_states):
     if not 2 <= S <= MAX_STATES:
         raise ValueError("n_states must be 2 to %d, got %r" % (MAX_STATES, n_states))
     return S
+
+
+def _scan(scan):
+    """``scan`` as a threshold in windows: None, False and 0 are 0 (no record takes the tile scan), True is ``SCAN_FROM``, an
+    int >= 1 itself."""
+    if scan is None or scan is False:
+        return 0
+    if scan is True:
+        return SCAN_FROM
+    if isinstance(scan, (int, np.integer)) and 0 <= int(scan) < 2 ** 64:
+        return int(scan)
+    raise ValueError("scan must be None, a bool or an int >= 0, got %r" % (scan,))
 
 
 def _temper(temper):
@@ -161,6 +175,9 @@ class _DeviceEStep(object):
             self.host = self.batch.counts_u32()
         return self.host
 
+    def set_scan(self, scan_from):
+        self.chain.set_scan(scan_from)
+
     def _set(self, log_profiles, trans, init, temper):
         self.chain.set(log_profiles, trans, init, quantise(np.log(trans)), quantise(np.log(init)), temper)
 
@@ -225,12 +242,16 @@ class Composition(object):
     def empty(self):
         return self.occupancy == 0
 
-    def decode(self, counts_or_batch, owner_or_offsets):
+    def decode(self, counts_or_batch, owner_or_offsets, scan=None):
         """The Viterbi path, the posteriors (n, S), the log evidence per record and the path score of count rows (or a
-        resident batch) cut into records by ``owner_or_offsets`` (see ``segment.decode``): a ``Decoded``."""
+        resident batch) cut into records by ``owner_or_offsets`` (see ``segment.decode``): a ``Decoded``.  ``scan``: the
+        records that take the tile scan (see ``fit``); their path and path score are the same bits either way."""
+        scan = _scan(scan)
         offsets = _record_offsets(counts_or_batch, owner_or_offsets)
         estep = _estep(counts_or_batch, offsets, self.n_states)
         try:
+            if scan:
+                estep.set_scan(scan)
             if estep.D != self.log_profiles.shape[1]:
                 raise ValueError("the counts have %d columns, the composition %d" % (estep.D, self.log_profiles.shape[1]))
             state, post, le, ps = estep.decode(self.log_profiles, self.trans, self.init, self.temper)
@@ -278,13 +299,17 @@ def _initial_profiles(estep, S, init, block, a):
 
 
 def fit(counts_or_batch, owner_or_offsets, n_states, mean_region=30000, step=500, temper=1.0, pseudocount=0.5, init=None,
-        block=20, prior_counts=0, fit_transitions=True, p_start='fixed', max_iter=100, tol=1e-6):
+        block=20, prior_counts=0, fit_transitions=True, p_start='fixed', max_iter=100, tol=1e-6, scan=None):
     """An S-state chain fitted by Baum-Welch to the count rows ``counts_or_batch`` ((n, D) integers, made resident once, or
     a ``_lib.Batch``, read where it lies) cut into records by ``owner_or_offsets`` (see ``segment.decode``).  The profiles
     start from ``start`` (``init``: S block indices or (S, D) profiles instead), the chain from ``start_chain``.  The loop
     is ``mixture``'s: it stops at the first iterate with F_i - F_{i-1} <= tol max(1, |F_i|) or after ``max_iter`` M-steps.
-    ``fit_transitions=False`` keeps the start chain.  gamma and E never leave the device.  A ``Composition``."""
+    ``fit_transitions=False`` keeps the start chain.  gamma and E never leave the device.  ``scan``: None, False or 0 keep
+    every record on the per-record route; True sends the records of at least ``SCAN_FROM`` windows, an int >= 1 those of at
+    least that many, through the tile scan, which works on a long record in parallel and gives
+    its expectations within that section's bound.  A ``Composition``."""
     S, a, t = _states(n_states), _pseudocount(pseudocount), _temper(temper)
+    scan = _scan(scan)
     max_iter, tol = int(max_iter), float(tol)
     if max_iter < 0 or not (np.isfinite(tol) and tol >= 0):
         raise ValueError("max_iter >= 0 and a finite tol >= 0 are required")
@@ -294,6 +319,8 @@ def fit(counts_or_batch, owner_or_offsets, n_states, mean_region=30000, step=500
     offsets = _record_offsets(counts_or_batch, owner_or_offsets)
     estep = _estep(counts_or_batch, offsets, S)
     try:
+        if scan:
+            estep.set_scan(scan)
         logp = _initial_profiles(estep, S, init, block, a)
         trace, F_prev, converged = [], None, False
         for it in range(max_iter + 1):
@@ -343,11 +370,14 @@ class ComposedSequences(object):
                  int(b - a + 1), float(self.posterior[a:b + 1, int(self.state[a])].mean())) for a, b in zip(first, last)]
 
 
-def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_length=4, both_strands=False, **fit_options):
+def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_length=4, both_strands=False, scan=None,
+                      **fit_options):
     """Counts the windows of a FASTA file (or a list of strings) as one resident batch, fits ``n_states`` compositions to
     them and decodes: a ``ComposedSequences``.  ``temper`` defaults to ``segment.default_temper(window, step, k)``; the other
-    ``fit_options`` are ``fit``'s (``step`` is passed on).  ValueError when no sequence holds a window."""
+    ``fit_options`` are ``fit``'s (``step`` is passed on); ``scan`` goes to the fit and to the decode.  ValueError when no
+    sequence holds a window."""
     from . import kmer
+    scan = _scan(scan)
     both_strands = kmer._check_strands(kmer.DNA, both_strands)
     record_ids, lengths, batch = kmer._windows_batch(fasta_or_sequences, kmer_length, window, step)
     if batch is None:
@@ -358,8 +388,8 @@ def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_l
         owner, first = kmer.window_plan(lengths, window, step)
         fit_options.setdefault("temper", default_temper(window, step, kmer_length))
         offsets = _KnownOffsets(np.concatenate(([0], np.cumsum(np.bincount(owner, minlength=len(record_ids))))))
-        comp = fit(batch, offsets, n_states, step=step, **fit_options)
-        decoded = comp.decode(batch, offsets)
+        comp = fit(batch, offsets, n_states, step=step, scan=scan, **fit_options)
+        decoded = comp.decode(batch, offsets, scan=scan)
     finally:
         batch.close()
     return ComposedSequences(comp, record_ids, owner, first, window, step, decoded)
@@ -383,6 +413,8 @@ def _parser():
     ap.add_argument('--max_iter', type=int, default=100, help="Most M-steps")
     ap.add_argument('--tol', type=float, default=1e-6, help="Relative gain of the evidence below which the loop stops")
     ap.add_argument('--keep_transitions', action='store_true', help="Do not fit the transition probabilities")
+    ap.add_argument('--scan', type=int, nargs='?', const=True, default=None, metavar='N',
+                    help="Work on records of at least N windows in parallel by the tile scan (without N: %d)" % SCAN_FROM)
     ap.add_argument('-pf', '--positive_features', default=None, help="Count file of the positive reference (labels the states)")
     ap.add_argument('-nf', '--negative_features', default=None, help="Count file of the negative reference")
     return ap
@@ -424,8 +456,10 @@ def main(argv=None):
                    fit_transitions=not args.keep_transitions)
     if args.temper is not None:
         options["temper"] = args.temper
+    if args.scan is not None and args.scan is not True and args.scan < 1:
+        raise SystemExit("--scan takes a number of windows >= 1")
     result = segment_sequences(args.input_file, args.states, args.window, args.step, args.kmer_length, args.both_strands,
-                               **options)
+                               args.scan, **options)
     score = None
     if args.positive_features is not None:
         from . import fileIO

@@ -26,6 +26,8 @@
 //                              global row index
 //   phk_chain_fold_kernel      mix_fold_body: the fixed 256-row tree, over the row blocks' partial vectors and over the records'
 //                              vectors alike
+// The records of at least scan_from windows (phk_chain_set_scan; 0: none) are passed over by the four per-record kernels and
+// take the tile scan, the phk_chain_scan_* kernels further down.
 // The integer sums: |q| <= 2^31 and |qlog| <= 2^31 (checked), so a path over n <= 2^30 windows stays inside 2^62.
 // The float sums stay away from 0 / 0 as long as the ratio of two entries of a row or column of A stays inside the format
 // (entries of 1e-12 are tested): the largest entry of a rescaled vector is in [1/2, 1) and the state of the largest emission
@@ -78,6 +80,9 @@ __global__ __launch_bounds__(256) void phk_chain_rowmax_kernel(const double *__r
     }
 }
 
+// a record of `len` windows takes the tile scan (the per-record kernels pass over it); scan_from == 0: no record does
+__device__ __forceinline__ bool chain_scanned(uint64_t len, uint64_t scan_from) { return scan_from != 0 && len >= scan_from; }
+
 // the sum of v over the group's lanes in state order; every lane gets the same bits
 template <int SP>
 __device__ __forceinline__ double chain_sum(double v) {
@@ -104,7 +109,8 @@ __device__ __forceinline__ int chain_scale2(double &v) {
 template <int SP>
 __global__ __launch_bounds__(64) void phk_chain_backward_kernel(const double *__restrict__ E, const double *__restrict__ M,
                                                                 const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
-                                                                const double *__restrict__ par, double *__restrict__ B) {
+                                                                const double *__restrict__ par, double *__restrict__ B,
+                                                                uint64_t scan_from) {
     const uint32_t j = threadIdx.x % SP;
     const bool live = j < S;
     const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
@@ -113,7 +119,7 @@ __global__ __launch_bounds__(64) void phk_chain_backward_kernel(const double *__
     for (int i = 0; i < SP; ++i) arow[i] = (live && (uint32_t)i < S) ? par[j * S + i] : 0.0;
     for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
         const uint64_t w0 = off[r], w1 = off[r + 1];
-        if (w1 == w0) continue;
+        if (w1 == w0 || chain_scanned(w1 - w0, scan_from)) continue;
         double b = live ? 1.0 : 0.0;
         uint64_t w = w1 - 1;
         double x = live ? E[w * S + j] - M[w] : 0.0;
@@ -138,7 +144,8 @@ template <int SP>
 __global__ __launch_bounds__(64) void phk_chain_forward_kernel(const double *__restrict__ E, const double *__restrict__ M,
                                                                const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
                                                                const double *__restrict__ par, const double *__restrict__ B,
-                                                               double *__restrict__ G, double *__restrict__ V) {
+                                                               double *__restrict__ G, double *__restrict__ V,
+                                                               uint64_t scan_from) {
     const uint32_t j = threadIdx.x % SP;
     const bool live = j < S;
     const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
@@ -149,6 +156,7 @@ __global__ __launch_bounds__(64) void phk_chain_forward_kernel(const double *__r
     const double pj = live ? par[S * S + j] : 0.0;
     for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
         const uint64_t w0 = off[r], w1 = off[r + 1];
+        if (chain_scanned(w1 - w0, scan_from)) continue;
         double *out = V + r * Ev;
         double xi[SP];
 #pragma unroll
@@ -218,7 +226,8 @@ template <int SP>
 __global__ __launch_bounds__(64) void phk_chain_viterbi_kernel(const double *__restrict__ E, const double *__restrict__ M,
                                                                const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
                                                                const int64_t *__restrict__ qpar, uint8_t *__restrict__ BP,
-                                                               int64_t *__restrict__ score, uint8_t *__restrict__ last) {
+                                                               int64_t *__restrict__ score, uint8_t *__restrict__ last,
+                                                               uint64_t scan_from) {
     const uint32_t j = threadIdx.x % SP;
     const bool live = j < S;
     const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
@@ -228,6 +237,7 @@ __global__ __launch_bounds__(64) void phk_chain_viterbi_kernel(const double *__r
     const long long qp = live ? (long long)qpar[S * S + j] : 0ll;
     for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
         const uint64_t w0 = off[r], w1 = off[r + 1];
+        if (chain_scanned(w1 - w0, scan_from)) continue;
         if (w1 == w0) {
             if (j == 0) score[r] = 0, last[r] = 0;
             continue;
@@ -263,9 +273,10 @@ __global__ __launch_bounds__(64) void phk_chain_viterbi_kernel(const double *__r
 
 __global__ __launch_bounds__(64) void phk_chain_trace_kernel(const uint64_t *__restrict__ off, uint64_t R,
                                                              const uint8_t *__restrict__ last, const uint64_t *__restrict__ BP,
-                                                             uint8_t *__restrict__ state) {
+                                                             uint8_t *__restrict__ state, uint64_t scan_from) {
     for (uint64_t r = (uint64_t)blockIdx.x * 64 + threadIdx.x; r < R; r += (uint64_t)gridDim.x * 64) {
         const uint64_t w0 = off[r];
+        if (chain_scanned(off[r + 1] - w0, scan_from)) continue;
         uint32_t s = last[r];
 #pragma unroll 8
         for (uint64_t w = off[r + 1]; w > w0; --w) {
@@ -300,6 +311,409 @@ __global__ __launch_bounds__(256) void phk_chain_fold_kernel(const double *__res
 
 extern "C" uint64_t phk_chain_grid_pass(void) { return (uint64_t)CH_BLOCKS_MAX * 32; }
 
+// ---- the tile scan ----------------------------------------------------------------------------------------
+// A record of at least scan_from windows is cut into tiles of PHK_CHAIN_TILE windows from its own start.  The scanned records
+// are s = 0 .. ns - 1 (record sr[s], tiles st[s] .. st[s + 1] - 1); tile t belongs to scanned record ti[t].
+//   phk_chain_scan_tile_kernel   a group of SP x SP lanes per tile, lane (i, j) = entry [i][j]: F = the ordered product of the
+//                                tile's A diag(e_t) with the exponent of its power-of-two rescaling, the max-plus product Vq on
+//                                int64, the tile's sum of M.  A record's first tile starts from pi: every row is that vector.
+//   phk_chain_scan_carry_kernel  a group of SP x SP lanes per scanned record, over its tiles in tile order; blockIdx.y is the
+//                                role: alpha entering every tile and the log evidence (left to right), beta leaving every tile
+//                                (right to left), delta entering every tile, path_score and the last state (left to right).
+//                                The tiles' matrices are loaded CH_PF tiles ahead of the chain.
+//   phk_chain_scan_walk_kernel   a group of SP lanes per tile: the backward and the forward recurrence of the per-record kernels
+//                                inside the tile from the vectors that enter it; gamma, the tile's xi, gamma_0 from the first
+//   phk_chain_scan_path_kernel   likewise the max-plus recurrence: the backpointer words (the tile's first step too) and the
+//                                tile's map from end state to the state before the tile
+//   phk_chain_scan_fold_kernel   xi of a record = its tiles' xi added in tile order, into V[r]
+//   phk_chain_scan_ends_kernel   lane per scanned record: the state at every tile's end, right to left through the maps
+//   phk_chain_scan_fill_kernel   lane per tile: the tile's states from its end state and its words
+#define CH_SCAN_PASS 4096ull    // tiles per launch of the per-tile kernels
+#define CH_PF 8                 // tiles the carry loads ahead
+
+static_assert(PHK_CHAIN_TILE == 64, "DESIGN.md 4.27 states the step count for 64");
+
+// tile t: its record, whether it is the record's first, its windows [a, b)
+__device__ __forceinline__ void chain_scan_tile(const uint32_t *__restrict__ ti, const uint64_t *__restrict__ sr,
+                                                const uint64_t *__restrict__ st, const uint64_t *__restrict__ off, uint64_t t,
+                                                uint64_t &r, bool &first, uint64_t &a, uint64_t &b) {
+    const uint32_t s = ti[t];
+    r = sr[s];
+    const uint64_t t0 = st[s], w1 = off[r + 1];
+    first = t == t0;
+    a = off[r] + (t - t0) * PHK_CHAIN_TILE;
+    b = a + PHK_CHAIN_TILE < w1 ? a + PHK_CHAIN_TILE : w1;
+}
+
+// v / 2^e with e the exponent of the largest v over the lanes l ^ o, o = LO, 2 LO, .. < HI: exact; returns e
+template <int LO, int HI>
+__device__ __forceinline__ int chain_scale2x(double &v) {
+    double m = v;
+#pragma unroll
+    for (int o = LO; o < HI; o <<= 1) m = fmax(m, __shfl_xor(m, o, HI));
+    int e;
+    (void)frexp(m, &e);
+    v = ldexp(v, -e);
+    return e;
+}
+
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_scan_tile_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                                 const uint64_t *__restrict__ off, const uint32_t *__restrict__ ti,
+                                                                 const uint64_t *__restrict__ sr, const uint64_t *__restrict__ st,
+                                                                 uint64_t nt, uint32_t S, const double *__restrict__ par,
+                                                                 const int64_t *__restrict__ qpar, double *__restrict__ F,
+                                                                 int32_t *__restrict__ FE, int64_t *__restrict__ Vq,
+                                                                 double *__restrict__ SM) {
+    constexpr int G = SP * SP;
+    const uint32_t g = threadIdx.x % G, i = g / SP, j = g % SP;
+    const bool lj = j < S, live = lj && i < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / G);
+    double acol[SP];
+    long long qcol[SP];
+#pragma unroll
+    for (int k = 0; k < SP; ++k) {
+        acol[k] = (lj && (uint32_t)k < S) ? par[(uint32_t)k * S + j] : 0.0;
+        qcol[k] = (lj && (uint32_t)k < S) ? (long long)qpar[(uint32_t)k * S + j] : 0ll;
+    }
+    const double aij = live ? par[i * S + j] : 0.0, pj = live ? par[S * S + j] : 0.0;
+    const long long qij = live ? (long long)qpar[i * S + j] : 0ll, qpj = live ? (long long)qpar[S * S + j] : 0ll;
+    for (uint64_t t = (uint64_t)blockIdx.x * (64 / G) + threadIdx.x / G; t < nt; t += groups) {
+        uint64_t r, a, b;
+        bool first;
+        chain_scan_tile(ti, sr, st, off, t, r, first, a, b);
+        double mw = M[a];
+        double x = lj ? E[a * S + j] - mw : 0.0;
+        double f = (first ? pj : aij) * (lj ? exp(x) : 0.0);
+        long long v = (first ? qpj : qij) + (lj ? (long long)chain_quant(x) : 0ll);
+        int fe = chain_scale2x<1, G>(f);
+        double sm = mw;
+        uint64_t w = a + 1;
+        if (w < b) {
+            mw = M[w];
+            x = lj ? E[w * S + j] - mw : 0.0;
+        }
+        while (w < b) {
+            const double e = lj ? exp(x) : 0.0;
+            const long long q = lj ? (long long)chain_quant(x) : 0ll;
+            sm += mw;
+            const uint64_t wn = w + 1;
+            if (wn < b) {   // the next step's loads, issued ahead of this step's chain
+                mw = M[wn];
+                x = lj ? E[wn * S + j] - mw : 0.0;
+            }
+            double gs = 0.0;
+#pragma unroll
+            for (int k = 0; k < SP; ++k) gs += __shfl(f, k, SP) * acol[k];
+            f = gs * e;
+            fe += chain_scale2x<1, G>(f);
+            long long best = __shfl(v, 0, SP) + qcol[0];
+#pragma unroll
+            for (int k = 1; k < SP; ++k) {
+                const long long c = __shfl(v, k, SP) + qcol[k];
+                if ((uint32_t)k < S && c > best) best = c;
+            }
+            v = best + q;
+            w = wn;
+        }
+        F[t * G + g] = f;
+        Vq[t * G + g] = live ? (int64_t)v : 0;
+        if (g == 0) FE[t] = fe, SM[t] = sm;
+    }
+}
+
+// roles: 0 alpha and the evidence, 1 beta, 2 delta, path_score and the last state.  AI[t][i] = alpha entering tile t (t not the
+// record's first), BO[t][j] = beta of tile t's last step, DI[t][i] = delta entering tile t; V[r]'s last entry = log evidence.
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_scan_carry_kernel(const double *__restrict__ F, const int32_t *__restrict__ FE,
+                                                                  const int64_t *__restrict__ Vq, const double *__restrict__ SM,
+                                                                  const uint64_t *__restrict__ sr, const uint64_t *__restrict__ st,
+                                                                  uint64_t ns, uint32_t S, uint32_t role0, double *__restrict__ AI,
+                                                                  double *__restrict__ BO, int64_t *__restrict__ DI,
+                                                                  double *__restrict__ V, int64_t *__restrict__ score,
+                                                                  uint8_t *__restrict__ last) {
+    constexpr int G = SP * SP;
+    const uint32_t g = threadIdx.x % G, i = g / SP, j = g % SP;
+    const uint32_t role = role0 + blockIdx.y;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / G), Ev = (uint64_t)S * S + S + 1;
+    for (uint64_t s = (uint64_t)blockIdx.x * (64 / G) + threadIdx.x / G; s < ns; s += groups) {
+        const uint64_t t0 = st[s], t1 = st[s + 1], r = sr[s];
+        if (role == 0) {
+            // lane (i, j) holds alpha(i) in ai and alpha(j) in ar; the first tile's row 0 is the vector from pi
+            double ai = F[t0 * G + i], ar = F[t0 * G + j], sm = SM[t0];
+            int64_t ex = FE[t0];
+            double fb[CH_PF], sb[CH_PF];
+            int eb[CH_PF];
+#pragma unroll
+            for (int p = 0; p < CH_PF; ++p) {
+                const uint64_t t = t0 + 1 + p;
+                const bool ok = t < t1;
+                fb[p] = ok ? F[t * G + g] : 0.0, eb[p] = ok ? FE[t] : 0, sb[p] = ok ? SM[t] : 0.0;
+            }
+            for (uint64_t base = t0 + 1; base < t1; base += CH_PF) {
+#pragma unroll
+                for (int p = 0; p < CH_PF; ++p) {
+                    const uint64_t t = base + p, tn = t + CH_PF;
+                    if (t >= t1) break;
+                    const double f = fb[p], smt = sb[p];
+                    const int fe = eb[p];
+                    if (tn < t1) fb[p] = F[tn * G + g], eb[p] = FE[tn], sb[p] = SM[tn];
+                    if (j == 0) AI[t * SP + i] = ai;
+                    const double pr = ai * f;
+                    double sum = __shfl(pr, j, G);
+#pragma unroll
+                    for (int k = 1; k < SP; ++k) sum += __shfl(pr, k * SP + j, G);   // over the start states in state order
+                    ex += fe + chain_scale2x<1, SP>(sum);
+                    ar = sum;
+                    ai = __shfl(sum, i, G);
+                    sm += smt;
+                }
+            }
+            int e2;
+            const double m = frexp(chain_sum<SP>(ar), &e2);
+            if (g == 0) V[r * Ev + S * S + S] = ((double)(ex + e2) * CH_LN2 + log(m)) + sm;
+        } else if (role == 1) {
+            // lane (i, j) holds beta(j); tiles t1 - 1 down to t0, c counts them
+            const uint64_t K = t1 - t0;
+            double bj = j < S ? 1.0 : 0.0;
+            double fb[CH_PF];
+#pragma unroll
+            for (int p = 0; p < CH_PF; ++p) fb[p] = (uint64_t)p + 1 < K ? F[(t1 - 1 - p) * G + g] : 0.0;
+            for (uint64_t base = 0; base < K; base += CH_PF) {
+#pragma unroll
+                for (int p = 0; p < CH_PF; ++p) {
+                    const uint64_t c = base + p, cn = c + CH_PF;
+                    if (c >= K) break;
+                    const uint64_t t = t1 - 1 - c;
+                    const double f = fb[p];
+                    if (cn + 1 < K) fb[p] = F[(t1 - 1 - cn) * G + g];
+                    if (i == 0) BO[t * SP + j] = bj;
+                    if (c + 1 == K) break;
+                    double sum = chain_sum<SP>(f * bj);   // beta'(i), over the end states in state order
+                    (void)chain_scale2x<SP, G>(sum);
+                    bj = __shfl(sum, j * SP, G);
+                }
+            }
+        } else {
+            long long di = Vq[t0 * G + i], dr = Vq[t0 * G + j];
+            long long vb[CH_PF];
+#pragma unroll
+            for (int p = 0; p < CH_PF; ++p) vb[p] = t0 + 1 + p < t1 ? (long long)Vq[(t0 + 1 + p) * G + g] : 0ll;
+            for (uint64_t base = t0 + 1; base < t1; base += CH_PF) {
+#pragma unroll
+                for (int p = 0; p < CH_PF; ++p) {
+                    const uint64_t t = base + p, tn = t + CH_PF;
+                    if (t >= t1) break;
+                    const long long v = vb[p];
+                    if (tn < t1) vb[p] = (long long)Vq[tn * G + g];
+                    if (j == 0) DI[t * SP + i] = (int64_t)di;
+                    const long long c = di + v;
+                    long long best = __shfl(c, j, G);
+#pragma unroll
+                    for (int k = 1; k < SP; ++k) {
+                        const long long o = __shfl(c, k * SP + j, G);
+                        if ((uint32_t)k < S && o > best) best = o;
+                    }
+                    dr = best;
+                    di = __shfl(best, i, G);
+                }
+            }
+            long long best = __shfl(dr, 0, SP);
+            uint32_t k = 0;
+#pragma unroll
+            for (int q = 1; q < SP; ++q) {
+                const long long c = __shfl(dr, q, SP);
+                if ((uint32_t)q < S && c > best) best = c, k = (uint32_t)q;   // a tie stays with the smaller state
+            }
+            if (g == 0) score[r] = (int64_t)best, last[r] = (uint8_t)k;
+        }
+    }
+}
+
+// XI[t][i][j] = the tile's xi (SP x SP, zeros past S); gamma_0 goes into V[r] from the record's first tile.
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_scan_walk_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                                 const uint64_t *__restrict__ off, const uint32_t *__restrict__ ti,
+                                                                 const uint64_t *__restrict__ sr, const uint64_t *__restrict__ st,
+                                                                 uint64_t nt, uint32_t S, const double *__restrict__ par,
+                                                                 const double *__restrict__ AI, const double *__restrict__ BO,
+                                                                 double *B, double *__restrict__ Gm, double *__restrict__ XI,
+                                                                 double *__restrict__ V) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP), Ev = (uint64_t)S * S + S + 1;
+    double arow[SP], acol[SP];
+#pragma unroll
+    for (int i = 0; i < SP; ++i) {
+        arow[i] = (live && (uint32_t)i < S) ? par[j * S + i] : 0.0;
+        acol[i] = (live && (uint32_t)i < S) ? par[(uint32_t)i * S + j] : 0.0;
+    }
+    const double pj = live ? par[S * S + j] : 0.0;
+    for (uint64_t t = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; t < nt; t += groups) {
+        uint64_t r, a, b;
+        bool first;
+        chain_scan_tile(ti, sr, st, off, t, r, first, a, b);
+        // beta of the tile's steps, right to left from the vector of its last step
+        double bv = live ? BO[t * SP + j] : 0.0;
+        {
+            uint64_t w = b - 1;
+            double x = live ? E[w * S + j] - M[w] : 0.0;
+            for (;;) {
+                if (live) B[w * S + j] = bv;
+                if (w == a) break;
+                const double e = live ? exp(x) : 0.0;
+                --w;
+                x = live ? E[w * S + j] - M[w] : 0.0;
+                const double u = e * bv;
+                double nb = 0.0;
+#pragma unroll
+                for (int i = 0; i < SP; ++i) nb += arow[i] * __shfl(u, i, SP);
+                (void)chain_scale2<SP>(nb);
+                bv = nb;
+            }
+        }
+        // alpha, gamma and xi left to right; bv is now beta of the tile's first step
+        double xi[SP];
+#pragma unroll
+        for (int i = 0; i < SP; ++i) xi[i] = 0.0;
+        double x = live ? E[a * S + j] - M[a] : 0.0, bw = bv, al;
+        uint64_t w = a;
+        if (first) {
+            const double e = live ? exp(x) : 0.0;
+            const double p = pj * (e * bw);
+            const double g0 = p / chain_sum<SP>(p);
+            if (live) Gm[a * S + j] = g0, V[r * Ev + S * S + j] = g0;
+            al = pj * e;
+            (void)chain_scale2<SP>(al);
+            w = a + 1;
+            if (w < b) x = live ? E[w * S + j] - M[w] : 0.0, bw = live ? B[w * S + j] : 0.0;
+        } else {
+            al = live ? AI[t * SP + j] : 0.0;
+        }
+        while (w < b) {
+            const double e = live ? exp(x) : 0.0;
+            const double c = e * bw;
+            const uint64_t wn = w + 1;
+            if (wn < b) x = live ? E[wn * S + j] - M[wn] : 0.0, bw = live ? B[wn * S + j] : 0.0;
+            double wv[SP], gs = 0.0, col = 0.0;
+#pragma unroll
+            for (int i = 0; i < SP; ++i) {
+                const double pr = __shfl(al, i, SP) * acol[i];
+                gs += pr;
+                wv[i] = pr * c;
+                col += wv[i];
+            }
+            const double inv = 1.0 / chain_sum<SP>(col);
+#pragma unroll
+            for (int i = 0; i < SP; ++i) xi[i] += wv[i] * inv;
+            if (live) Gm[w * S + j] = col * inv;
+            al = gs * e;
+            (void)chain_scale2<SP>(al);
+            w = wn;
+        }
+#pragma unroll
+        for (int i = 0; i < SP; ++i) XI[t * (SP * SP) + (uint32_t)i * SP + j] = xi[i];
+    }
+}
+
+// MP[8 t + j] = the state before tile t on the best path that ends the tile in state j.
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_scan_path_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                                 const uint64_t *__restrict__ off, const uint32_t *__restrict__ ti,
+                                                                 const uint64_t *__restrict__ sr, const uint64_t *__restrict__ st,
+                                                                 uint64_t nt, uint32_t S, const int64_t *__restrict__ qpar,
+                                                                 const int64_t *__restrict__ DI, uint8_t *__restrict__ BP,
+                                                                 uint8_t *__restrict__ MP) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    long long qcol[SP];
+#pragma unroll
+    for (int i = 0; i < SP; ++i) qcol[i] = (live && (uint32_t)i < S) ? (long long)qpar[(uint32_t)i * S + j] : 0ll;
+    const long long qp = live ? (long long)qpar[S * S + j] : 0ll;
+    for (uint64_t t = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; t < nt; t += groups) {
+        uint64_t r, a, b;
+        bool first;
+        chain_scan_tile(ti, sr, st, off, t, r, first, a, b);
+        long long d;
+        uint64_t w = a;
+        uint32_t org = j;
+        if (first) {
+            d = qp + (live ? (long long)chain_quant(E[a * S + j] - M[a]) : 0ll);
+            w = a + 1;
+        } else {
+            d = live ? (long long)DI[t * SP + j] : 0ll;
+        }
+        double x = (live && w < b) ? E[w * S + j] - M[w] : 0.0;
+        while (w < b) {
+            const long long q = (long long)chain_quant(x);
+            const uint64_t wn = w + 1;
+            x = (live && wn < b) ? E[wn * S + j] - M[wn] : 0.0;
+            long long best = __shfl(d, 0, SP) + qcol[0];
+            uint32_t k = 0;
+#pragma unroll
+            for (int i = 1; i < SP; ++i) {
+                const long long c = __shfl(d, i, SP) + qcol[i];
+                if ((uint32_t)i < S && c > best) best = c, k = (uint32_t)i;   // a tie stays with the smaller predecessor
+            }
+            d = best + q;
+            BP[8 * w + j] = (uint8_t)k;
+            org = __shfl(org, k, SP);
+            w = wn;
+        }
+        MP[8 * t + j] = (uint8_t)org;
+    }
+}
+
+__global__ __launch_bounds__(256) void phk_chain_scan_fold_kernel(const double *__restrict__ XI, const uint64_t *__restrict__ sr,
+                                                                  const uint64_t *__restrict__ st, uint64_t ns, uint32_t S,
+                                                                  uint32_t SP, double *__restrict__ V) {
+    const uint64_t SS = (uint64_t)S * S, Ev = SS + S + 1, G = (uint64_t)SP * SP;
+    for (uint64_t x = (uint64_t)blockIdx.x * 256 + threadIdx.x; x < ns * SS; x += (uint64_t)gridDim.x * 256) {
+        const uint64_t s = x / SS, q = x % SS;
+        const double *p = XI + st[s] * G + (q / S) * SP + q % S;
+        const uint64_t K = st[s + 1] - st[s];
+        double acc = 0.0;
+#pragma unroll 16
+        for (uint64_t k = 0; k < K; ++k) acc += p[k * G];
+        V[sr[s] * Ev + q] = acc;
+    }
+}
+
+__global__ __launch_bounds__(64) void phk_chain_scan_ends_kernel(const uint64_t *__restrict__ sr, const uint64_t *__restrict__ st,
+                                                                 uint64_t ns, const uint8_t *__restrict__ last,
+                                                                 const uint64_t *__restrict__ MP, uint8_t *__restrict__ END) {
+    for (uint64_t s = (uint64_t)blockIdx.x * 64 + threadIdx.x; s < ns; s += (uint64_t)gridDim.x * 64) {
+        const uint64_t t0 = st[s];
+        uint32_t x = last[sr[s]];
+#pragma unroll 8
+        for (uint64_t t = st[s + 1]; t > t0; --t) {
+            END[t - 1] = (uint8_t)x;
+            x = (uint32_t)(MP[t - 1] >> (8 * x)) & 0xffu;   // (the map of the record's first tile is not followed)
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void phk_chain_scan_fill_kernel(const uint64_t *__restrict__ off, const uint32_t *__restrict__ ti,
+                                                                 const uint64_t *__restrict__ sr, const uint64_t *__restrict__ st,
+                                                                 uint64_t nt, const uint8_t *__restrict__ END,
+                                                                 const uint64_t *__restrict__ BP, uint8_t *__restrict__ state) {
+    for (uint64_t t = (uint64_t)blockIdx.x * 64 + threadIdx.x; t < nt; t += (uint64_t)gridDim.x * 64) {
+        uint64_t r, a, b;
+        bool first;
+        chain_scan_tile(ti, sr, st, off, t, r, first, a, b);
+        uint32_t s = END[t];
+#pragma unroll 8
+        for (uint64_t w = b; w > a; --w) {
+            state[w - 1] = (uint8_t)s;
+            s = (uint32_t)(BP[w - 1] >> (8 * s)) & 0xffu;
+        }
+    }
+}
+
+extern "C" uint64_t phk_chain_tile(void) { return PHK_CHAIN_TILE; }
+extern "C" uint64_t phk_chain_scan_grid_pass(void) { return CH_SCAN_PASS; }
+
 // ---- the resident chain ------------------------------------------------------------------------------------------------
 struct phk_chain {
     uint64_t n = 0, R = 0, D = 0, B = 0;   // B: rows per batch of the emission and expectation passes
@@ -307,6 +721,10 @@ struct phk_chain {
     bool from_counts = false, ready = false;
     const uint32_t *counts = nullptr;      // the batch's rows, or own_counts
     PhkDevMem own_counts, off, E, M, Bt, G, BP, state, par, qpar, logp, V, last, score, Rx, part, fold[2];
+    // the tile scan (phk_chain_set_scan): ns scanned records, nt tiles; 0 = every record on the per-record route
+    uint64_t scan_from = 0, ns = 0, nt = 0;
+    std::vector<uint64_t> h_off;           // the offsets on the host: the tile tables are built from them
+    PhkDevMem s_ti, s_sr, s_st, s_F, s_FE, s_Vq, s_SM, s_AI, s_BO, s_DI, s_XI, s_MP, s_END;
 };
 
 static unsigned chain_grid(uint64_t items, uint64_t per_block, uint64_t cap) {
@@ -356,6 +774,7 @@ static int chain_alloc(phk_ctx *ctx, const char *who, phk_chain *c, const uint64
         PHK_TRY(c->part.alloc(who, "partial vectors", nblocks * Em * 8));
     }
     if (R) PHK_TRY(phk_copy_to_device(ctx, c->off.ptr, offsets, (R + 1) * 8));
+    if (R) c->h_off.assign(offsets, offsets + R + 1);
     return PHK_OK;
 }
 
@@ -437,6 +856,59 @@ extern "C" int phk_chain_destroy(phk_ctx *ctx, phk_chain *c) {
         (void)hipStreamSynchronize(ctx->stream);
     }
     delete c;
+    return PHK_OK;
+}
+
+static int chain_scan_alloc(phk_ctx *ctx, phk_chain *c, const std::vector<uint32_t> &ti, const std::vector<uint64_t> &sr,
+                            const std::vector<uint64_t> &st) {
+    const char *who = "phk_chain_set_scan";
+    const uint64_t nt = ti.size(), ns = sr.size(), SP = c->S <= 2 ? 2 : (c->S <= 4 ? 4 : 8), G = SP * SP;
+    PHK_TRY(c->s_ti.alloc(who, "tile table", nt * 4));
+    PHK_TRY(c->s_sr.alloc(who, "tile table", ns * 8));
+    PHK_TRY(c->s_st.alloc(who, "tile table", (ns + 1) * 8));
+    PHK_TRY(c->s_F.alloc(who, "tile matrices", nt * G * 8));
+    PHK_TRY(c->s_FE.alloc(who, "tile exponents", nt * 4));
+    PHK_TRY(c->s_Vq.alloc(who, "tile matrices", nt * G * 8));
+    PHK_TRY(c->s_SM.alloc(who, "tile sums", nt * 8));
+    PHK_TRY(c->s_AI.alloc(who, "entering vectors", nt * SP * 8));
+    PHK_TRY(c->s_BO.alloc(who, "entering vectors", nt * SP * 8));
+    PHK_TRY(c->s_DI.alloc(who, "entering vectors", nt * SP * 8));
+    PHK_TRY(c->s_XI.alloc(who, "tile vectors", nt * G * 8));
+    PHK_TRY(c->s_MP.alloc(who, "tile maps", nt * 8));
+    PHK_TRY(c->s_END.alloc(who, "tile end states", nt));
+    PHK_TRY(phk_copy_to_device(ctx, c->s_ti.ptr, ti.data(), nt * 4));
+    PHK_TRY(phk_copy_to_device(ctx, c->s_sr.ptr, sr.data(), ns * 8));
+    PHK_TRY(phk_copy_to_device(ctx, c->s_st.ptr, st.data(), (ns + 1) * 8));
+    PHK_HIP(hipStreamSynchronize(ctx->stream));   // the tables leave scope
+    return PHK_OK;
+}
+
+extern "C" int phk_chain_set_scan(phk_ctx *ctx, phk_chain *c, uint64_t scan_from) {
+    PHK_ENTER(ctx, "phk_chain_set_scan");
+    PHK_REQUIRE(c, "phk_chain_set_scan: NULL chain");
+    PHK_HIP(hipStreamSynchronize(ctx->stream));   // the buffers of an earlier threshold may be in use
+    PhkDevMem *mem[] = {&c->s_ti, &c->s_sr, &c->s_st, &c->s_F, &c->s_FE, &c->s_Vq, &c->s_SM,
+                        &c->s_AI, &c->s_BO, &c->s_DI, &c->s_XI, &c->s_MP, &c->s_END};
+    for (PhkDevMem *m : mem) m->release();
+    c->scan_from = 0, c->ns = 0, c->nt = 0;
+    if (scan_from == 0 || c->n == 0) return PHK_OK;
+    std::vector<uint32_t> ti;
+    std::vector<uint64_t> sr, st;
+    for (uint64_t r = 0; r < c->R; ++r) {
+        const uint64_t len = c->h_off[r + 1] - c->h_off[r];
+        if (len < scan_from) continue;   // (scan_from >= 1: a record without windows is never scanned)
+        st.push_back(ti.size());
+        ti.insert(ti.end(), phk_div_up(len, PHK_CHAIN_TILE), (uint32_t)sr.size());
+        sr.push_back(r);
+    }
+    if (sr.empty()) return PHK_OK;
+    st.push_back(ti.size());
+    const int rc = chain_scan_alloc(ctx, c, ti, sr, st);
+    if (rc != PHK_OK) {
+        for (PhkDevMem *m : mem) m->release();
+        return rc;
+    }
+    c->scan_from = scan_from, c->ns = sr.size(), c->nt = ti.size();
     return PHK_OK;
 }
 
@@ -527,19 +999,91 @@ extern "C" int phk_chain_emissions(phk_ctx *ctx, const phk_chain *c, double *E) 
         }                     \
     } while (0)
 
+// the scanned records' tiles: F, Vq and the sums of M
+static int chain_scan_tiles(phk_ctx *ctx, const phk_chain *c) {
+#define CH_TILES(SP)                                                                                                          \
+    PHK_LAUNCH(ctx, "phk_chain_scan_tile_kernel",                                                                             \
+               phk_chain_scan_tile_kernel<SP>                                                                                 \
+               <<<dim3(chain_grid(c->nt, 64 / (SP * SP), CH_SCAN_PASS / (64 / (SP * SP)))), dim3(64), 0, ctx->stream>>>(      \
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), \
+                   c->s_st.as<uint64_t>(), c->nt, c->S, c->par.as<double>(), c->qpar.as<int64_t>(), c->s_F.as<double>(),      \
+                   c->s_FE.as<int32_t>(), c->s_Vq.as<int64_t>(), c->s_SM.as<double>()))
+    CHAIN_BY_SP(c->S, CH_TILES);
+#undef CH_TILES
+    return PHK_OK;
+}
+
+// the carry over the scanned records' tiles: `roles` roles from `role0` on (0 alpha, 1 beta, 2 delta)
+static int chain_scan_carry(phk_ctx *ctx, const phk_chain *c, uint32_t role0, uint32_t roles) {
+#define CH_CARRY(SP)                                                                                                          \
+    PHK_LAUNCH(ctx, "phk_chain_scan_carry_kernel",                                                                            \
+               phk_chain_scan_carry_kernel<SP>                                                                                \
+               <<<dim3(chain_grid(c->ns, 64 / (SP * SP), CH_BLOCKS_MAX), roles), dim3(64), 0, ctx->stream>>>(                 \
+                   c->s_F.as<double>(), c->s_FE.as<int32_t>(), c->s_Vq.as<int64_t>(), c->s_SM.as<double>(),                   \
+                   c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->ns, c->S, role0, c->s_AI.as<double>(),                  \
+                   c->s_BO.as<double>(), c->s_DI.as<int64_t>(), c->V.as<double>(), c->score.as<int64_t>(),                    \
+                   c->last.as<uint8_t>()))
+    CHAIN_BY_SP(c->S, CH_CARRY);
+#undef CH_CARRY
+    return PHK_OK;
+}
+
+// forward-backward of the scanned records (after chain_scan_tiles): B, G and V as the per-record kernels leave them
+static int chain_scan_forward_backward(phk_ctx *ctx, const phk_chain *c) {
+    PHK_TRY(chain_scan_carry(ctx, c, 0, 2));
+#define CH_WALK(SP)                                                                                                           \
+    PHK_LAUNCH(ctx, "phk_chain_scan_walk_kernel",                                                                             \
+               phk_chain_scan_walk_kernel<SP>                                                                                 \
+               <<<dim3(chain_grid(c->nt, 64 / SP, CH_SCAN_PASS / (64 / SP))), dim3(64), 0, ctx->stream>>>(                    \
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), \
+                   c->s_st.as<uint64_t>(), c->nt, c->S, c->par.as<double>(), c->s_AI.as<double>(), c->s_BO.as<double>(),      \
+                   c->Bt.as<double>(), c->G.as<double>(), c->s_XI.as<double>(), c->V.as<double>()));                          \
+    PHK_LAUNCH(ctx, "phk_chain_scan_fold_kernel",                                                                             \
+               phk_chain_scan_fold_kernel<<<dim3(chain_grid(c->ns * c->S * c->S, 256, 4096)), dim3(256), 0, ctx->stream>>>(   \
+                   c->s_XI.as<double>(), c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->ns, c->S, SP, c->V.as<double>()))
+    CHAIN_BY_SP(c->S, CH_WALK);
+#undef CH_WALK
+    return PHK_OK;
+}
+
+// the max-plus half of the scanned records (after chain_scan_tiles): BP, state, score and last as the per-record kernels
+// leave them
+static int chain_scan_path(phk_ctx *ctx, const phk_chain *c) {
+    PHK_TRY(chain_scan_carry(ctx, c, 2, 1));
+#define CH_PATH(SP)                                                                                                           \
+    PHK_LAUNCH(ctx, "phk_chain_scan_path_kernel",                                                                             \
+               phk_chain_scan_path_kernel<SP>                                                                                 \
+               <<<dim3(chain_grid(c->nt, 64 / SP, CH_SCAN_PASS / (64 / SP))), dim3(64), 0, ctx->stream>>>(                    \
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), \
+                   c->s_st.as<uint64_t>(), c->nt, c->S, c->qpar.as<int64_t>(), c->s_DI.as<int64_t>(), c->BP.as<uint8_t>(),    \
+                   c->s_MP.as<uint8_t>()))
+    CHAIN_BY_SP(c->S, CH_PATH);
+#undef CH_PATH
+    PHK_LAUNCH(ctx, "phk_chain_scan_ends_kernel",
+               phk_chain_scan_ends_kernel<<<dim3(chain_grid(c->ns, 64, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(
+                   c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->ns, c->last.as<uint8_t>(), c->s_MP.as<uint64_t>(),
+                   c->s_END.as<uint8_t>()));
+    PHK_LAUNCH(ctx, "phk_chain_scan_fill_kernel",
+               phk_chain_scan_fill_kernel<<<dim3(chain_grid(c->nt, 64, CH_SCAN_PASS / 64)), dim3(64), 0, ctx->stream>>>(
+                   c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->nt,
+                   c->s_END.as<uint8_t>(), c->BP.as<uint64_t>(), c->state.as<uint8_t>()));
+    return PHK_OK;
+}
+
 // backward then forward over every record: B, G and the records' vectors V
 static int chain_forward_backward(phk_ctx *ctx, const phk_chain *c) {
     const double *E = c->E.as<double>(), *M = c->M.as<double>(), *par = c->par.as<double>();
-    const uint64_t *off = c->off.as<uint64_t>();
+    const uint64_t *off = c->off.as<uint64_t>(), sf = c->scan_from;
+    if (sf) PHK_TRY(chain_scan_forward_backward(ctx, c));
 #define CH_FB(SP)                                                                                                             \
     {                                                                                                                         \
         const dim3 grid(chain_grid(c->R, 64 / SP, CH_BLOCKS_MAX));                                                            \
         PHK_LAUNCH(ctx, "phk_chain_backward_kernel", phk_chain_backward_kernel<SP><<<grid, dim3(64), 0, ctx->stream>>>(       \
-                                                         E, M, off, c->R, c->S, par, c->Bt.as<double>()));                    \
+                                                         E, M, off, c->R, c->S, par, c->Bt.as<double>(), sf));                \
         PHK_LAUNCH(ctx, "phk_chain_forward_kernel",                                                                           \
                    phk_chain_forward_kernel<SP><<<grid, dim3(64), 0, ctx->stream>>>(E, M, off, c->R, c->S, par,               \
                                                                                     c->Bt.as<double>(), c->G.as<double>(),    \
-                                                                                    c->V.as<double>()));                      \
+                                                                                    c->V.as<double>(), sf));                  \
     }
     CHAIN_BY_SP(c->S, CH_FB);
 #undef CH_FB
@@ -564,6 +1108,7 @@ static int chain_fold(phk_ctx *ctx, const phk_chain *c, const double *in, uint64
 static int chain_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, double *Ns, double *xi, double *gamma0,
                             double *log_evidence, double *log_evidence_rec) {
     const uint64_t S = c->S, D = c->D, R = c->R, n = c->n, Ev = S * S + S + 1, Em = S * D + S + 1;
+    if (c->scan_from) PHK_TRY(chain_scan_tiles(ctx, c));
     PHK_TRY(chain_forward_backward(ctx, c));
     const double *tot;
     PHK_TRY(chain_fold(ctx, c, c->V.as<double>(), R, Ev, &tot));
@@ -627,18 +1172,20 @@ extern "C" int phk_chain_expect(phk_ctx *ctx, const phk_chain *c, double *T, dou
 static int chain_decode_run(phk_ctx *ctx, const phk_chain *c, uint8_t *state, double *posterior, double *log_evidence_rec,
                             int64_t *path_score) {
     const uint64_t S = c->S, R = c->R, n = c->n, Ev = S * S + S + 1;
-    const uint64_t *off = c->off.as<uint64_t>();
+    const uint64_t *off = c->off.as<uint64_t>(), sf = c->scan_from;
+    if (sf) PHK_TRY(chain_scan_tiles(ctx, c));
     if (posterior || log_evidence_rec) PHK_TRY(chain_forward_backward(ctx, c));
+    if (sf) PHK_TRY(chain_scan_path(ctx, c));
 #define CH_VIT(SP)                                                                                                        \
     PHK_LAUNCH(ctx, "phk_chain_viterbi_kernel",                                                                           \
                phk_chain_viterbi_kernel<SP><<<dim3(chain_grid(R, 64 / SP, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(   \
                    c->E.as<double>(), c->M.as<double>(), off, R, c->S, c->qpar.as<int64_t>(), c->BP.as<uint8_t>(),        \
-                   c->score.as<int64_t>(), c->last.as<uint8_t>()))
+                   c->score.as<int64_t>(), c->last.as<uint8_t>(), sf))
     CHAIN_BY_SP(c->S, CH_VIT);
 #undef CH_VIT
     PHK_LAUNCH(ctx, "phk_chain_trace_kernel",
                phk_chain_trace_kernel<<<dim3(chain_grid(R, 64, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(
-                   off, R, c->last.as<uint8_t>(), c->BP.as<uint64_t>(), c->state.as<uint8_t>()));
+                   off, R, c->last.as<uint8_t>(), c->BP.as<uint64_t>(), c->state.as<uint8_t>(), sf));
     PHK_TRY(phk_copy_to_host(ctx, state, c->state.ptr, n));
     if (path_score) PHK_TRY(phk_copy_to_host(ctx, path_score, c->score.ptr, R * 8));
     if (posterior) PHK_TRY(phk_copy_to_host(ctx, posterior, c->G.ptr, n * S * 8));
