@@ -686,6 +686,30 @@ int phk_chain_set_scan(phk_ctx *ctx, phk_chain *chain, uint64_t scan_from);
 uint64_t phk_chain_tile(void);
 uint64_t phk_chain_scan_grid_pass(void);
 
+/* Grouped chains: one set of parameters per group of consecutive records, all groups in one call.
+ * phk_chain_set_groups(chain, group_offsets[G + 1], G): group g holds the records group_offsets[g] .. group_offsets[g + 1] - 1
+ * (from 0 to R, non-decreasing; a group without records or without windows is legal).  G = 0 with NULL offsets returns the
+ * chain to one set of parameters (phk_chain_set comes next).  PHK_ERR_ARG for a chain made from emissions, for offsets that
+ * do not run from 0 to R or decrease, and while the tile scan is asked for (phk_chain_set_scan with a threshold on a grouped
+ * chain is PHK_ERR_ARG too).
+ * phk_chain_set_grouped(log_profiles[G][S][D], D, trans[G][S][S], init[G][S], qlog_trans, qlog_init, temper, active[G] or
+ * NULL = all): the parameters of every group, checked as phk_chain_set checks them (PHK_ERR_ARG / PHK_ERR_NAN before any
+ * launch; the chain then waits for a successful set) for the active groups only: the parameters of an inactive group are
+ * not read.  Forms the emissions of the active groups.
+ * phk_chain_expect_grouped: one E-step of every group: T[G][S][D], Ns[G][S], xi[G][S][S], gamma0[G][S], log_evidence[G] and
+ * (or NULL) log_evidence_rec[R].  phk_chain_decode and phk_chain_emissions work on a grouped chain: every record with its
+ * group's parameters.  Every result of a group is bit for bit what a chain made from that group's records alone gives with
+ * phk_chain_set / phk_chain_expect / phk_chain_decode: the expectation blocks are anchored at the group's first window and
+ * both trees run over the group's own vectors.  An inactive group, and a group without windows, is passed over by every
+ * kernel: its outputs are zeros (T, Ns, xi, gamma0, evidence, emissions, state, posterior, path score).  phk_chain_set and
+ * phk_chain_expect on a grouped chain, and the grouped calls on a chain without groups, are PHK_ERR_ARG. */
+int phk_chain_set_groups(phk_ctx *ctx, phk_chain *chain, const uint64_t *group_offsets, uint64_t G);
+int phk_chain_set_grouped(phk_ctx *ctx, phk_chain *chain, const double *log_profiles, uint64_t D, const double *trans,
+                          const double *init, const int64_t *qlog_trans, const int64_t *qlog_init, double temper,
+                          const uint8_t *active);
+int phk_chain_expect_grouped(phk_ctx *ctx, const phk_chain *chain, double *T, double *Ns, double *xi, double *gamma0,
+                             double *log_evidence, double *log_evidence_rec);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -137,6 +137,10 @@ SIGNATURES = {
     "phk_chain_set_scan": (c_int, [c_void_p, c_void_p, c_u64]),
     "phk_chain_tile": (c_u64, []),
     "phk_chain_scan_grid_pass": (c_u64, []),
+    "phk_chain_set_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_u64]),
+    "phk_chain_set_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
+                                      c_void_p]),
+    "phk_chain_expect_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1365,6 +1369,7 @@ class Chain(_Resident):
                                           ctypes.byref(h))
         self._rc(rc)
         self.handle = h
+        self.G = 0     # groups (set_groups); 0: one set of parameters for every record
 
     @staticmethod
     def _rc(rc):
@@ -1395,6 +1400,54 @@ class Chain(_Resident):
         if not 0 <= scan_from < 2 ** 64:
             raise ValueError("scan_from = %r" % (scan_from,))
         self._rc(self.ctx.lib.phk_chain_set_scan(self.ctx.handle, self.handle, scan_from))
+
+    def set_groups(self, group_offsets):
+        """Cuts the records into groups of consecutive records (phk_chain_set_groups):
+        ``group_offsets`` (G + 1,) runs from 0 to R; every group then has parameters of its own (``set_grouped``,
+        ``expect_grouped``; ``decode`` and ``emissions`` work as before).  None returns the chain to one set of parameters."""
+        self._open()
+        if group_offsets is None:
+            self._rc(self.ctx.lib.phk_chain_set_groups(self.ctx.handle, self.handle, None, 0))
+            self.G = 0
+            return
+        go = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        if go.ndim != 1 or go.shape[0] < 2:
+            raise ValueError("group_offsets must be (G + 1,) with G >= 1")
+        self._rc(self.ctx.lib.phk_chain_set_groups(self.ctx.handle, self.handle, ptr(go), go.shape[0] - 1))
+        self.G = go.shape[0] - 1
+
+    def set_grouped(self, log_profiles, trans, init, qlog_trans, qlog_init, temper=1.0, active=None):
+        """The parameters of every group (phk_chain_set_grouped): ``log_profiles`` (G, S, D), ``trans`` (G, S, S), ``init``
+        (G, S) with their quantised logarithms; ``active`` (G,) bool or None for all.  An inactive group is passed over by
+        every kernel, its parameters are not read and its outputs are zeros."""
+        self._open()
+        S, G = self.S, self.G
+        lp = np.ascontiguousarray(log_profiles, dtype=np.float64)
+        tr, pi = np.ascontiguousarray(trans, dtype=np.float64), np.ascontiguousarray(init, dtype=np.float64)
+        qt, qp = np.ascontiguousarray(qlog_trans, dtype=np.int64), np.ascontiguousarray(qlog_init, dtype=np.int64)
+        if G and (lp.ndim != 3 or lp.shape[:2] != (G, S) or tr.shape != (G, S, S) or pi.shape != (G, S)
+                  or qt.shape != (G, S, S) or qp.shape != (G, S)):
+            raise ValueError("log_profiles must be (%d, %d, D), trans (%d, %d, %d) and init (%d, %d), with their quantised "
+                             "logarithms" % (G, S, G, S, S, G, S))
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(np.asarray(active).astype(bool), dtype=np.uint8)
+            if act.shape != (G,):
+                raise ValueError("active must be (%d,)" % G)
+        self._rc(self.ctx.lib.phk_chain_set_grouped(self.ctx.handle, self.handle, ptr(lp), lp.shape[-1], ptr(tr), ptr(pi), ptr(qt),
+                                                    ptr(qp), float(temper), ptr(act)))
+
+    def expect_grouped(self, records=False):
+        """One E-step of every group (phk_chain_expect_grouped): (T (G, S, D), Ns (G, S), xi (G, S, S), gamma0 (G, S),
+        log_evidence (G,)), and with ``records`` also the log evidence per record (R,)."""
+        self._open()
+        S, G = self.S, self.G
+        T, Ns, xi = np.zeros((G, S, self.D)), np.zeros((G, S)), np.zeros((G, S, S))
+        g0, L = np.zeros((G, S)), np.zeros(G)
+        rec = np.zeros(self.R) if records else None
+        self._rc(self.ctx.lib.phk_chain_expect_grouped(self.ctx.handle, self.handle, ptr(T), ptr(Ns), ptr(xi), ptr(g0), ptr(L),
+                                                       ptr(rec)))
+        return (T, Ns, xi, g0, L) + ((rec,) if records else ())
 
     def emissions(self):
         """E (n, S) float64 as the device holds it (phk_chain_emissions)."""

@@ -28,7 +28,11 @@ Two findings of the CPU study this module was built after:
     fit(counts_or_batch, owner_or_offsets, n_states, ...)       a Composition
     segment_sequences(fasta_or_sequences, n_states, ...)        a ComposedSequences (fit + decode of the windows)
     load(path)                                                  a Composition saved with Composition.save
-    python -m phamers_amd.compose -in FASTA -out DIR -S n [--scan [N]]
+    fit_groups(counts_or_batch, owner_or_offsets, group_offsets, n_states, ...)
+                                                                a Compositions: one fit per group of consecutive records,
+                                                                all groups in one device call per iteration (section 4.28)
+    load_groups(path)                                           a Compositions saved with Compositions.save
+    python -m phamers_amd.compose -in FASTA -out DIR -S n [--scan [N]] [--per_record]
 """
 import collections
 import os
@@ -344,6 +348,255 @@ def fit(counts_or_batch, owner_or_offsets, n_states, mean_region=30000, step=500
     return Composition(logp, A, pi, t, a, Ns, T, np.array(trace, dtype=np.float64), len(trace) - 1, converged, bic)
 
 
+# ---- one fit per group of records ---------------------------------------------------------------------
+GROUP_FITTED, GROUP_TOO_SHORT = 0, 1     # ``Compositions.status``
+
+
+class _DeviceGroupEStep(object):
+    """The device half of ``fit_groups`` and ``Compositions.decode``: the rows resident once in a grouped ``_lib.Chain``."""
+
+    def __init__(self, counts_or_batch, offsets, group_offsets, n_states, batch_rows=0):
+        self.base = _DeviceEStep(counts_or_batch, offsets, n_states, batch_rows)
+        self.n, self.D, self.offsets = self.base.n, self.base.D, self.base.offsets
+        self.group_offsets = np.ascontiguousarray(group_offsets, dtype=np.uint64)
+        try:
+            self.base.chain.set_groups(self.group_offsets)
+        except Exception:
+            self.base.close()
+            raise
+
+    def counts(self):
+        return self.base.counts()
+
+    def _set(self, log_profiles, trans, init, temper, active):
+        tr, pi = np.asarray(trans, dtype=np.float64), np.asarray(init, dtype=np.float64)
+        self.base.chain.set_grouped(log_profiles, tr, pi, quantise(np.log(tr)), quantise(np.log(pi)), temper, active)
+
+    def __call__(self, log_profiles, trans, init, temper, active):
+        """(T (G, S, D), Ns, xi, gamma0, L (G,)) of one E-step of the active groups (zeros for the others)."""
+        self._set(log_profiles, trans, init, temper, active)
+        return self.base.chain.expect_grouped()
+
+    def decode(self, log_profiles, trans, init, temper, active):
+        self._set(log_profiles, trans, init, temper, active)
+        return self.base.chain.decode()
+
+    def close(self):
+        self.base.close()
+
+
+def _estep_groups(counts_or_batch, offsets, group_offsets, n_states, batch_rows=0):
+    """The grouped E-step object of the rows (the tests put the statement in its place)."""
+    return _DeviceGroupEStep(counts_or_batch, offsets, group_offsets, n_states, batch_rows)
+
+
+def _group_offsets(group_offsets, n_records):
+    go = np.asarray(group_offsets)
+    if go.ndim != 1 or len(go) < 1 or not np.issubdtype(go.dtype, np.integer):
+        raise ValueError("group_offsets must be (G + 1,) integers")
+    go = go.astype(np.int64)
+    if go[0] != 0 or go[-1] != n_records or (np.diff(go) < 0).any():
+        raise ValueError("group_offsets must run from 0 to the %d records and never decrease" % n_records)
+    return go.astype(np.uint64)
+
+
+class _GroupRows(object):
+    """The rows of one group as ``_initial_profiles`` reads them: its count rows and its own record offsets."""
+
+    def __init__(self, rows, offsets, D):
+        self.rows, self.offsets, self.D = rows, offsets, D
+
+    def counts(self):
+        return self.rows
+
+
+def _group_rows(counts, offsets, group_offsets, g, D):
+    r0, r1 = int(group_offsets[g]), int(group_offsets[g + 1])
+    off = np.asarray(offsets[r0:r1 + 1]).astype(np.int64)
+    return _GroupRows(counts[int(off[0]):int(off[-1])], (off - off[0]).astype(np.uint64), D)
+
+
+def group_status(rows, offsets, n_states, block):
+    """``GROUP_TOO_SHORT`` for rows whose records hold fewer than ``n_states`` blocks of ``block`` windows with k-mers
+    (``start`` has nothing to choose from; ``fit`` raises for them), else ``GROUP_FITTED``."""
+    live = int((_blocks(rows, offsets, block).sum(axis=1) > 0).sum()) if len(rows) else 0
+    return GROUP_TOO_SHORT if live < n_states else GROUP_FITTED
+
+
+class Compositions(object):
+    """What ``fit_groups`` returns: one fitted chain per group of records.  ``len`` and ``[g]`` (a ``Composition``, or None
+    for a group that was not fitted); stacked over the groups ``log_profiles`` (G, S, D), ``trans`` (G, S, S), ``init``
+    (G, S), ``occupancy`` (G, S), ``expected_counts`` (G, S, D), ``n_iter``, ``converged``, ``bic`` and ``status`` (G,)
+    (``GROUP_FITTED`` or ``GROUP_TOO_SHORT``; a group that was not fitted has NaN parameters); ``traces``: a list of
+    (iterates, 2) arrays.  State numbers are a group's own: state 1 of one group and state 1 of another have nothing to
+    do with each other (``label`` scores every state against two references, which is comparable)."""
+
+    def __init__(self, compositions, status, n_states, n_columns, temper=1.0, pseudocount=0.5):
+        self._items = list(compositions)
+        self.status = np.asarray(status, dtype=np.int64).reshape(len(self._items))
+        self.n_states, self.n_columns = _states(n_states), int(n_columns)
+        self.temper, self.pseudocount = _temper(temper), float(pseudocount)
+        G, S, D = len(self._items), self.n_states, self.n_columns
+        for c in self._items:
+            if c is not None and c.log_profiles.shape != (S, D):
+                raise ValueError("every composition must be (%d, %d)" % (S, D))
+        stack = lambda name, shape: np.array([np.full(shape, np.nan) if c is None else getattr(c, name) for c in self._items],
+                                             dtype=np.float64).reshape((G,) + shape)
+        self.log_profiles, self.expected_counts = stack("log_profiles", (S, D)), stack("expected_counts", (S, D))
+        self.trans, self.init, self.occupancy = stack("trans", (S, S)), stack("init", (S,)), stack("occupancy", (S,))
+        self.bic = stack("bic", ())
+        self.n_iter = np.array([0 if c is None else c.n_iter for c in self._items], dtype=np.int64)
+        self.converged = np.array([False if c is None else c.converged for c in self._items], dtype=bool)
+        self.traces = [np.zeros((0, 2)) if c is None else c.trace for c in self._items]
+
+    def __len__(self):
+        return len(self._items)
+
+    def __getitem__(self, g):
+        return self._items[g]
+
+    @property
+    def fitted(self):
+        """(G,) bool: the groups that have a Composition."""
+        return np.array([c is not None for c in self._items], dtype=bool)
+
+    def decode(self, counts_or_batch, owner_or_offsets, group_offsets):
+        """Every record decoded with its group's chain, all groups in one device call: a ``Decoded`` over all the windows
+        and records.  The records of a group that was not fitted get state 0, NaN posteriors, NaN evidence and NaN path
+        score (path_score_q 0)."""
+        offsets = _record_offsets(counts_or_batch, owner_or_offsets)
+        go = _group_offsets(group_offsets, len(offsets) - 1)
+        if len(go) - 1 != len(self):
+            raise ValueError("%d groups, %d compositions" % (len(go) - 1, len(self)))
+        S, fitted = self.n_states, self.fitted
+        estep = _estep_groups(counts_or_batch, offsets, go, S)
+        try:
+            if estep.D != self.n_columns:
+                raise ValueError("the counts have %d columns, the compositions %d" % (estep.D, self.n_columns))
+            A0, pi0 = start_chain(S)
+            logp = np.where(fitted[:, None, None], self.log_profiles, 0.0)
+            A, pi = np.where(fitted[:, None, None], self.trans, A0), np.where(fitted[:, None], self.init, pi0)
+            state, post, le, ps = estep.decode(logp, A, pi, self.temper, fitted)
+        finally:
+            estep.close()
+        score = ps.astype(np.float64) * 2.0 ** -QUANT_BITS
+        off = offsets.astype(np.int64)
+        for g in np.flatnonzero(~fitted):
+            r0, r1 = int(go[g]), int(go[g + 1])
+            state[off[r0]:off[r1]], post[off[r0]:off[r1]] = 0, np.nan
+            le[r0:r1], score[r0:r1], ps[r0:r1] = np.nan, np.nan, 0
+        return Decoded(state, post, le, score, ps)
+
+    def label(self, positive_counts, negative_counts):
+        """(G, S) float64: ``Composition.label`` of every group -- every state's rint(T_s) row scored against the two
+        references, which is comparable between groups where state numbers are not (NaN for a group that was not fitted)."""
+        from . import likelihood
+        out = np.full((len(self), self.n_states), np.nan)
+        fitted = np.flatnonzero(self.fitted)
+        if len(fitted):
+            rows = np.rint(self.expected_counts[fitted]).reshape(-1, self.n_columns)
+            out[fitted] = likelihood.score(rows.astype(np.uint32), positive_counts, negative_counts, self.pseudocount,
+                                           per_kmer=True).reshape(len(fitted), self.n_states)
+        return out
+
+    def save(self, path):
+        """A ``.npz`` file that ``load_groups`` reads back."""
+        ends = np.cumsum([0] + [len(t) for t in self.traces])
+        trace = np.concatenate(self.traces).reshape(-1, 2) if len(self.traces) else np.zeros((0, 2))
+        with open(path, 'wb') as f:
+            np.savez(f, log_profiles=self.log_profiles, trans=self.trans, init=self.init, temper=self.temper,
+                     pseudocount=self.pseudocount, occupancy=self.occupancy, expected_counts=self.expected_counts, trace=trace,
+                     trace_offsets=ends, n_iter=self.n_iter, converged=self.converged, bic=self.bic, status=self.status,
+                     n_states=self.n_states, n_columns=self.n_columns)
+
+
+def load_groups(path):
+    """The Compositions of a file written by ``Compositions.save``."""
+    with np.load(path) as z:
+        t, a, ends = float(z["temper"]), float(z["pseudocount"]), z["trace_offsets"]
+        items = [None if z["status"][g] != GROUP_FITTED else
+                 Composition(z["log_profiles"][g], z["trans"][g], z["init"][g], t, a, z["occupancy"][g], z["expected_counts"][g],
+                             z["trace"][ends[g]:ends[g + 1]], int(z["n_iter"][g]), bool(z["converged"][g]), float(z["bic"][g]))
+                 for g in range(len(z["status"]))]
+        return Compositions(items, z["status"], int(z["n_states"]), int(z["n_columns"]), t, a)
+
+
+def fit_groups(counts_or_batch, owner_or_offsets, group_offsets, n_states, mean_region=30000, step=500, temper=1.0,
+               pseudocount=0.5, init=None, block=20, prior_counts=0, fit_transitions=True, p_start='fixed', max_iter=100,
+               tol=1e-6, **options):
+    """One ``fit`` per group of records, all groups side by side: the records (``owner_or_offsets`` as in ``fit``) are cut
+    into G groups of consecutive records by ``group_offsets`` (G + 1,) -- a scaffold, or the scaffolds of a bin --, every
+    group has its own profiles, transition matrix and start vector, and every Baum-Welch iteration is one device call for
+    all the groups that have not stopped.  Per group the start rule (``start`` on the group's own
+    records), ``start_chain``, ``m_step``, the stop rule and ``max_iter`` are ``fit``'s, and the group's ``Composition``
+    is bit for bit what ``fit`` gives on the group's records alone.  ``init``: as in ``fit`` for every group, or a list
+    with one entry per group.  A group with fewer than ``n_states`` blocks with k-mers (``fit`` raises for it) is not
+    fitted: status ``GROUP_TOO_SHORT``, NaN parameters, no device work.  The tile scan is not available here (``scan``
+    raises ValueError).  A ``Compositions``."""
+    if "scan" in options:
+        raise ValueError("fit_groups does not take the tile scan (scan=): a grouped chain runs the per-record route")
+    if options:
+        raise TypeError("fit_groups() got unexpected arguments %s" % sorted(options))
+    S, a, t = _states(n_states), _pseudocount(pseudocount), _temper(temper)
+    max_iter, tol = int(max_iter), float(tol)
+    if max_iter < 0 or not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("max_iter >= 0 and a finite tol >= 0 are required")
+    if p_start not in ('fixed', 'free'):
+        raise ValueError("p_start must be 'fixed' or 'free'")
+    A0, pi0 = start_chain(S, mean_region, step)
+    offsets = _record_offsets(counts_or_batch, owner_or_offsets)
+    go = _group_offsets(group_offsets, len(offsets) - 1)
+    G = len(go) - 1
+    inits = list(init) if isinstance(init, list) else [init] * G
+    if len(inits) != G:
+        raise ValueError("init lists %d groups of %d" % (len(inits), G))
+    estep = _estep_groups(counts_or_batch, offsets, go, S)
+    try:
+        D, counts = estep.D, estep.counts()
+        status = np.zeros(G, dtype=np.int64)
+        logp, A, pi = [np.zeros((S, D))] * G, [A0] * G, [pi0] * G
+        n_windows = np.zeros(G, dtype=np.int64)
+        for g in range(G):
+            rows = _group_rows(counts, offsets, go, g, D)
+            n_windows[g] = len(rows.rows)
+            status[g] = group_status(rows.rows, rows.offsets, S, block)
+            if status[g] == GROUP_FITTED:
+                logp[g] = _initial_profiles(rows, S, inits[g], block, a)
+        active = status == GROUP_FITTED
+        traces, F_prev = [[] for _ in range(G)], [None] * G
+        converged, T_last, Ns_last = np.zeros(G, dtype=bool), [None] * G, [None] * G
+        for it in range(max_iter + 1):
+            if not active.any():
+                break
+            T, Ns, xi, g0, L = estep(np.array(logp), np.array(A), np.array(pi), t, active)
+            for g in np.flatnonzero(active):
+                F = float(L[g]) + a * float(np.sum(logp[g]))
+                traces[g].append((float(L[g]), F))
+                T_last[g], Ns_last[g] = T[g], Ns[g]
+                if F_prev[g] is not None and F - F_prev[g] <= tol * max(1.0, abs(F)):
+                    converged[g], active[g] = True, False     # (a group that has stopped drops out of the later calls)
+                    continue
+                if it == max_iter:
+                    active[g] = False
+                    continue
+                F_prev[g] = F
+                logp[g], A2, pi2 = m_step(T[g], xi[g], g0[g], a, prior_counts, p_start, A[g], pi[g])
+                if fit_transitions:
+                    A[g], pi[g] = A2, pi2
+    finally:
+        estep.close()
+    free = S * (D - 1) + (S * (S - 1) if fit_transitions else 0) + (S - 1 if p_start == 'free' else 0)
+    items = []
+    for g in range(G):
+        if status[g] != GROUP_FITTED:
+            items.append(None)
+            continue
+        bic = -2.0 * float(traces[g][-1][0]) + free * float(np.log(max(int(n_windows[g]), 1)))
+        items.append(Composition(logp[g], A[g], pi[g], t, a, Ns_last[g].copy(), T_last[g].copy(), np.array(traces[g], dtype=np.float64),
+                                 len(traces[g]) - 1, bool(converged[g]), bic))
+    return Compositions(items, status, S, D, t, a)
+
+
 class ComposedSequences(object):
     """What ``segment_sequences`` returns: ``composition``; the windows' ``record_ids``, ``owner``, ``start``, ``window``,
     ``step``; ``state`` (n,), ``posterior`` (n, S); ``log_evidence`` and ``path_score`` per record."""
@@ -371,13 +624,21 @@ class ComposedSequences(object):
 
 
 def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_length=4, both_strands=False, scan=None,
-                      **fit_options):
+                      per_record=False, **fit_options):
     """Counts the windows of a FASTA file (or a list of strings) as one resident batch, fits ``n_states`` compositions to
     them and decodes: a ``ComposedSequences``.  ``temper`` defaults to ``segment.default_temper(window, step, k)``; the other
     ``fit_options`` are ``fit``'s (``step`` is passed on); ``scan`` goes to the fit and to the decode.  ValueError when no
-    sequence holds a window."""
+    sequence holds a window.
+
+    ``per_record=True`` fits one chain per record instead (``fit_groups`` with one group per record: a prophage or island
+    then stands out against its own scaffold, not against the other organisms of an assembly); ``composition`` is then
+    the ``Compositions``.  State numbers are then NOT comparable between records -- state 1 of one record and state 1 of
+    another are unrelated; ``Compositions.label`` scores every (record, state) against two references, which is.  A record
+    too short for ``n_states`` is not fitted (state 0, NaN posteriors).  ``per_record`` does not go with ``scan``."""
     from . import kmer
     scan = _scan(scan)
+    if per_record and scan:
+        raise ValueError("per_record does not go with the tile scan (scan=)")
     both_strands = kmer._check_strands(kmer.DNA, both_strands)
     record_ids, lengths, batch = kmer._windows_batch(fasta_or_sequences, kmer_length, window, step)
     if batch is None:
@@ -388,8 +649,13 @@ def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_l
         owner, first = kmer.window_plan(lengths, window, step)
         fit_options.setdefault("temper", default_temper(window, step, kmer_length))
         offsets = _KnownOffsets(np.concatenate(([0], np.cumsum(np.bincount(owner, minlength=len(record_ids))))))
-        comp = fit(batch, offsets, n_states, step=step, scan=scan, **fit_options)
-        decoded = comp.decode(batch, offsets, scan=scan)
+        if per_record:
+            groups = np.arange(len(record_ids) + 1, dtype=np.uint64)
+            comp = fit_groups(batch, offsets, groups, n_states, step=step, **fit_options)
+            decoded = comp.decode(batch, offsets, groups)
+        else:
+            comp = fit(batch, offsets, n_states, step=step, scan=scan, **fit_options)
+            decoded = comp.decode(batch, offsets, scan=scan)
     finally:
         batch.close()
     return ComposedSequences(comp, record_ids, owner, first, window, step, decoded)
@@ -415,16 +681,51 @@ def _parser():
     ap.add_argument('--keep_transitions', action='store_true', help="Do not fit the transition probabilities")
     ap.add_argument('--scan', type=int, nargs='?', const=True, default=None, metavar='N',
                     help="Work on records of at least N windows in parallel by the tile scan (without N: %d)" % SCAN_FROM)
+    ap.add_argument('--per_record', action='store_true',
+                    help="Fit one chain per record (state numbers are then a record's own; not with --scan)")
     ap.add_argument('-pf', '--positive_features', default=None, help="Count file of the positive reference (labels the states)")
     ap.add_argument('-nf', '--negative_features', default=None, help="Count file of the negative reference")
     return ap
 
 
+def _write_record_files(directory, result, phage_score):
+    """compose_profiles.csv and compose_trace.csv with a leading record_id column, and compose_records.csv, of a
+    ``ComposedSequences`` whose composition is a ``Compositions`` (one group per record)."""
+    comps = result.composition
+    S, D = comps.n_states, comps.n_columns
+    n_windows = np.bincount(result.owner, minlength=len(comps))
+    with open(os.path.join(directory, "compose_profiles.csv"), 'w') as f:
+        f.write("record_id,state,occupancy,self_transition,mean_region," + ("phage_score," if phage_score is not None else "")
+                + ",".join("p%d" % j for j in range(D)) + "\n")
+        for g, comp in enumerate(comps):
+            if comp is None:
+                continue
+            for s in range(S):
+                stay = float(comp.trans[s, s])
+                f.write("%s,%d,%r,%r,%r,%s%s\n" % (result.record_ids[g], s, float(comp.occupancy[s]), stay,
+                                                   result.step / (1.0 - stay),
+                                                   ("%r," % float(phage_score[g][s])) if phage_score is not None else "",
+                                                   ",".join(repr(float(v)) for v in np.exp(comp.log_profiles[s]))))
+    with open(os.path.join(directory, "compose_trace.csv"), 'w') as f:
+        f.write("record_id,iteration," + ",".join(TRACE_COLUMNS) + "\n")
+        for g, trace in enumerate(comps.traces):
+            for i, (L, F) in enumerate(trace):
+                f.write("%s,%d,%r,%r\n" % (result.record_ids[g], i, float(L), float(F)))
+    with open(os.path.join(directory, "compose_records.csv"), 'w') as f:
+        f.write("record_id,n_windows,status,n_iter,converged,log_evidence,bic\n")
+        for g in range(len(comps)):
+            f.write("%s,%d,%d,%d,%d,%r,%r\n" % (result.record_ids[g], int(n_windows[g]), int(comps.status[g]),
+                                                int(comps.n_iter[g]), int(comps.converged[g]), float(result.log_evidence[g]),
+                                                float(comps.bic[g])))
+
+
 def write_files(directory, result, phage_score=None):
-    """compose_windows.csv, compose_segments.csv, compose_profiles.csv and compose_trace.csv of a ``ComposedSequences``."""
+    """compose_windows.csv, compose_segments.csv, compose_profiles.csv and compose_trace.csv of a ``ComposedSequences``; for
+    one fitted per record (``segment_sequences(per_record=True)``) the last two gain a leading record_id column and
+    compose_records.csv is written beside them."""
     os.makedirs(directory, exist_ok=True)
     comp = result.composition
-    S, D = comp.log_profiles.shape
+    S, D = (comp.n_states, comp.n_columns) if isinstance(comp, Compositions) else comp.log_profiles.shape
     with open(os.path.join(directory, "compose_windows.csv"), 'w') as f:
         f.write("record_id,start,state," + ",".join("posterior%d" % s for s in range(S)) + "\n")
         for i in range(len(result)):
@@ -434,6 +735,8 @@ def write_files(directory, result, phage_score=None):
         f.write("record_id,start,end,state,n_windows,mean_posterior\n")
         for rid, a, b, s, nw, mp in result.regions():
             f.write("%s,%d,%d,%d,%d,%r\n" % (rid, a, b, s, nw, mp))
+    if isinstance(comp, Compositions):
+        return _write_record_files(directory, result, phage_score)
     with open(os.path.join(directory, "compose_profiles.csv"), 'w') as f:
         f.write("state,occupancy,self_transition,mean_region," + ("phage_score," if phage_score is not None else "")
                 + ",".join("p%d" % j for j in range(D)) + "\n")
@@ -458,8 +761,10 @@ def main(argv=None):
         options["temper"] = args.temper
     if args.scan is not None and args.scan is not True and args.scan < 1:
         raise SystemExit("--scan takes a number of windows >= 1")
+    if args.per_record and args.scan is not None:
+        raise SystemExit("--per_record does not go with --scan")
     result = segment_sequences(args.input_file, args.states, args.window, args.step, args.kmer_length, args.both_strands,
-                               args.scan, **options)
+                               args.scan, args.per_record, **options)
     score = None
     if args.positive_features is not None:
         from . import fileIO

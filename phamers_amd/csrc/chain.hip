@@ -28,6 +28,8 @@
 //                              vectors alike
 // The records of at least scan_from windows (phk_chain_set_scan; 0: none) are passed over by the four per-record kernels and
 // take the tile scan, the phk_chain_scan_* kernels further down.
+// The recurrences of a record and the emission epilogue are the bodies of chain_body.h: the phk_chain_group_* kernels further
+// down call the same bodies with the parameters of the record's group (phk_chain_set_groups).
 // The integer sums: |q| <= 2^31 and |qlog| <= 2^31 (checked), so a path over n <= 2^30 windows stays inside 2^62.
 // The float sums stay away from 0 / 0 as long as the ratio of two entries of a row or column of A stays inside the format
 // (entries of 1e-12 are tested): the largest entry of a rescaled vector is in [1/2, 1) and the state of the largest emission
@@ -35,11 +37,11 @@
 #include <algorithm>
 #include <cmath>
 
-#include "mixture_body.h"
+#include <vector>
+
+#include "chain_body.h"
 
 #define CH_BLOCKS_MAX 1024      // 64-lane workgroups per launch of the per-record kernels
-#define CH_CLAMP 32768.0
-#define CH_LN2 0.693147180559945309417232121458
 #define CH_KP MIX_CT            // row stride of the spread gamma
 #define CH_QMAX (1ll << 31)
 #define CH_NMAX (1ull << 30)
@@ -51,24 +53,11 @@ __global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_chain_emit_kernel(const 
                                                                         const double *__restrict__ L, uint32_t S, uint64_t D,
                                                                         double temper, double *__restrict__ E,
                                                                         double *__restrict__ M) {
-    const int li = threadIdx.x & 15, wave = threadIdx.x >> 6;
+    const int wave = threadIdx.x >> 6;
     const uint64_t q0 = (uint64_t)blockIdx.x * GT_QB + (uint64_t)wave * (GT_QT * 16);
     f64x4 acc[GT_QT][GT_RT];
     gram_tile<FULL, GT_QT, uint32_t>(C, nq, q0, L, S, 0, D, acc);   // S <= 8: the states are rows 0 .. S - 1 of row tile 0
-#pragma unroll
-    for (int a = 0; a < GT_QT; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double e = acc[a][0][r] * temper;
-            double m = (uint32_t)li < S ? e : -__builtin_inf();
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) m = fmax(m, __shfl_xor(m, o));
-            const uint64_t q = gram_query(q0, a, r);
-            if (q < nq) {
-                if ((uint32_t)li < S) E[q * S + li] = e;
-                if (li == 0) M[q] = m;
-            }
-        }
+    chain_emit_epilogue(acc, q0, nq, S, temper, E, M);
 }
 
 __global__ __launch_bounds__(256) void phk_chain_rowmax_kernel(const double *__restrict__ E, uint64_t n, uint32_t S,
@@ -82,27 +71,6 @@ __global__ __launch_bounds__(256) void phk_chain_rowmax_kernel(const double *__r
 
 // a record of `len` windows takes the tile scan (the per-record kernels pass over it); scan_from == 0: no record does
 __device__ __forceinline__ bool chain_scanned(uint64_t len, uint64_t scan_from) { return scan_from != 0 && len >= scan_from; }
-
-// the sum of v over the group's lanes in state order; every lane gets the same bits
-template <int SP>
-__device__ __forceinline__ double chain_sum(double v) {
-    double s = __shfl(v, 0, SP);
-#pragma unroll
-    for (int i = 1; i < SP; ++i) s += __shfl(v, i, SP);
-    return s;
-}
-
-// v / 2^e with e the exponent of the group's largest v: exact; returns e
-template <int SP>
-__device__ __forceinline__ int chain_scale2(double &v) {
-    double m = v;
-#pragma unroll
-    for (int o = 1; o < SP; o <<= 1) m = fmax(m, __shfl_xor(m, o, SP));
-    int e;
-    (void)frexp(m, &e);
-    v = ldexp(v, -e);
-    return e;
-}
 
 // par = A[S][S] then pi[S].  B[w][j] = beta_w(j) up to a power of two: beta of the record's last step is 1,
 // beta_{t-1}(i) = sum_j A_ij e_t(j) beta_t(j).
@@ -120,22 +88,7 @@ __global__ __launch_bounds__(64) void phk_chain_backward_kernel(const double *__
     for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
         const uint64_t w0 = off[r], w1 = off[r + 1];
         if (w1 == w0 || chain_scanned(w1 - w0, scan_from)) continue;
-        double b = live ? 1.0 : 0.0;
-        uint64_t w = w1 - 1;
-        double x = live ? E[w * S + j] - M[w] : 0.0;
-        for (;;) {
-            if (live) B[w * S + j] = b;
-            if (w == w0) break;
-            const double e = live ? exp(x) : 0.0;
-            --w;
-            x = live ? E[w * S + j] - M[w] : 0.0;   // the next step's load, issued ahead of this step's chain
-            const double u = e * b;
-            double nb = 0.0;
-#pragma unroll
-            for (int i = 0; i < SP; ++i) nb += arow[i] * __shfl(u, i, SP);
-            (void)chain_scale2<SP>(nb);
-            b = nb;
-        }
+        chain_backward_record<SP>(E, M, w0, w1, S, j, live, arow, B);
     }
 }
 
@@ -157,69 +110,9 @@ __global__ __launch_bounds__(64) void phk_chain_forward_kernel(const double *__r
     for (uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP; r < R; r += groups) {
         const uint64_t w0 = off[r], w1 = off[r + 1];
         if (chain_scanned(w1 - w0, scan_from)) continue;
-        double *out = V + r * Ev;
-        double xi[SP];
-#pragma unroll
-        for (int i = 0; i < SP; ++i) xi[i] = 0.0;
-        double g0 = 0.0, le = 0.0;
-        if (w1 > w0) {
-            double mw = M[w0];
-            double x = live ? E[w0 * S + j] - mw : 0.0, bw = live ? B[w0 * S + j] : 0.0;
-            double e = live ? exp(x) : 0.0;
-            double sm = mw;
-            int64_t ex = 0;
-            {
-                const double p = pj * (e * bw);
-                g0 = p / chain_sum<SP>(p);
-                if (live) G[w0 * S + j] = g0;
-            }
-            double a = pj * e;
-            ex += chain_scale2<SP>(a);
-            uint64_t w = w0 + 1;
-            if (w < w1) {
-                mw = M[w];
-                x = live ? E[w * S + j] - mw : 0.0, bw = live ? B[w * S + j] : 0.0;
-            }
-            while (w < w1) {
-                e = live ? exp(x) : 0.0;
-                const double c = e * bw;
-                sm += mw;
-                const uint64_t wn = w + 1;
-                if (wn < w1) {   // the next step's loads, issued ahead of this step's chain
-                    mw = M[wn];
-                    x = live ? E[wn * S + j] - mw : 0.0, bw = live ? B[wn * S + j] : 0.0;
-                }
-                double wv[SP], g = 0.0, col = 0.0;
-#pragma unroll
-                for (int i = 0; i < SP; ++i) {
-                    const double pr = __shfl(a, i, SP) * acol[i];
-                    g += pr;
-                    wv[i] = pr * c;
-                    col += wv[i];
-                }
-                const double inv = 1.0 / chain_sum<SP>(col);
-#pragma unroll
-                for (int i = 0; i < SP; ++i) xi[i] += wv[i] * inv;
-                if (live) G[w * S + j] = col * inv;
-                a = g * e;
-                ex += chain_scale2<SP>(a);
-                w = wn;
-            }
-            int e2;
-            const double m = frexp(chain_sum<SP>(a), &e2);
-            le = ((double)(ex + e2) * CH_LN2 + log(m)) + sm;
-        }
-        if (live) {
-#pragma unroll
-            for (int i = 0; i < SP; ++i)
-                if ((uint32_t)i < S) out[(uint32_t)i * S + j] = xi[i];
-            out[S * S + j] = g0;
-            if (j == 0) out[S * S + S] = le;
-        }
+        chain_forward_record<SP>(E, M, w0, w1, S, j, live, acol, pj, B, G, V + r * Ev);
     }
 }
-
-__device__ __forceinline__ int64_t chain_quant(double d) { return (int64_t)rint(fmax(d, -CH_CLAMP) * 65536.0); }
 
 // qpar = qlog A[S][S] then qlog pi[S].  BP[8 w + j] = the predecessor of state j at step w (w > the record's first).
 template <int SP>
@@ -242,32 +135,7 @@ __global__ __launch_bounds__(64) void phk_chain_viterbi_kernel(const double *__r
             if (j == 0) score[r] = 0, last[r] = 0;
             continue;
         }
-        long long d = qp + (live ? (long long)chain_quant(E[w0 * S + j] - M[w0]) : 0ll);
-        uint64_t w = w0 + 1;
-        double x = (live && w < w1) ? E[w * S + j] - M[w] : 0.0;
-        while (w < w1) {
-            const long long q = (long long)chain_quant(x);
-            const uint64_t wn = w + 1;
-            x = (live && wn < w1) ? E[wn * S + j] - M[wn] : 0.0;
-            long long best = __shfl(d, 0, SP) + qcol[0];
-            uint32_t k = 0;
-#pragma unroll
-            for (int i = 1; i < SP; ++i) {
-                const long long c = __shfl(d, i, SP) + qcol[i];
-                if ((uint32_t)i < S && c > best) best = c, k = (uint32_t)i;   // a tie stays with the smaller predecessor
-            }
-            d = best + q;
-            BP[8 * w + j] = (uint8_t)k;
-            w = wn;
-        }
-        long long best = __shfl(d, 0, SP);
-        uint32_t k = 0;
-#pragma unroll
-        for (int i = 1; i < SP; ++i) {
-            const long long c = __shfl(d, i, SP);
-            if ((uint32_t)i < S && c > best) best = c, k = (uint32_t)i;
-        }
-        if (j == 0) score[r] = (int64_t)best, last[r] = (uint8_t)k;
+        chain_viterbi_record<SP>(E, M, w0, w1, S, j, live, qcol, qp, BP, score, last, r);
     }
 }
 
@@ -307,6 +175,178 @@ __global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_chain_expect_kernel(cons
 __global__ __launch_bounds__(256) void phk_chain_fold_kernel(const double *__restrict__ in, uint64_t m, uint64_t Ev,
                                                              double *__restrict__ out) {
     mix_fold_body(in, m, Ev, blockIdx.x, blockIdx.y, out + (uint64_t)blockIdx.y * Ev);
+}
+
+// ---- grouped chains -------------------------------------------------------------------------------------
+// The records are cut into groups g = 0 .. G - 1 of consecutive records, each with its own log profiles, A, pi: gpar =
+// [G][S^2 + S] (A then pi), gqpar likewise, glogp = [G][S][D].  rg[r] = the group of record r, or CH_NO_GROUP for a record
+// the kernels pass over (its group is inactive or holds no window).  The matrix-pipe kernels and the fold find their work
+// in descriptor tables built per phk_chain_set_grouped for the groups at work and read at blockIdx.x (uniform addresses);
+// the per-record kernels load a record's parameters from its group one record ahead of the record they work on.
+//   phk_chain_group_emit_kernel      gram_tile + chain_emit_epilogue for the workgroup's (group, row tile of that group)
+//   phk_chain_group_backward_kernel  chain_backward_record with the record's group's A
+//   phk_chain_group_forward_kernel   chain_forward_record
+//   phk_chain_group_viterbi_kernel   chain_viterbi_record
+//   phk_chain_group_expect_kernel    mix_expect_body for the workgroup's (group, block of MIX_RB rows from the group's first
+//                                    window, column group)
+//   phk_chain_group_fold_kernel      mix_fold_body for the workgroup's (vectors of one group, 256 elements), a launch per level
+#define CH_NO_GROUP 0xffffffffu
+
+struct ChainGroup {        // one per group
+    uint64_t w0, n;        // its first window and its windows
+};
+struct ChainGroupTile {    // emit: tile = row tile of the group; expect: tile = row block of the group, y = column group
+    uint32_t group, tile, y, pad;
+    uint64_t part;         // expect: the block's partial vector among all the call's
+};
+struct ChainGroupFold {    // one workgroup of a fold level: elements 256 ex .. of the tree over vectors 256 vb .. of in
+    const double *in;
+    double *out;           // the output vector of vb
+    uint64_t m, E;
+    uint32_t ex, vb;
+};
+
+template <bool FULL>
+__global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_chain_group_emit_kernel(const uint32_t *__restrict__ C,
+                                                                              const ChainGroup *__restrict__ grp,
+                                                                              const ChainGroupTile *__restrict__ tiles,
+                                                                              const double *__restrict__ L, uint32_t S, uint64_t D,
+                                                                              double temper, double *__restrict__ E,
+                                                                              double *__restrict__ M) {
+    const ChainGroupTile t = tiles[blockIdx.x];
+    const ChainGroup g = grp[t.group];
+    const int wave = threadIdx.x >> 6;
+    const uint64_t q0 = (uint64_t)t.tile * GT_QB + (uint64_t)wave * (GT_QT * 16);
+    f64x4 acc[GT_QT][GT_RT];
+    gram_tile<FULL, GT_QT, uint32_t>(C + g.w0 * D, g.n, q0, L + (uint64_t)t.group * S * D, S, 0, D, acc);
+    chain_emit_epilogue(acc, q0, g.n, S, temper, E + g.w0 * S, M + g.w0);
+}
+
+// A[j][:] of group g into arow (zeros past S and for CH_NO_GROUP)
+template <int SP>
+__device__ __forceinline__ void chain_group_row(const double *__restrict__ par, uint32_t g, uint32_t S, uint32_t j, bool live,
+                                                double (&arow)[SP]) {
+    const double *p = par + (uint64_t)(g == CH_NO_GROUP ? 0 : g) * (S * S + S);
+    const bool ok = live && g != CH_NO_GROUP;
+#pragma unroll
+    for (int i = 0; i < SP; ++i) arow[i] = (ok && (uint32_t)i < S) ? p[j * S + i] : 0.0;
+}
+
+// A[:][j] and pi[j] of group g
+template <int SP, typename T>
+__device__ __forceinline__ void chain_group_col(const T *__restrict__ par, uint32_t g, uint32_t S, uint32_t j, bool live,
+                                                T (&acol)[SP], T &pj) {
+    const T *p = par + (uint64_t)(g == CH_NO_GROUP ? 0 : g) * (S * S + S);
+    const bool ok = live && g != CH_NO_GROUP;
+#pragma unroll
+    for (int i = 0; i < SP; ++i) acol[i] = (ok && (uint32_t)i < S) ? p[(uint32_t)i * S + j] : (T)0;
+    pj = ok ? p[S * S + j] : (T)0;
+}
+
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_group_backward_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                                      const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
+                                                                      const uint32_t *__restrict__ rg,
+                                                                      const double *__restrict__ gpar, double *__restrict__ B) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP;
+    uint32_t g = r < R ? rg[r] : CH_NO_GROUP;
+    double arow[SP];
+    chain_group_row<SP>(gpar, g, S, j, live, arow);
+    for (; r < R; r += groups) {
+        const uint64_t rn = r + groups;
+        const uint32_t gn = rn < R ? rg[rn] : CH_NO_GROUP;   // the next record's parameters, issued ahead of this record's chain
+        double an[SP];
+        chain_group_row<SP>(gpar, gn, S, j, live, an);
+        if (g != CH_NO_GROUP) {
+            const uint64_t w0 = off[r], w1 = off[r + 1];
+            if (w1 != w0) chain_backward_record<SP>(E, M, w0, w1, S, j, live, arow, B);
+        }
+        g = gn;
+#pragma unroll
+        for (int i = 0; i < SP; ++i) arow[i] = an[i];
+    }
+}
+
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_group_forward_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                                     const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
+                                                                     const uint32_t *__restrict__ rg,
+                                                                     const double *__restrict__ gpar,
+                                                                     const double *__restrict__ B, double *__restrict__ G,
+                                                                     double *__restrict__ V) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    const uint64_t Ev = (uint64_t)S * S + S + 1;
+    uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP;
+    uint32_t g = r < R ? rg[r] : CH_NO_GROUP;
+    double acol[SP], pj;
+    chain_group_col<SP, double>(gpar, g, S, j, live, acol, pj);
+    for (; r < R; r += groups) {
+        const uint64_t rn = r + groups;
+        const uint32_t gn = rn < R ? rg[rn] : CH_NO_GROUP;
+        double an[SP], pn;
+        chain_group_col<SP, double>(gpar, gn, S, j, live, an, pn);
+        if (g != CH_NO_GROUP) chain_forward_record<SP>(E, M, off[r], off[r + 1], S, j, live, acol, pj, B, G, V + r * Ev);
+        g = gn, pj = pn;
+#pragma unroll
+        for (int i = 0; i < SP; ++i) acol[i] = an[i];
+    }
+}
+
+template <int SP>
+__global__ __launch_bounds__(64) void phk_chain_group_viterbi_kernel(const double *__restrict__ E, const double *__restrict__ M,
+                                                                     const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
+                                                                     const uint32_t *__restrict__ rg,
+                                                                     const int64_t *__restrict__ gqpar, uint8_t *__restrict__ BP,
+                                                                     int64_t *__restrict__ score, uint8_t *__restrict__ last) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP;
+    uint32_t g = r < R ? rg[r] : CH_NO_GROUP;
+    long long qcol[SP], qp;
+    chain_group_col<SP, long long>((const long long *)gqpar, g, S, j, live, qcol, qp);
+    for (; r < R; r += groups) {
+        const uint64_t rn = r + groups;
+        const uint32_t gn = rn < R ? rg[rn] : CH_NO_GROUP;
+        long long qn[SP], qpn;
+        chain_group_col<SP, long long>((const long long *)gqpar, gn, S, j, live, qn, qpn);
+        if (g != CH_NO_GROUP) {
+            const uint64_t w0 = off[r], w1 = off[r + 1];
+            if (w1 == w0) {
+                if (j == 0) score[r] = 0, last[r] = 0;
+            } else {
+                chain_viterbi_record<SP>(E, M, w0, w1, S, j, live, qcol, qp, BP, score, last, r);
+            }
+        }
+        g = gn, qp = qpn;
+#pragma unroll
+        for (int i = 0; i < SP; ++i) qcol[i] = qn[i];
+    }
+}
+
+// Rx holds the spread gamma of the windows wa .. of the batch; a group's rows start at window w0 (before wa for a group cut
+// over several batches: the body reads the block's rows only, which the batch holds)
+template <bool VEC>
+__global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_chain_group_expect_kernel(const double *__restrict__ Rx, uint64_t wa,
+                                                                                const uint32_t *__restrict__ C, uint64_t D,
+                                                                                const ChainGroup *__restrict__ grp,
+                                                                                const ChainGroupTile *__restrict__ tiles,
+                                                                                const double *__restrict__ M, uint32_t S,
+                                                                                uint64_t Em, double *__restrict__ part) {
+    const ChainGroupTile t = tiles[blockIdx.x];
+    const ChainGroup g = grp[t.group];
+    const double *R0 = Rx + ((int64_t)g.w0 - (int64_t)wa) * (int64_t)CH_KP;
+    mix_expect_body<VEC>(R0, CH_KP, C + g.w0 * D, D, g.n, M + g.w0, S, t.tile, t.y, 0, part + t.part * Em);
+}
+
+__global__ __launch_bounds__(256) void phk_chain_group_fold_kernel(const ChainGroupFold *__restrict__ folds) {
+    const ChainGroupFold f = folds[blockIdx.x];
+    mix_fold_body(f.in, f.m, f.E, f.ex, f.vb, f.out);
 }
 
 extern "C" uint64_t phk_chain_grid_pass(void) { return (uint64_t)CH_BLOCKS_MAX * 32; }
@@ -725,6 +765,17 @@ struct phk_chain {
     uint64_t scan_from = 0, ns = 0, nt = 0;
     std::vector<uint64_t> h_off;           // the offsets on the host: the tile tables are built from them
     PhkDevMem s_ti, s_sr, s_st, s_F, s_FE, s_Vq, s_SM, s_AI, s_BO, s_DI, s_XI, s_MP, s_END;
+    uint64_t scan_asked = 0;               // the threshold as the caller gave it (grouped mode refuses any but 0)
+    // grouped mode (phk_chain_set_groups): G groups of consecutive records; 0 = one set of parameters for every record
+    uint64_t NG = 0;
+    std::vector<uint64_t> g_off;           // [G + 1] over the records
+    std::vector<uint8_t> g_work;           // per group: at work in the calls after the last phk_chain_set_grouped
+    bool g_tables = false;                 // the descriptor tables below are those of g_work
+    struct Batch { uint64_t wa, nb, d0, d1; };                    // windows wa .. wa + nb - 1, expect descriptors d0 .. d1 - 1
+    std::vector<Batch> g_batches;
+    std::vector<std::pair<uint64_t, uint64_t>> g_levels_v, g_levels_t;   // fold descriptors [first, last) level by level
+    uint64_t g_ntiles = 0;
+    PhkDevMem g_rg, g_grp, g_par, g_qpar, g_logp, g_part, g_resT, g_resV, g_fold, g_tiles, g_etiles, g_folds;
 };
 
 static unsigned chain_grid(uint64_t items, uint64_t per_block, uint64_t cap) {
@@ -886,11 +937,12 @@ static int chain_scan_alloc(phk_ctx *ctx, phk_chain *c, const std::vector<uint32
 extern "C" int phk_chain_set_scan(phk_ctx *ctx, phk_chain *c, uint64_t scan_from) {
     PHK_ENTER(ctx, "phk_chain_set_scan");
     PHK_REQUIRE(c, "phk_chain_set_scan: NULL chain");
+    PHK_REQUIRE(!(c->NG && scan_from), "phk_chain_set_scan: a grouped chain does not take the tile scan");
     PHK_HIP(hipStreamSynchronize(ctx->stream));   // the buffers of an earlier threshold may be in use
     PhkDevMem *mem[] = {&c->s_ti, &c->s_sr, &c->s_st, &c->s_F, &c->s_FE, &c->s_Vq, &c->s_SM,
                         &c->s_AI, &c->s_BO, &c->s_DI, &c->s_XI, &c->s_MP, &c->s_END};
     for (PhkDevMem *m : mem) m->release();
-    c->scan_from = 0, c->ns = 0, c->nt = 0;
+    c->scan_from = 0, c->ns = 0, c->nt = 0, c->scan_asked = scan_from;
     if (scan_from == 0 || c->n == 0) return PHK_OK;
     std::vector<uint32_t> ti;
     std::vector<uint64_t> sr, st;
@@ -906,6 +958,7 @@ extern "C" int phk_chain_set_scan(phk_ctx *ctx, phk_chain *c, uint64_t scan_from
     const int rc = chain_scan_alloc(ctx, c, ti, sr, st);
     if (rc != PHK_OK) {
         for (PhkDevMem *m : mem) m->release();
+        c->scan_asked = 0;
         return rc;
     }
     c->scan_from = scan_from, c->ns = sr.size(), c->nt = ti.size();
@@ -934,6 +987,7 @@ extern "C" int phk_chain_set(phk_ctx *ctx, phk_chain *c, const double *log_profi
                              const double *init, const int64_t *qlog_trans, const int64_t *qlog_init, double temper) {
     PHK_ENTER(ctx, "phk_chain_set");
     PHK_REQUIRE(c, "phk_chain_set: NULL chain");
+    PHK_REQUIRE(!c->NG, "phk_chain_set: a grouped chain takes its parameters from phk_chain_set_grouped");
     PHK_REQUIRE(trans && init && qlog_trans && qlog_init, "phk_chain_set: NULL parameters");
     const uint32_t S = c->S;
     for (uint32_t i = 0; i < S * S; ++i)
@@ -980,12 +1034,19 @@ extern "C" int phk_chain_set(phk_ctx *ctx, phk_chain *c, const double *log_profi
     return rc;
 }
 
+static int chain_group_forward_backward(phk_ctx *ctx, const phk_chain *c);
+static int chain_group_viterbi(phk_ctx *ctx, const phk_chain *c);
+template <typename T>
+static void chain_group_zero(const phk_chain *c, T *x, uint64_t per, T *y);
+
 extern "C" int phk_chain_emissions(phk_ctx *ctx, const phk_chain *c, double *E) {
     PHK_ENTER(ctx, "phk_chain_emissions");
     PHK_REQUIRE(c && c->ready, "phk_chain_emissions: no chain, or phk_chain_set has not succeeded on it");
     if (c->n == 0) return PHK_OK;
     PHK_REQUIRE(E, "phk_chain_emissions: NULL pointer");
-    return phk_copy_to_host(ctx, E, c->E.ptr, c->n * c->S * 8);
+    PHK_TRY(phk_copy_to_host(ctx, E, c->E.ptr, c->n * c->S * 8));
+    if (c->NG) chain_group_zero<double>(c, E, c->S, nullptr);   // a group that is not at work has no emissions
+    return PHK_OK;
 }
 
 #define CHAIN_BY_SP(S, CALL)  \
@@ -1153,6 +1214,7 @@ extern "C" int phk_chain_expect(phk_ctx *ctx, const phk_chain *c, double *T, dou
                                 double *log_evidence, double *log_evidence_rec) {
     PHK_ENTER(ctx, "phk_chain_expect");
     PHK_REQUIRE(c && c->ready, "phk_chain_expect: no chain, or phk_chain_set has not succeeded on it");
+    PHK_REQUIRE(!c->NG, "phk_chain_expect: a grouped chain gives its expectations through phk_chain_expect_grouped");
     PHK_REQUIRE(xi && gamma0 && log_evidence, "phk_chain_expect: NULL pointer");
     PHK_REQUIRE(!T == !Ns, "phk_chain_expect: T and Ns go together");
     PHK_REQUIRE(!T || c->from_counts, "phk_chain_expect: a chain made from emissions has no T");
@@ -1173,16 +1235,21 @@ static int chain_decode_run(phk_ctx *ctx, const phk_chain *c, uint8_t *state, do
                             int64_t *path_score) {
     const uint64_t S = c->S, R = c->R, n = c->n, Ev = S * S + S + 1;
     const uint64_t *off = c->off.as<uint64_t>(), sf = c->scan_from;
-    if (sf) PHK_TRY(chain_scan_tiles(ctx, c));
-    if (posterior || log_evidence_rec) PHK_TRY(chain_forward_backward(ctx, c));
-    if (sf) PHK_TRY(chain_scan_path(ctx, c));
+    if (c->NG) {   // every record with its group's parameters; the trace needs none
+        if (posterior || log_evidence_rec) PHK_TRY(chain_group_forward_backward(ctx, c));
+        PHK_TRY(chain_group_viterbi(ctx, c));
+    } else {
+        if (sf) PHK_TRY(chain_scan_tiles(ctx, c));
+        if (posterior || log_evidence_rec) PHK_TRY(chain_forward_backward(ctx, c));
+        if (sf) PHK_TRY(chain_scan_path(ctx, c));
 #define CH_VIT(SP)                                                                                                        \
-    PHK_LAUNCH(ctx, "phk_chain_viterbi_kernel",                                                                           \
-               phk_chain_viterbi_kernel<SP><<<dim3(chain_grid(R, 64 / SP, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(   \
-                   c->E.as<double>(), c->M.as<double>(), off, R, c->S, c->qpar.as<int64_t>(), c->BP.as<uint8_t>(),        \
-                   c->score.as<int64_t>(), c->last.as<uint8_t>(), sf))
-    CHAIN_BY_SP(c->S, CH_VIT);
+        PHK_LAUNCH(ctx, "phk_chain_viterbi_kernel",                                                                           \
+                   phk_chain_viterbi_kernel<SP><<<dim3(chain_grid(R, 64 / SP, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(   \
+                       c->E.as<double>(), c->M.as<double>(), off, R, c->S, c->qpar.as<int64_t>(), c->BP.as<uint8_t>(),        \
+                       c->score.as<int64_t>(), c->last.as<uint8_t>(), sf))
+        CHAIN_BY_SP(c->S, CH_VIT);
 #undef CH_VIT
+    }
     PHK_LAUNCH(ctx, "phk_chain_trace_kernel",
                phk_chain_trace_kernel<<<dim3(chain_grid(R, 64, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(
                    off, R, c->last.as<uint8_t>(), c->BP.as<uint64_t>(), c->state.as<uint8_t>(), sf));
@@ -1193,6 +1260,12 @@ static int chain_decode_run(phk_ctx *ctx, const phk_chain *c, uint8_t *state, do
         std::vector<double> rec(R * Ev);
         PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
         for (uint64_t r = 0; r < R; ++r) log_evidence_rec[r] = rec[r * Ev + S * S + S];
+    }
+    if (c->NG) {   // zeros for the groups that are not at work
+        chain_group_zero<uint8_t>(c, state, 1, nullptr);
+        if (posterior) chain_group_zero<double>(c, posterior, S, nullptr);
+        if (log_evidence_rec) chain_group_zero<double>(c, nullptr, 0, log_evidence_rec);
+        if (path_score) chain_group_zero<int64_t>(c, nullptr, 0, path_score);
     }
     return PHK_OK;
 }
@@ -1210,6 +1283,373 @@ extern "C" int phk_chain_decode(phk_ctx *ctx, const phk_chain *c, uint8_t *state
     }
     PHK_REQUIRE(state, "phk_chain_decode: NULL state");
     const int rc = chain_decode_run(ctx, c, state, posterior, log_evidence_rec, path_score);
+    if (rc != PHK_OK) (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
+// ---- grouped chains: the host half ----------------------------------------------------------------------
+static void chain_group_release(phk_chain *c) {
+    PhkDevMem *mem[] = {&c->g_rg, &c->g_grp, &c->g_par, &c->g_qpar, &c->g_logp, &c->g_part, &c->g_resT, &c->g_resV,
+                        &c->g_fold, &c->g_tiles, &c->g_etiles, &c->g_folds};
+    for (PhkDevMem *m : mem) m->release();
+    c->NG = 0, c->g_tables = false, c->g_ntiles = 0;
+    c->g_off.clear(), c->g_work.clear(), c->g_batches.clear(), c->g_levels_v.clear(), c->g_levels_t.clear();
+}
+
+// the windows [w0, w1) of group g
+static inline void chain_group_span(const phk_chain *c, uint64_t g, uint64_t &w0, uint64_t &w1) {
+    const uint64_t r0 = c->g_off[g], r1 = c->g_off[g + 1];
+    w0 = c->R ? c->h_off[r0] : 0, w1 = c->R ? c->h_off[r1] : 0;
+}
+
+extern "C" int phk_chain_set_groups(phk_ctx *ctx, phk_chain *c, const uint64_t *group_offsets, uint64_t G) {
+    const char *who = "phk_chain_set_groups";
+    PHK_ENTER(ctx, "phk_chain_set_groups");
+    PHK_REQUIRE(c, "%s: NULL chain", who);
+    if (G == 0) {
+        PHK_REQUIRE(!group_offsets, "%s: offsets and no group", who);
+        if (!c->NG) return PHK_OK;
+        PHK_HIP(hipStreamSynchronize(ctx->stream));
+        chain_group_release(c);
+        c->ready = false;   // (the parameters of the calls that follow come from phk_chain_set)
+        return PHK_OK;
+    }
+    PHK_REQUIRE(c->from_counts, "%s: a chain made from emissions has no groups", who);
+    PHK_REQUIRE(c->scan_asked == 0, "%s: the tile scan is on (phk_chain_set_scan): grouped chains do not take it", who);
+    PHK_REQUIRE(group_offsets, "%s: NULL offsets", who);
+    PHK_REQUIRE(G < CH_NO_GROUP, "%s: 2^32 - 1 groups or more", who);
+    PHK_REQUIRE(group_offsets[0] == 0 && group_offsets[G] == c->R, "%s: the group offsets do not run from 0 to the %llu records",
+                who, (unsigned long long)c->R);
+    for (uint64_t g = 0; g < G; ++g)
+        PHK_REQUIRE(group_offsets[g] <= group_offsets[g + 1], "%s: the group offsets decrease at group %llu", who,
+                    (unsigned long long)g);
+    PHK_HIP(hipStreamSynchronize(ctx->stream));   // the buffers of earlier groups may be in use
+    chain_group_release(c);
+    c->ready = false;
+    c->g_off.assign(group_offsets, group_offsets + G + 1);
+    c->NG = G;
+    const uint64_t S = c->S, D = c->D, PS = S * S + S, Ev = PS + 1, Em = S * D + S + 1;
+    // every group at work at once: its blocks' partial vectors, and two fold buffers per tree that has a second level
+    std::vector<ChainGroup> grp(G);
+    uint64_t blocks = 0, fold = 0;
+    for (uint64_t g = 0; g < G; ++g) {
+        uint64_t w0, w1;
+        chain_group_span(c, g, w0, w1);
+        grp[g] = ChainGroup{w0, w1 - w0};
+        const uint64_t nb = phk_div_up(w1 - w0, MIX_RB), nr = c->g_off[g + 1] - c->g_off[g];
+        blocks += nb;
+        if (nb > 256) fold += 2 * phk_div_up(nb, 256) * Em;
+        if (nr > 256) fold += 2 * phk_div_up(nr, 256) * Ev;
+    }
+    auto body = [&]() -> int {
+        PHK_TRY(c->g_rg.alloc(who, "record groups", c->R * 4));
+        PHK_TRY(c->g_grp.alloc(who, "groups", G * sizeof(ChainGroup)));
+        PHK_TRY(c->g_par.alloc(who, "parameters", G * PS * 8));
+        PHK_TRY(c->g_qpar.alloc(who, "parameters", G * PS * 8));
+        PHK_TRY(c->g_logp.alloc(who, "log profiles", G * S * D * 8));
+        PHK_TRY(c->g_part.alloc(who, "partial vectors", blocks * Em * 8));
+        PHK_TRY(c->g_resT.alloc(who, "group vectors", G * Em * 8));
+        PHK_TRY(c->g_resV.alloc(who, "group vectors", G * Ev * 8));
+        PHK_TRY(c->g_fold.alloc(who, "fold vectors", fold * 8));
+        PHK_TRY(phk_copy_to_device(ctx, c->g_grp.ptr, grp.data(), G * sizeof(ChainGroup)));
+        if (c->R) PHK_HIP(hipMemsetAsync(c->last.ptr, 0, c->R, ctx->stream));   // the trace reads it for every record
+        PHK_HIP(hipStreamSynchronize(ctx->stream));   // grp leaves scope
+        return PHK_OK;
+    };
+    const int rc = body();
+    if (rc != PHK_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        chain_group_release(c);
+    }
+    return rc;
+}
+
+// The tables of the groups at work (c->g_work): the records' groups, the emission tiles, the expectation blocks in batches
+// of at most c->B consecutive windows, the fold levels of the records' vectors and of the blocks' partial vectors.
+static int chain_group_tables(phk_ctx *ctx, phk_chain *c) {
+    const char *who = "phk_chain_set_grouped";
+    const uint64_t G = c->NG, S = c->S, D = c->D, Ev = S * S + S + 1, Em = S * D + S + 1;
+    const uint64_t ygroups = phk_div_up(D, GT_WAVES * MIX_CT), cap = c->B > c->n ? c->n : c->B;
+    std::vector<uint32_t> rg(c->R, CH_NO_GROUP);
+    std::vector<ChainGroupTile> tiles, etiles;
+    std::vector<ChainGroupFold> folds;
+    c->g_batches.clear(), c->g_levels_v.clear(), c->g_levels_t.clear();
+    struct Live { const double *in; double *res, *f[2]; uint64_t m; };
+    std::vector<Live> live_v, live_t;
+    uint64_t part_at = 0, fold_at = 0;
+    double *part = c->g_part.as<double>(), *fold = c->g_fold.as<double>();
+    for (uint64_t g = 0; g < G; ++g) {
+        if (!c->g_work[g]) continue;
+        uint64_t w0, w1;
+        chain_group_span(c, g, w0, w1);
+        const uint64_t r0 = c->g_off[g], r1 = c->g_off[g + 1], n = w1 - w0, nb = phk_div_up(n, MIX_RB);
+        std::fill(rg.begin() + r0, rg.begin() + r1, (uint32_t)g);
+        for (uint64_t t = 0; t < phk_div_up(n, GT_QB); ++t) tiles.push_back(ChainGroupTile{(uint32_t)g, (uint32_t)t, 0, 0, 0});
+        for (uint64_t b = 0; b < nb; ++b) {
+            const uint64_t a = w0 + b * MIX_RB, e = a + MIX_RB < w1 ? a + MIX_RB : w1;
+            if (c->g_batches.empty() || e - c->g_batches.back().wa > cap)
+                c->g_batches.push_back(phk_chain::Batch{a, 0, etiles.size(), etiles.size()});
+            for (uint64_t y = 0; y < ygroups; ++y)
+                etiles.push_back(ChainGroupTile{(uint32_t)g, (uint32_t)b, (uint32_t)y, 0, part_at + b});
+            c->g_batches.back().nb = e - c->g_batches.back().wa, c->g_batches.back().d1 = etiles.size();
+        }
+        Live t{part + part_at * Em, c->g_resT.as<double>() + g * Em, {nullptr, nullptr}, nb};
+        if (nb > 256) t.f[0] = fold + fold_at, t.f[1] = t.f[0] + phk_div_up(nb, 256) * Em, fold_at += 2 * phk_div_up(nb, 256) * Em;
+        live_t.push_back(t);
+        Live v{c->V.as<double>() + r0 * Ev, c->g_resV.as<double>() + g * Ev, {nullptr, nullptr}, r1 - r0};
+        if (v.m > 256) v.f[0] = fold + fold_at, v.f[1] = v.f[0] + phk_div_up(v.m, 256) * Ev, fold_at += 2 * phk_div_up(v.m, 256) * Ev;
+        live_v.push_back(v);
+        part_at += nb;
+    }
+    // a group's level reads m vectors and writes ceil(m / 256); the last one is the group's result
+    auto levels = [&](std::vector<Live> &live, uint64_t E, std::vector<std::pair<uint64_t, uint64_t>> &out) {
+        for (int level = 0; !live.empty(); ++level) {
+            const uint64_t first = folds.size();
+            std::vector<Live> next;
+            for (Live &v : live) {
+                const uint64_t blocks = phk_div_up(v.m, 256);
+                double *o = blocks == 1 ? v.res : v.f[level & 1];
+                for (uint64_t vb = 0; vb < blocks; ++vb)
+                    for (uint64_t ex = 0; ex < phk_div_up(E, 256); ++ex)
+                        folds.push_back(ChainGroupFold{v.in, o + vb * E, v.m, E, (uint32_t)ex, (uint32_t)vb});
+                if (blocks > 1) v.in = o, v.m = blocks, next.push_back(v);
+            }
+            out.push_back({first, folds.size()});
+            live.swap(next);
+        }
+    };
+    levels(live_v, Ev, c->g_levels_v);
+    levels(live_t, Em, c->g_levels_t);
+    PHK_REQUIRE(tiles.size() < (1ull << 31) && etiles.size() < (1ull << 31) && folds.size() < (1ull << 31),
+                "%s: more than 2^31 workgroups in one launch", who);
+    c->g_ntiles = tiles.size();
+    if (c->g_tiles.bytes < tiles.size() * sizeof(ChainGroupTile))
+        PHK_TRY(c->g_tiles.alloc(who, "descriptors", tiles.size() * sizeof(ChainGroupTile)));
+    if (c->g_etiles.bytes < etiles.size() * sizeof(ChainGroupTile))
+        PHK_TRY(c->g_etiles.alloc(who, "descriptors", etiles.size() * sizeof(ChainGroupTile)));
+    if (c->g_folds.bytes < folds.size() * sizeof(ChainGroupFold))
+        PHK_TRY(c->g_folds.alloc(who, "descriptors", folds.size() * sizeof(ChainGroupFold)));
+    if (c->R) PHK_TRY(phk_copy_to_device(ctx, c->g_rg.ptr, rg.data(), c->R * 4));
+    if (!tiles.empty()) PHK_TRY(phk_copy_to_device(ctx, c->g_tiles.ptr, tiles.data(), tiles.size() * sizeof(ChainGroupTile)));
+    if (!etiles.empty()) PHK_TRY(phk_copy_to_device(ctx, c->g_etiles.ptr, etiles.data(), etiles.size() * sizeof(ChainGroupTile)));
+    if (!folds.empty()) PHK_TRY(phk_copy_to_device(ctx, c->g_folds.ptr, folds.data(), folds.size() * sizeof(ChainGroupFold)));
+    PHK_HIP(hipStreamSynchronize(ctx->stream));   // the tables leave scope
+    return PHK_OK;
+}
+
+extern "C" int phk_chain_set_grouped(phk_ctx *ctx, phk_chain *c, const double *log_profiles, uint64_t D, const double *trans,
+                                     const double *init, const int64_t *qlog_trans, const int64_t *qlog_init, double temper,
+                                     const uint8_t *active) {
+    const char *who = "phk_chain_set_grouped";
+    PHK_ENTER(ctx, "phk_chain_set_grouped");
+    PHK_REQUIRE(c, "%s: NULL chain", who);
+    PHK_REQUIRE(c->NG, "%s: the chain has no groups (phk_chain_set_groups)", who);
+    PHK_REQUIRE(log_profiles && trans && init && qlog_trans && qlog_init, "%s: NULL parameters", who);
+    PHK_REQUIRE(D == c->D, "%s: the profiles have %llu columns, the count rows %llu", who, (unsigned long long)D,
+                (unsigned long long)c->D);
+    PHK_REQUIRE(temper > 0.0 && temper - temper == 0.0, "%s: temper = %g is not finite and > 0", who, temper);
+    const uint64_t G = c->NG, S = c->S, SS = S * S, PS = SS + S;
+    for (uint64_t g = 0; g < G; ++g) {
+        if (active && !active[g]) continue;
+        const double *A = trans + g * SS, *pi = init + g * S;
+        const unsigned long long gl = (unsigned long long)g;
+        for (uint32_t i = 0; i < SS; ++i)
+            PHK_REQUIRE(A[i] > 0.0 && A[i] < 1.0, "%s: group %llu: transition probability %u = %g is not in (0, 1)", who, gl, i, A[i]);
+        for (uint32_t i = 0; i < S; ++i)
+            PHK_REQUIRE(pi[i] > 0.0 && pi[i] < 1.0, "%s: group %llu: initial probability %u = %g is not in (0, 1)", who, gl, i, pi[i]);
+        for (uint32_t i = 0; i <= S; ++i) {
+            const double *row = i < S ? A + i * S : pi;
+            double sum = 0.0;
+            for (uint32_t j = 0; j < S; ++j) sum += row[j];
+            PHK_REQUIRE(fabs(sum - 1.0) <= 4.0 * 0x1p-52, "%s: group %llu: row %u of the transition matrix (row %u: the initial "
+                                                          "distribution) does not sum to 1", who, gl, i, (uint32_t)S);
+        }
+        for (uint32_t i = 0; i < PS; ++i) {
+            const int64_t q = i < SS ? qlog_trans[g * SS + i] : qlog_init[g * S + i - SS];
+            PHK_REQUIRE(q <= 0 && q >= -CH_QMAX, "%s: group %llu: quantised logarithm %u = %lld is not in [-2^31, 0]", who, gl, i,
+                        (long long)q);
+        }
+    }
+    for (uint64_t g = 0; g < G; ++g) {
+        if (active && !active[g]) continue;
+        if (!phk_rows_finite(log_profiles + g * S * D, S * D)) {
+            phk_set_error("%s: group %llu: the log profiles hold a value that is not finite (a zero profile entry?)", who,
+                          (unsigned long long)g);
+            return PHK_ERR_NAN;
+        }
+    }
+    PHK_HIP(hipStreamSynchronize(ctx->stream));
+    c->ready = false;
+    // the groups at work: active and with a window; their parameters packed as the kernels read them (the others' stay
+    // unread: zeros go up in their place)
+    std::vector<uint8_t> work(G);
+    std::vector<double> par(G * PS, 0.0), logp;
+    std::vector<int64_t> qpar(G * PS, 0);
+    bool all = true;
+    for (uint64_t g = 0; g < G; ++g) {
+        uint64_t w0, w1;
+        chain_group_span(c, g, w0, w1);
+        work[g] = (!active || active[g]) && w1 > w0;
+        all = all && work[g];
+        if (!work[g]) continue;
+        std::copy(trans + g * SS, trans + (g + 1) * SS, par.begin() + g * PS);
+        std::copy(init + g * S, init + (g + 1) * S, par.begin() + g * PS + SS);
+        std::copy(qlog_trans + g * SS, qlog_trans + (g + 1) * SS, qpar.begin() + g * PS);
+        std::copy(qlog_init + g * S, qlog_init + (g + 1) * S, qpar.begin() + g * PS + SS);
+    }
+    const double *lp = log_profiles;
+    if (!all) {
+        logp.assign(G * S * D, 0.0);
+        for (uint64_t g = 0; g < G; ++g)
+            if (work[g]) std::copy(log_profiles + g * S * D, log_profiles + (g + 1) * S * D, logp.begin() + g * S * D);
+        lp = logp.data();
+    }
+    auto body = [&]() -> int {
+        if (!c->g_tables || work != c->g_work) {
+            c->g_tables = false;
+            c->g_work = work;
+            PHK_TRY(chain_group_tables(ctx, c));
+            c->g_tables = true;
+        }
+        PHK_TRY(phk_copy_to_device(ctx, c->g_par.ptr, par.data(), G * PS * 8));
+        PHK_TRY(phk_copy_to_device(ctx, c->g_qpar.ptr, qpar.data(), G * PS * 8));
+        PHK_TRY(phk_copy_to_device(ctx, c->g_logp.ptr, lp, G * S * D * 8));
+        if (c->g_ntiles) {
+            const dim3 grid((unsigned)c->g_ntiles), blk(GT_WAVES * 64);
+            if (D % GT_KC == 0) {
+                PHK_LAUNCH(ctx, "phk_chain_group_emit_kernel",
+                           phk_chain_group_emit_kernel<true><<<grid, blk, 0, ctx->stream>>>(
+                               c->counts, c->g_grp.as<ChainGroup>(), c->g_tiles.as<ChainGroupTile>(), c->g_logp.as<double>(),
+                               c->S, D, temper, c->E.as<double>(), c->M.as<double>()));
+            } else {
+                PHK_LAUNCH(ctx, "phk_chain_group_emit_kernel",
+                           phk_chain_group_emit_kernel<false><<<grid, blk, 0, ctx->stream>>>(
+                               c->counts, c->g_grp.as<ChainGroup>(), c->g_tiles.as<ChainGroupTile>(), c->g_logp.as<double>(),
+                               c->S, D, temper, c->E.as<double>(), c->M.as<double>()));
+            }
+        }
+        return PHK_OK;
+    };
+    int rc = body();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PHK_OK) {   // the packed parameters leave scope
+        phk_set_error("%s: the stream failed", who);
+        rc = PHK_ERR_HIP;
+    }
+    c->ready = rc == PHK_OK;
+    return rc;
+}
+
+// backward then forward over the records of the groups at work
+static int chain_group_forward_backward(phk_ctx *ctx, const phk_chain *c) {
+    const double *E = c->E.as<double>(), *M = c->M.as<double>(), *par = c->g_par.as<double>();
+    const uint64_t *off = c->off.as<uint64_t>();
+    const uint32_t *rg = c->g_rg.as<uint32_t>();
+#define CH_GFB(SP)                                                                                                            \
+    {                                                                                                                         \
+        const dim3 grid(chain_grid(c->R, 64 / SP, CH_BLOCKS_MAX));                                                            \
+        PHK_LAUNCH(ctx, "phk_chain_group_backward_kernel", phk_chain_group_backward_kernel<SP><<<grid, dim3(64), 0, ctx->stream>>>( \
+                                                               E, M, off, c->R, c->S, rg, par, c->Bt.as<double>()));          \
+        PHK_LAUNCH(ctx, "phk_chain_group_forward_kernel",                                                                     \
+                   phk_chain_group_forward_kernel<SP><<<grid, dim3(64), 0, ctx->stream>>>(                                    \
+                       E, M, off, c->R, c->S, rg, par, c->Bt.as<double>(), c->G.as<double>(), c->V.as<double>()));            \
+    }
+    CHAIN_BY_SP(c->S, CH_GFB);
+#undef CH_GFB
+    return PHK_OK;
+}
+
+static int chain_group_viterbi(phk_ctx *ctx, const phk_chain *c) {
+#define CH_GVIT(SP)                                                                                                           \
+    PHK_LAUNCH(ctx, "phk_chain_group_viterbi_kernel",                                                                         \
+               phk_chain_group_viterbi_kernel<SP><<<dim3(chain_grid(c->R, 64 / SP, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>( \
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->R, c->S, c->g_rg.as<uint32_t>(),           \
+                   c->g_qpar.as<int64_t>(), c->BP.as<uint8_t>(), c->score.as<int64_t>(), c->last.as<uint8_t>()))
+    CHAIN_BY_SP(c->S, CH_GVIT);
+#undef CH_GVIT
+    return PHK_OK;
+}
+
+static int chain_group_fold(phk_ctx *ctx, const phk_chain *c, const std::vector<std::pair<uint64_t, uint64_t>> &levels) {
+    for (const auto &lv : levels) {
+        if (lv.second == lv.first) continue;
+        PHK_LAUNCH(ctx, "phk_chain_group_fold_kernel",
+                   phk_chain_group_fold_kernel<<<dim3((unsigned)(lv.second - lv.first)), dim3(256), 0, ctx->stream>>>(
+                       c->g_folds.as<ChainGroupFold>() + lv.first));
+    }
+    return PHK_OK;
+}
+
+// zeros over the windows (x: per window, `per` elements each) or records (per == 0: y, one element each) of the groups
+// that are not at work
+template <typename T>
+static void chain_group_zero(const phk_chain *c, T *x, uint64_t per, T *y) {
+    for (uint64_t g = 0; g < c->NG; ++g) {
+        if (c->g_work[g]) continue;
+        uint64_t w0, w1;
+        chain_group_span(c, g, w0, w1);
+        if (x) std::fill(x + w0 * per, x + w1 * per, (T)0);
+        if (y) std::fill(y + c->g_off[g], y + c->g_off[g + 1], (T)0);
+    }
+}
+
+static int chain_group_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, double *Ns, double *xi, double *gamma0,
+                                  double *log_evidence, double *log_evidence_rec) {
+    const uint64_t S = c->S, D = c->D, R = c->R, G = c->NG, SS = S * S, Ev = SS + S + 1, Em = S * D + S + 1;
+    PHK_TRY(chain_group_forward_backward(ctx, c));
+    PHK_TRY(chain_group_fold(ctx, c, c->g_levels_v));
+    const bool vec = D % 4 == 0;
+    for (const phk_chain::Batch &b : c->g_batches) {
+        PHK_LAUNCH(ctx, "phk_chain_spread_kernel",
+                   phk_chain_spread_kernel<<<dim3(chain_grid(b.nb * CH_KP, 256, 4096)), dim3(256), 0, ctx->stream>>>(
+                       c->G.as<double>() + b.wa * S, b.nb, (uint32_t)S, c->Rx.as<double>()));
+        const dim3 grid((unsigned)(b.d1 - b.d0)), blk(GT_WAVES * 64);
+        const ChainGroupTile *tiles = c->g_etiles.as<ChainGroupTile>() + b.d0;
+        if (vec) {
+            PHK_LAUNCH(ctx, "phk_chain_group_expect_kernel",
+                       phk_chain_group_expect_kernel<true><<<grid, blk, 0, ctx->stream>>>(
+                           c->Rx.as<double>(), b.wa, c->counts, D, c->g_grp.as<ChainGroup>(), tiles, c->M.as<double>(),
+                           (uint32_t)S, Em, c->g_part.as<double>()));
+        } else {
+            PHK_LAUNCH(ctx, "phk_chain_group_expect_kernel",
+                       phk_chain_group_expect_kernel<false><<<grid, blk, 0, ctx->stream>>>(
+                           c->Rx.as<double>(), b.wa, c->counts, D, c->g_grp.as<ChainGroup>(), tiles, c->M.as<double>(),
+                           (uint32_t)S, Em, c->g_part.as<double>()));
+        }
+    }
+    PHK_TRY(chain_group_fold(ctx, c, c->g_levels_t));
+    std::vector<double> v(G * Ev), t(G * Em);
+    PHK_TRY(phk_copy_to_host(ctx, v.data(), c->g_resV.ptr, G * Ev * 8));
+    PHK_TRY(phk_copy_to_host(ctx, t.data(), c->g_resT.ptr, G * Em * 8));
+    for (uint64_t g = 0; g < G; ++g) {
+        if (!c->g_work[g]) {
+            std::fill(xi + g * SS, xi + (g + 1) * SS, 0.0), std::fill(gamma0 + g * S, gamma0 + (g + 1) * S, 0.0);
+            std::fill(T + g * S * D, T + (g + 1) * S * D, 0.0), std::fill(Ns + g * S, Ns + (g + 1) * S, 0.0);
+            log_evidence[g] = 0.0;
+            continue;
+        }
+        const double *pv = v.data() + g * Ev, *pt = t.data() + g * Em;
+        std::copy(pv, pv + SS, xi + g * SS), std::copy(pv + SS, pv + SS + S, gamma0 + g * S);
+        log_evidence[g] = pv[SS + S];
+        std::copy(pt, pt + S * D, T + g * S * D), std::copy(pt + S * D, pt + S * D + S, Ns + g * S);
+    }
+    if (log_evidence_rec) {
+        std::vector<double> rec(R * Ev);
+        PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
+        for (uint64_t r = 0; r < R; ++r) log_evidence_rec[r] = rec[r * Ev + SS + S];
+        chain_group_zero<double>(c, nullptr, 0, log_evidence_rec);
+    }
+    return PHK_OK;
+}
+
+extern "C" int phk_chain_expect_grouped(phk_ctx *ctx, const phk_chain *c, double *T, double *Ns, double *xi, double *gamma0,
+                                        double *log_evidence, double *log_evidence_rec) {
+    const char *who = "phk_chain_expect_grouped";
+    PHK_ENTER(ctx, "phk_chain_expect_grouped");
+    PHK_REQUIRE(c, "%s: NULL chain", who);
+    PHK_REQUIRE(c->NG, "%s: the chain has no groups (phk_chain_set_groups)", who);
+    PHK_REQUIRE(c->ready, "%s: phk_chain_set_grouped has not succeeded on the chain", who);
+    PHK_REQUIRE(T && Ns && xi && gamma0 && log_evidence, "%s: NULL pointer", who);
+    const int rc = chain_group_expect_run(ctx, c, T, Ns, xi, gamma0, log_evidence, log_evidence_rec);
     if (rc != PHK_OK) (void)hipStreamSynchronize(ctx->stream);
     return rc;
 }
