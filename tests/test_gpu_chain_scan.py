@@ -4,7 +4,9 @@ xi / gamma_0 / T / N_s inside the bounds of tests/chain_scan_ref.py of the longd
 emissions, a record below the threshold untouched inside a mixed call, a scanned record's bits independent of the call
 around it, of the threshold, of batch_rows and of the entry point, more tiles than one launch covers, exact ties at tile
 edges, extremes across tile edges, errors, the fit and the command line.  Shapes: records of 1, 2, T - 1, 0, T, T + 1, 2 T,
-2 T + 1, 3 T + 5, 1 and 1000 windows in one call (T = phk_chain_tile()), S = 2, 3, 5, 8, D = 256 and 30."""
+2 T + 1, 3 T + 5, 1 and 1000 windows in one call (T = phk_chain_tile()), S = 2 .. 8 at D = 256 and S = 3, 4, 8 at D = 30;
+more tiles than one launch at every padded width (S = 2, 4, 5).  More scanned records than one carry launch and every tile
+count around the carry's look-ahead are tests/test_gpu_chain_shapes.py's."""
 import csv
 import os
 
@@ -18,7 +20,7 @@ pytestmark = pytest.mark.gpu
 LD = cref.LD
 T = sref.TILE
 LENGTHS = [1, 2, T - 1, 0, T, T + 1, 2 * T, 2 * T + 1, 3 * T + 5, 1, 1000]
-KEYS = [(S, 256) for S in base.STATES] + [(3, 30), (8, 30)]
+KEYS = base.KEYS
 PATH = ("state", "score")
 ALL = ("E", "T", "Ns", "xi", "gamma0", "L", "L_rec", "state", "posterior", "le", "score")
 
@@ -150,7 +152,7 @@ def test_same_bits_from_host_rows_a_resident_batch_and_any_batch_rows(cases, S):
         assert np.array_equal(em[k], c["on"][k]), k
 
 
-@pytest.mark.parametrize("S", [2, 5])
+@pytest.mark.parametrize("S", [2, 4, 5])
 def test_more_tiles_than_one_launch_covers(S):
     from phamers_amd import _lib
     n_long = int(_lib.load().phk_chain_scan_grid_pass()) * T + 3 * T + 1

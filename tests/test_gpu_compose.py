@@ -4,8 +4,9 @@ splits, the Viterbi path bit for bit the integer recurrence on the device's own 
 counts within the derived bounds of the sequential longdouble statement, independence of a record from the rest of the
 call, exact ties, extremes, error codes, the fit and the command line on the "small" sequence.  Shapes are the smallest that
 reach each path: records of 1, 2, 63, 64, 65, 129 and 1000 windows with an empty and a one-window record among them (1325
-rows: two reduction blocks of 1024, eleven emission tiles of 128), S = 2, 3, 5, 8 (every padded width, with and without
-padding), D = 256 and a D that is no multiple of 4."""
+rows: two reduction blocks of 1024, eleven emission tiles of 128), S = 2 .. 8 (every state count: the padded widths 2, 4 and
+8 full, and with one, two and three padded lanes), D = 256 and a D that is no multiple of 4 (S = 3, 4 and 8).  The shapes
+past these -- launches, tile counts, fold levels, column groups -- are tests/test_gpu_chain_shapes.py's."""
 import csv
 import os
 
@@ -17,7 +18,7 @@ from tests import compose_ref as cref, helpers
 pytestmark = pytest.mark.gpu
 LD = cref.LD
 LENGTHS = [1, 2, 63, 0, 64, 65, 129, 1, 1000]
-STATES = [2, 3, 5, 8]
+STATES = [2, 3, 4, 5, 6, 7, 8]
 
 
 def chain_parameters(rng, S, stay=0.9):
@@ -74,14 +75,14 @@ def same(a, b, keys=("E", "T", "Ns", "xi", "gamma0", "L", "L_rec", "state", "pos
 @pytest.fixture(scope="module")
 def cases():
     out = {(S, 256): make_case(S, 256) for S in STATES}
-    out[(3, 30)] = make_case(3, 30)
-    out[(8, 30)] = make_case(8, 30)
+    for S in (3, 4, 8):
+        out[(S, 30)] = make_case(S, 30)
     for c in out.values():
         c["got"] = run(c)
     return out
 
 
-KEYS = [(S, 256) for S in STATES] + [(3, 30), (8, 30)]
+KEYS = [(S, 256) for S in STATES] + [(3, 30), (4, 30), (8, 30)]
 
 
 @pytest.mark.parametrize("key", KEYS)
@@ -185,7 +186,7 @@ def test_a_record_alone_gives_the_bits_it_gives_inside_a_shuffled_call(cases, S)
         assert got["le"][r] == alone["le"][0] and got["score"][r] == alone["score"][0]
 
 
-@pytest.mark.parametrize("S,extra", [(2, 300), (5, 900)])
+@pytest.mark.parametrize("S,extra", [(2, 300), (4, 600), (5, 900)])
 def test_more_records_than_one_launch_covers(S, extra):
     from phamers_amd import _lib
     pad = 2 if S <= 2 else (4 if S <= 4 else 8)

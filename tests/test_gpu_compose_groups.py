@@ -4,7 +4,9 @@ the Viterbi path against the integer recurrence and the float results against th
 active mask, the order of the groups, more groups than one launch covers, the mode's errors, and ``compose.fit_groups``
 against ``compose.fit`` per scaffold.  Shapes: the records of tests/test_gpu_compose.py and one more, cut into a one-window
 group, a group without records, a group holding an empty record, two-record groups and a last group of 1090 windows that
-crosses a reduction block and starts at a window that is no multiple of 128."""
+crosses a reduction block and starts at a window that is no multiple of 128; S = 2 .. 8 at D = 256, S = 3 and 8 at D = 30;
+more groups than one launch at every padded width (S = 2, 4, 5).  Fold levels past the first, the tables of one chain under
+changing masks and more than one column group are tests/test_gpu_chain_shapes.py's."""
 import csv
 import os
 
@@ -19,7 +21,7 @@ pytestmark = pytest.mark.gpu
 LD = cref.LD
 LENGTHS = [1, 2, 63, 0, 64, 65, 129, 1, 1000, 90]
 GROUPS = np.array([0, 1, 1, 4, 5, 7, 8, 10], dtype=np.uint64)
-KEYS = [(2, 256), (3, 256), (5, 256), (8, 256), (3, 30), (8, 30)]
+KEYS = [(2, 256), (3, 256), (4, 256), (5, 256), (6, 256), (7, 256), (8, 256), (3, 30), (8, 30)]
 OUTPUTS = ("E", "T", "Ns", "xi", "gamma0", "L", "L_rec", "state", "posterior", "le", "score")
 
 
@@ -199,10 +201,10 @@ def test_the_order_of_the_groups_does_not_matter(cases, key):
             assert differing(group_part(moved, got, i), c["alone"][g]) == [], (order.tolist(), g)
 
 
-@pytest.mark.parametrize("S", [2, 5])
+@pytest.mark.parametrize("S", [2, 4, 5])
 def test_more_groups_than_one_launch_covers(S):
     from phamers_amd import _lib
-    D, pad = 30, 2 if S <= 2 else 8
+    D, pad = 30, 2 if S <= 2 else (4 if S <= 4 else 8)
     G = int(_lib.load().phk_chain_grid_pass()) + 300
     edge = int(_lib.load().phk_chain_grid_pass()) * 2 // pad           # the first record past one launch at this width
     base = group_case(S, D, lengths=[2] * 7, groups=np.arange(8))
