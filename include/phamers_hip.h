@@ -710,6 +710,34 @@ int phk_chain_set_grouped(phk_ctx *ctx, phk_chain *chain, const double *log_prof
 int phk_chain_expect_grouped(phk_ctx *ctx, const phk_chain *chain, double *T, double *Ns, double *xi, double *gamma0,
                              double *log_evidence, double *log_evidence_rec);
 
+/* Segment boundaries refined to the base.  The sequences are n_seq records of a packed stream
+ * (bases, seq_offsets[n_seq + 1] as phk_count_ascii takes them); the k-mer starting at base i of a sequence of L bases is
+ * valid when i + k <= L and its k bases are symbols -- the rule of the count kernels; it never runs into the next sequence --
+ * and code(i) is its column in a count row.  qtable[n_rows][D], D = 4^k, int64 with |q| <= 2^31 (segment.quantise of log
+ * profiles: units of 2^-PHK_SEG_QUANT_BITS nat).  Boundary b = (seq, lo, x, hi, left_row, right_row) with
+ * 0 <= lo <= x <= hi <= L_seq and hi - lo <= 2^30:
+ *     d(i) = q[left_row][code(i)] - q[right_row][code(i)] for a valid k-mer, 0 otherwise
+ *     P(p) = sum_{lo <= i < p} d(i)                       p = lo .. hi
+ *     position[b]    = the p that maximises P; ties to the smallest |p - x|, then to the smallest p
+ *     evidence[b][0] = P(position) - P(x)    the gain over the window boundary
+ *     evidence[b][1] = P(position) - P(lo)   evidence[b][2] = P(position) - P(hi)
+ *     support[b]     = the valid k-mers starting in [lo, hi)
+ * All integer, exact, inside 2^63; a boundary's result is a function of its own sequence's bases in [lo, hi + k - 1), its two
+ * rows, lo, x and hi alone: not of the other boundaries, their order or number, the launch or the run.  The bases go up once
+ * and are packed by the packer of the count path; _fasta takes a parsed file's records.  PHK_ERR_ARG, before any launch: D not
+ * 4^k, a row or sequence index out of range, lo > x, x > hi, hi > L_seq, hi - lo > 2^30, |q| > 2^31, a NULL where B > 0.
+ * B == 0 is PHK_OK with nothing launched.  phk_refine_grid_pass(): the most boundaries one launch covers in one pass of its
+ * grid (further ones by grid stride; for the tests). */
+int phk_refine_boundaries_ascii(phk_ctx *ctx, const char *bases, const uint64_t *seq_offsets, uint64_t n_seq, int k,
+                                const char *symbols4, const int64_t *qtable, uint64_t n_rows, uint64_t D, const uint64_t *seq,
+                                const uint64_t *lo, const uint64_t *x, const uint64_t *hi, const uint32_t *left_row,
+                                const uint32_t *right_row, uint64_t B, int64_t *position, int64_t *evidence, uint32_t *support);
+int phk_refine_boundaries_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const char *symbols4, const int64_t *qtable,
+                                uint64_t n_rows, uint64_t D, const uint64_t *seq, const uint64_t *lo, const uint64_t *x,
+                                const uint64_t *hi, const uint32_t *left_row, const uint32_t *right_row, uint64_t B,
+                                int64_t *position, int64_t *evidence, uint32_t *support);
+uint64_t phk_refine_grid_pass(void);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

@@ -141,6 +141,11 @@ SIGNATURES = {
     "phk_chain_set_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
                                       c_void_p]),
     "phk_chain_expect_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "phk_refine_boundaries_ascii": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_char_p, c_void_p, c_u64, c_u64, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p]),
+    "phk_refine_boundaries_fasta": (c_int, [c_void_p, c_void_p, c_int, c_char_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p]),
+    "phk_refine_grid_pass": (c_u64, []),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1652,6 +1657,42 @@ class Batch(_Resident):
         idx, dist = _neighbor_outputs(self.n, k)
         return _neighbor_result(self.ctx.lib.phk_batch_neighbors(self.ctx.handle, model.handle, self.handle, int(k), ptr(idx),
                                                                  ptr(dist)), idx, dist)
+
+
+def refine_grid_pass():
+    """Boundaries one launch of the refinement kernel covers in one pass of its grid (phk_refine_grid_pass)."""
+    return int(load().phk_refine_grid_pass())
+
+
+def refine_boundaries(ctx, source, kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row):
+    """(position (B,) int64, evidence (B, 3) int64, support (B,) uint32) of phk_refine_boundaries_fasta (``source`` a
+    ``Fasta``) or phk_refine_boundaries_ascii (a list of strings).  The arrays are converted, not checked: the library
+    refuses what it does not take (ValueError for its PHK_ERR_ARG)."""
+    q = np.ascontiguousarray(qtable, dtype=np.int64)
+    if q.ndim != 2:
+        raise ValueError("refine_boundaries: the table must be (n_rows, D)")
+    u64 = lambda v: np.ascontiguousarray(v, dtype=np.uint64).ravel()
+    u32 = lambda v: np.ascontiguousarray(v, dtype=np.uint32).ravel()
+    seq, lo, x, hi, left_row, right_row = u64(seq), u64(lo), u64(x), u64(hi), u32(left_row), u32(right_row)
+    B = seq.shape[0]
+    if not all(a.shape[0] == B for a in (lo, x, hi, left_row, right_row)):
+        raise ValueError("refine_boundaries: seq, lo, x, hi, left_row and right_row must have one entry per boundary")
+    position, evidence = np.zeros(B, dtype=np.int64), np.zeros((B, 3), dtype=np.int64)
+    support = np.zeros(B, dtype=np.uint32)
+    tail = (ptr(q), q.shape[0], q.shape[1], ptr(seq), ptr(lo), ptr(x), ptr(hi), ptr(left_row), ptr(right_row), B, ptr(position),
+            ptr(evidence), ptr(support))
+    if isinstance(source, Fasta):
+        rc = ctx.lib.phk_refine_boundaries_fasta(ctx.handle, source.handle, int(kmer_length), symbols, *tail)
+    else:
+        raw = [s.encode("latin-1", "replace") for s in source]
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        if raw:
+            offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
+        rc = ctx.lib.phk_refine_boundaries_ascii(ctx.handle, ptr(np.ascontiguousarray(bases)), ptr(offsets), len(raw),
+                                                 int(kmer_length), symbols, *tail)
+    check_value(rc, nan=False)
+    return position, evidence, support
 
 
 class Fasta(object):

@@ -32,7 +32,10 @@ Two findings of the CPU study this module was built after:
                                                                 a Compositions: one fit per group of consecutive records,
                                                                 all groups in one device call per iteration (section 4.28)
     load_groups(path)                                           a Compositions saved with Compositions.save
-    python -m phamers_amd.compose -in FASTA -out DIR -S n [--scan [N]] [--per_record]
+    boundary_plan(state, owner, start, window, step, span)      the intervals around the region boundaries of a decode;
+                                                                ComposedSequences.refine / refined_regions: the boundaries
+                                                                to the base (section 4.29; refine.py)
+    python -m phamers_amd.compose -in FASTA -out DIR -S n [--scan [N]] [--per_record] [--refine [SPAN]]
 """
 import collections
 import os
@@ -597,18 +600,128 @@ def fit_groups(counts_or_batch, owner_or_offsets, group_offsets, n_states, mean_
     return Compositions(items, status, S, D, t, a)
 
 
+# ---- boundaries finer than a window ---------------------------------------------------------------
+BoundaryPlan = collections.namedtuple("BoundaryPlan", "record x lo hi left_state right_state first_window")
+BoundaryPlan.__doc__ = """One entry per pair of adjacent runs of a record, in window order, all (B,) int64: the record, the
+window boundary x, the interval lo .. hi in bases of the record, the two runs' states and the index of the right run's
+first window."""
+
+Boundaries = collections.namedtuple("Boundaries", "record record_id window_boundary position left_state right_state gain "
+                                                  "left_evidence right_evidence support evidence_q")
+Boundaries.__doc__ = """What ``ComposedSequences.refine`` fills, one entry per boundary: the record (index and id), the window
+boundary x, the refined position, the two states, gain / left_evidence / right_evidence in nats (float64) -- ``evidence_q``
+(B, 3) int64 holds the same three in units of 2^-16 nat, exact -- and the support (valid k-mers of the interval)."""
+
+
+def _runs(state, owner):
+    """(first, last) window index of every run of consecutive windows of one record in one state."""
+    joined = (state[1:] == state[:-1]) & (owner[1:] == owner[:-1])
+    return np.flatnonzero(np.concatenate(([True], ~joined))), np.flatnonzero(np.concatenate((~joined, [True])))
+
+
+def boundary_plan(state, owner, start, window, step, span=None):
+    """The intervals in which the boundaries of a decode are looked for: one per pair of adjacent runs A = windows a0 .. a1,
+    B = windows b0 .. b1 of one record (runs of different records are never joined).  With integer division throughout:
+
+        x         = (start[a1] + window + start[b0]) // 2        the window boundary (start[b0] when window = step)
+        left_mid  = (start[a0] + start[a1] + window) // 2        the middle of run A; right_mid likewise of run B
+        lo        = min(x, max(x - span, left_mid + 1))
+        hi        = max(x, min(x + span, right_mid))
+
+    ``span`` defaults to ``window``.  The middle of a run is at least the hi of the boundary before it and below the lo of
+    the one after it, so the intervals of a record are disjoint and, whatever position is chosen inside them, the refined
+    positions of a record increase strictly: no refined region is empty or out of order.  (This needs
+    (window + step) // 2 > window // 2, that is step >= 2 or an odd window; with step = 1 and an even window the two
+    intervals around a run of a single window share their end point.)  The formulas read the window starts; ``step`` is
+    only checked.  A ``BoundaryPlan``.  NumPy on the host."""
+    state, owner = np.asarray(state).astype(np.int64).reshape(-1), np.asarray(owner).astype(np.int64).reshape(-1)
+    start = np.asarray(start).astype(np.int64).reshape(-1)
+    window, step = int(window), int(step)
+    if window < 1 or step < 1:
+        raise ValueError("window and step must be >= 1")
+    span = window if span is None else int(span)
+    if span < 0:
+        raise ValueError("span must be >= 0, got %r" % (span,))
+    if not len(state) == len(owner) == len(start):
+        raise ValueError("state, owner and start must have one entry per window")
+    empty = np.zeros(0, dtype=np.int64)
+    if len(state) == 0:
+        return BoundaryPlan(*([empty] * 7))
+    first, last = _runs(state, owner)
+    pair = np.flatnonzero(owner[first[:-1]] == owner[first[1:]])
+    a0, a1, b0, b1 = first[pair], last[pair], first[pair + 1], last[pair + 1]
+    x = (start[a1] + window + start[b0]) // 2
+    left_mid = (start[a0] + start[a1] + window) // 2
+    right_mid = (start[b0] + start[b1] + window) // 2
+    lo = np.minimum(x, np.maximum(x - span, left_mid + 1))
+    hi = np.maximum(x, np.minimum(x + span, right_mid))
+    return BoundaryPlan(owner[a0], x, lo, hi, state[a0], state[b0], b0)
+
+
+def _span(refine):
+    """``refine`` of ``segment_sequences``: False / None = no, True = the default span (None), an int >= 0 = that span."""
+    if isinstance(refine, (bool, np.bool_)) or refine is None:
+        return bool(refine), None
+    if isinstance(refine, (int, np.integer)) and int(refine) >= 0:
+        return True, int(refine)
+    raise ValueError("refine must be a bool or a span in bases >= 0, got %r" % (refine,))
+
+
 class ComposedSequences(object):
     """What ``segment_sequences`` returns: ``composition``; the windows' ``record_ids``, ``owner``, ``start``, ``window``,
-    ``step``; ``state`` (n,), ``posterior`` (n, S); ``log_evidence`` and ``path_score`` per record."""
+    ``step``; ``state`` (n,), ``posterior`` (n, S); ``log_evidence`` and ``path_score`` per record; ``boundaries``: None until
+    ``refine`` has run, then a ``Boundaries``."""
 
     def __init__(self, composition, record_ids, owner, start, window, step, decoded):
         self.composition, self.record_ids, self.owner, self.start = composition, list(record_ids), owner, start
         self.window, self.step = int(window), int(step)
         self.state, self.posterior = decoded.state, decoded.posterior
         self.log_evidence, self.path_score = decoded.log_evidence, decoded.path_score
+        self.boundaries = None
 
     def __len__(self):
         return self.state.shape[0]
+
+    def refine(self, fasta_or_sequences, span=None):
+        """Refines every boundary between two runs of a record from the window grid to the base (``refine.boundaries`` on
+        the intervals of ``boundary_plan``; ``span``: bases searched on either side of a window boundary at most, default
+        ``window``) and fills ``self.boundaries``.  ``fasta_or_sequences`` is the input the windows were counted from.  The
+        two states' profiles are row s of a ``Composition``'s ``log_profiles``, or row g S + s of a ``Compositions``' for
+        record g (one group per record, as ``segment_sequences(per_record=True)`` fits them); a record whose group was not
+        fitted is one run of state 0 and has no boundary.  A composition fitted with ``both_strands`` has folded
+        (strand-symmetric) profiles; they are used as they are, with the forward strand's k-mers.  Returns ``self``."""
+        from . import refine as _refine
+        comp = self.composition
+        grouped = isinstance(comp, Compositions)
+        D = comp.n_columns if grouped else comp.log_profiles.shape[1]
+        k = int(round(np.log(D) / np.log(4)))
+        plan = boundary_plan(self.state, self.owner, self.start, self.window, self.step, span)
+        S = comp.n_states
+        if grouped:
+            table = np.where(np.isnan(comp.log_profiles), 0.0, comp.log_profiles).reshape(-1, D)
+            left, right = plan.record * S + plan.left_state, plan.record * S + plan.right_state
+        else:
+            table, left, right = comp.log_profiles, plan.left_state, plan.right_state
+        r = _refine.boundaries(fasta_or_sequences, k, table, plan.record, plan.lo, plan.x, plan.hi, left, right)
+        self.boundaries = Boundaries(plan.record, [self.record_ids[int(g)] for g in plan.record], plan.x, r.position,
+                                     plan.left_state, plan.right_state, r.gain_nats, r.left_evidence_nats, r.right_evidence_nats,
+                                     r.support, np.stack([r.gain, r.left_evidence, r.right_evidence], axis=1).reshape(-1, 3))
+        return self
+
+    def refined_regions(self):
+        """``regions()`` with the start and the end of every region that borders another region of its record replaced by
+        the refined position of that boundary; a record's first start and last end stay.  ValueError before ``refine``."""
+        if self.boundaries is None:
+            raise ValueError("refined_regions needs the boundaries: call refine(fasta_or_sequences) first")
+        regions = [list(r) for r in self.regions()]
+        if regions:
+            first, _ = _runs(self.state, self.owner)
+            pair = np.flatnonzero(self.owner[first[:-1]] == self.owner[first[1:]])
+            if len(pair) != len(self.boundaries.position):
+                raise ValueError("the boundaries do not belong to this decode")
+            for r, p in zip(pair, self.boundaries.position):
+                regions[int(r)][2] = regions[int(r) + 1][1] = int(p)
+        return [tuple(r) for r in regions]
 
     def regions(self):
         """Per run of consecutive windows of one record in one state: ``(record id, start of the first window, start of the
@@ -624,7 +737,7 @@ class ComposedSequences(object):
 
 
 def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_length=4, both_strands=False, scan=None,
-                      per_record=False, **fit_options):
+                      per_record=False, refine=False, **fit_options):
     """Counts the windows of a FASTA file (or a list of strings) as one resident batch, fits ``n_states`` compositions to
     them and decodes: a ``ComposedSequences``.  ``temper`` defaults to ``segment.default_temper(window, step, k)``; the other
     ``fit_options`` are ``fit``'s (``step`` is passed on); ``scan`` goes to the fit and to the decode.  ValueError when no
@@ -634,9 +747,13 @@ def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_l
     then stands out against its own scaffold, not against the other organisms of an assembly); ``composition`` is then
     the ``Compositions``.  State numbers are then NOT comparable between records -- state 1 of one record and state 1 of
     another are unrelated; ``Compositions.label`` scores every (record, state) against two references, which is.  A record
-    too short for ``n_states`` is not fitted (state 0, NaN posteriors).  ``per_record`` does not go with ``scan``."""
+    too short for ``n_states`` is not fitted (state 0, NaN posteriors).  ``per_record`` does not go with ``scan``.
+
+    ``refine``: True, or a span in bases, refines the region boundaries to the base before returning
+    (``ComposedSequences.refine`` with this call's input); False leaves ``boundaries`` None."""
     from . import kmer
     scan = _scan(scan)
+    refine, span = _span(refine)
     if per_record and scan:
         raise ValueError("per_record does not go with the tile scan (scan=)")
     both_strands = kmer._check_strands(kmer.DNA, both_strands)
@@ -658,7 +775,8 @@ def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_l
             decoded = comp.decode(batch, offsets, scan=scan)
     finally:
         batch.close()
-    return ComposedSequences(comp, record_ids, owner, first, window, step, decoded)
+    result = ComposedSequences(comp, record_ids, owner, first, window, step, decoded)
+    return result.refine(fasta_or_sequences, span) if refine else result
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------
@@ -683,6 +801,9 @@ def _parser():
                     help="Work on records of at least N windows in parallel by the tile scan (without N: %d)" % SCAN_FROM)
     ap.add_argument('--per_record', action='store_true',
                     help="Fit one chain per record (state numbers are then a record's own; not with --scan)")
+    ap.add_argument('--refine', type=int, nargs='?', const=True, default=None, metavar='SPAN',
+                    help="Refine the region boundaries to the base, searching SPAN bases on either side of a window boundary "
+                         "(without SPAN: the window); writes compose_boundaries.csv and compose_segments_refined.csv")
     ap.add_argument('-pf', '--positive_features', default=None, help="Count file of the positive reference (labels the states)")
     ap.add_argument('-nf', '--negative_features', default=None, help="Count file of the negative reference")
     return ap
@@ -719,10 +840,29 @@ def _write_record_files(directory, result, phage_score):
                                                 float(comps.bic[g])))
 
 
+def write_refined_files(directory, result):
+    """compose_boundaries.csv (one line per refined boundary; gain and evidences in nats) and compose_segments_refined.csv
+    (compose_segments.csv's columns, of ``refined_regions``) of a ``ComposedSequences`` whose ``refine`` has run."""
+    os.makedirs(directory, exist_ok=True)
+    b = result.boundaries
+    if b is None:
+        raise ValueError("write_refined_files needs the boundaries: call refine(fasta_or_sequences) first")
+    with open(os.path.join(directory, "compose_boundaries.csv"), 'w') as f:
+        f.write("record_id,window_boundary,position,left_state,right_state,gain,left_evidence,right_evidence,support\n")
+        for i in range(len(b.position)):
+            f.write("%s,%d,%d,%d,%d,%r,%r,%r,%d\n" % (b.record_id[i], int(b.window_boundary[i]), int(b.position[i]),
+                                                     int(b.left_state[i]), int(b.right_state[i]), float(b.gain[i]),
+                                                     float(b.left_evidence[i]), float(b.right_evidence[i]), int(b.support[i])))
+    with open(os.path.join(directory, "compose_segments_refined.csv"), 'w') as f:
+        f.write("record_id,start,end,state,n_windows,mean_posterior\n")
+        for rid, a, e, s, nw, mp in result.refined_regions():
+            f.write("%s,%d,%d,%d,%d,%r\n" % (rid, a, e, s, nw, mp))
+
+
 def write_files(directory, result, phage_score=None):
     """compose_windows.csv, compose_segments.csv, compose_profiles.csv and compose_trace.csv of a ``ComposedSequences``; for
     one fitted per record (``segment_sequences(per_record=True)``) the last two gain a leading record_id column and
-    compose_records.csv is written beside them."""
+    compose_records.csv is written beside them.  (The two files of ``--refine``: ``write_refined_files``.)"""
     os.makedirs(directory, exist_ok=True)
     comp = result.composition
     S, D = (comp.n_states, comp.n_columns) if isinstance(comp, Compositions) else comp.log_profiles.shape
@@ -763,6 +903,8 @@ def main(argv=None):
         raise SystemExit("--scan takes a number of windows >= 1")
     if args.per_record and args.scan is not None:
         raise SystemExit("--per_record does not go with --scan")
+    if args.refine is not None and args.refine is not True and args.refine < 0:
+        raise SystemExit("--refine takes a span in bases >= 0")
     result = segment_sequences(args.input_file, args.states, args.window, args.step, args.kmer_length, args.both_strands,
                                args.scan, args.per_record, **options)
     score = None
@@ -772,6 +914,9 @@ def main(argv=None):
         neg = fileIO.read_feature_file(args.negative_features, normalize=False)[1]
         score = result.composition.label(pos, neg)
     write_files(args.output_directory, result, score)
+    if args.refine is not None:
+        result.refine(args.input_file, None if args.refine is True else args.refine)
+        write_refined_files(args.output_directory, result)
     return result
 
 

@@ -1,0 +1,92 @@
+"""
+refine.py -- segment boundaries refined from the window grid to the base (this project's own).
+
+``compose`` decodes windows, so every region it reports ends on the window grid.  The fitted states hold what a finer answer
+needs: a profile log theta_s over the 4^k k-mers.  Around a boundary between a run of state a and a run of state b the best
+change point is the prefix maximum of the per-base log ratio
+
+    d(i) = q_a[kmer_i] - q_b[kmer_i]        q = segment.quantise(log theta): int64, units of 2^-16 nat
+    P(p) = sum_{lo <= i < p} d(i)           the k-mer starting at i belongs to the left segment exactly when i < p
+    p*   = arg max_{lo <= p <= hi} P(p)     ties: the smallest |p - x|, then the smallest p (x = the window boundary)
+
+one pass over the bases, a prefix sum and an arg-max, all in exact integers on the device (refine.hip): the result does not
+depend on the order of the reduction.  A k-mer with a base outside the alphabet, or running past its sequence's end, counts
+0 -- the rule by which the windows were counted.  The log profiles go in untempered: tempering scales every row alike and
+does not move an arg-max.
+
+    boundaries(fasta_or_sequences, kmer_length, log_profiles, seq, lo, x, hi, left_row, right_row)     a Refined
+
+``compose.boundary_plan`` makes the intervals from a decode; ``ComposedSequences.refine`` puts the two together.
+"""
+import collections
+
+import numpy as np
+
+from . import _lib
+from .segment import QUANT_BITS, quantise
+
+MAX_SPAN = 1 << 30
+
+Refined = collections.namedtuple("Refined", "position gain left_evidence right_evidence support gain_nats left_evidence_nats "
+                                            "right_evidence_nats")
+Refined.__doc__ = """position (B,) int64: the refined change point in bases of the sequence; gain = P(position) - P(x),
+left_evidence = P(position) - P(lo), right_evidence = P(position) - P(hi): (B,) int64 >= 0 in units of 2^-16 nat, and the
+same as float64 nats (``*_nats``); support (B,) int64: the valid k-mers starting in [lo, hi)."""
+
+
+def _refine(fasta_or_sequences, kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row):
+    """(position, evidence (B, 3), support) from the device (the tests put the statement in its place)."""
+    ctx = _lib.get_context()
+    if isinstance(fasta_or_sequences, str):
+        fasta = _lib.Fasta(fasta_or_sequences)
+        try:
+            return _lib.refine_boundaries(ctx, fasta, kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row)
+        finally:
+            fasta.close()
+    return _lib.refine_boundaries(ctx, list(fasta_or_sequences), kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row)
+
+
+def _indices(v, name):
+    a = np.asarray(v)
+    if a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+        raise ValueError("%s must be a 1-D integer array" % name)
+    a = a.astype(np.int64)
+    if a.size and a.min() < 0:
+        raise ValueError("%s must not be negative" % name)
+    return a
+
+
+def boundaries(fasta_or_sequences, kmer_length, log_profiles, seq, lo, x, hi, left_row, right_row, symbols=None):
+    """Boundary b lies in sequence ``seq[b]`` (the index of a record of the FASTA file, or of a string of the list), between
+    a segment whose k-mers follow row ``left_row[b]`` of ``log_profiles`` (n_rows, 4^k) and one that follows row
+    ``right_row[b]``; the window grid put it at base ``x[b]``, and it is looked for in ``lo[b] .. hi[b]``
+    (0 <= lo <= x <= hi <= the sequence's length, hi - lo <= 2^30).  The profiles are quantised by ``segment.quantise`` (no
+    logarithm is taken here or on the device).  A ``Refined``; a boundary without evidence stays at x.  ValueError for what
+    the library refuses."""
+    from . import kmer
+    symbols = kmer.DNA if symbols is None else symbols
+    sym = kmer._check_symbols(symbols)
+    k = int(kmer_length)
+    if not 1 <= k <= _lib.MAX_K:
+        raise ValueError("kmer_length must be 1 to %d, got %r" % (_lib.MAX_K, kmer_length))
+    logp = np.asarray(log_profiles, dtype=np.float64)
+    if logp.ndim != 2 or logp.shape[1] != 4 ** k:
+        raise ValueError("log_profiles must be (n_rows, %d) for k = %d" % (4 ** k, k))
+    if np.isnan(logp).any():
+        raise ValueError("log_profiles must not hold NaN")
+    seq, lo, x, hi = _indices(seq, "seq"), _indices(lo, "lo"), _indices(x, "x"), _indices(hi, "hi")
+    left_row, right_row = _indices(left_row, "left_row"), _indices(right_row, "right_row")
+    B = len(seq)
+    if not all(len(a) == B for a in (lo, x, hi, left_row, right_row)):
+        raise ValueError("seq, lo, x, hi, left_row and right_row must have one entry per boundary")
+    if B and (max(left_row.max(), right_row.max()) >= logp.shape[0]):
+        raise ValueError("a row index is outside the %d rows of log_profiles" % logp.shape[0])
+    if ((lo > x) | (x > hi)).any():
+        raise ValueError("every boundary needs lo <= x <= hi")
+    if (hi - lo > MAX_SPAN).any():
+        raise ValueError("an interval of more than 2^30 bases")
+    position, evidence, support = _refine(fasta_or_sequences, k, sym, quantise(logp), seq, lo, x, hi, left_row, right_row)
+    evidence = np.asarray(evidence, dtype=np.int64).reshape(B, 3)
+    nats = evidence.astype(np.float64) * 2.0 ** -QUANT_BITS
+    return Refined(np.asarray(position, dtype=np.int64), evidence[:, 0].copy(), evidence[:, 1].copy(), evidence[:, 2].copy(),
+                   np.asarray(support).astype(np.int64), nats[:, 0].copy(), nats[:, 1].copy(), nats[:, 2].copy())
