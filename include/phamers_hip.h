@@ -738,6 +738,31 @@ int phk_refine_boundaries_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const c
                                 int64_t *position, int64_t *evidence, uint32_t *support);
 uint64_t phk_refine_grid_pass(void);
 
+/* Boundary confidence: phk_refine_boundaries_* with a second kernel behind the first, which reads
+ * P* = P(position) and the position from the first one's device outputs and walks the prefix sums again.  position, evidence
+ * and support are the bits phk_refine_boundaries_* gives.  With drop_q >= 0 in units of 2^-16 nat, per boundary:
+ *     interval[b][0] = lower    the smallest p in [lo, hi] with P(p) >= P* - drop_q (in bases of the sequence)
+ *     interval[b][1] = upper    the largest such p          interval[b][2] = n_within, their number (they need not be contiguous)
+ *     w(p) = exp(-(P* - P(p)) 2^-16), and w(p) = 0 exactly where P* - P(p) > 700 * 2^16 (an integer comparison)
+ *     sums[b][0] = Z = sum_p w(p)                 sums[b][1] = M = sum of w(p) over lower <= p <= upper
+ *     sums[b][2] = sum_{p < position} (position - p) w(p)        sums[b][3] = sum_{p > position} (p - position) w(p)
+ *     sums[b][4] = sum_p (p - position)^2 w(p)
+ * lower <= position <= upper, n_within >= 1 and Z >= 1 always; an empty interval gives (lo, lo, 1) and (1, 1, 0, 0, 0).  The
+ * interval is exact.  The sums are float64, each weight one exp of an exact argument, added in an order that lo and hi alone
+ * fix (the candidate lo; then per 1024 candidates: 16 in order per lane, the lanes by a butterfly, the total onto the running
+ * sum): a boundary's eight numbers are the same bits whatever else the call holds and wherever its sequence lies in the
+ * stream.  No logarithm, division or root is taken.  The errors of phk_refine_boundaries_*, and PHK_ERR_ARG for drop_q < 0 or a
+ * NULL interval / sums where B > 0, before any launch. */
+int phk_refine_confidence_ascii(phk_ctx *ctx, const char *bases, const uint64_t *seq_offsets, uint64_t n_seq, int k,
+                                const char *symbols4, const int64_t *qtable, uint64_t n_rows, uint64_t D, const uint64_t *seq,
+                                const uint64_t *lo, const uint64_t *x, const uint64_t *hi, const uint32_t *left_row,
+                                const uint32_t *right_row, uint64_t B, int64_t drop_q, int64_t *position, int64_t *evidence,
+                                uint32_t *support, int64_t *interval, double *sums);
+int phk_refine_confidence_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const char *symbols4, const int64_t *qtable,
+                                uint64_t n_rows, uint64_t D, const uint64_t *seq, const uint64_t *lo, const uint64_t *x,
+                                const uint64_t *hi, const uint32_t *left_row, const uint32_t *right_row, uint64_t B, int64_t drop_q,
+                                int64_t *position, int64_t *evidence, uint32_t *support, int64_t *interval, double *sums);
+
 /* Nearest-reference lookup: the k nearest rows of X[M][D] for every row of Q[N][D], what sorting a row of
  * learning.distances (scripts/learning.py:47-66) gives and what learning.knn (scripts/learning.py:118-128) folds into a
  * vote.  With d2(q, j) the direct-difference squared distance accumulated by fma in column order (the value phk_distances

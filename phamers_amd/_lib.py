@@ -146,6 +146,12 @@ SIGNATURES = {
     "phk_refine_boundaries_fasta": (c_int, [c_void_p, c_void_p, c_int, c_char_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_void_p]),
     "phk_refine_grid_pass": (c_u64, []),
+    "phk_refine_confidence_ascii": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_char_p, c_void_p, c_u64, c_u64, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_u64, ctypes.c_int64, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
+    "phk_refine_confidence_fasta": (c_int, [c_void_p, c_void_p, c_int, c_char_p, c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_u64, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
     "phk_neighbors": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_u64, c_u64, c_int, c_u64, c_void_p, c_void_p]),
     "phk_model_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_u64, c_int, c_void_p, c_void_p]),
     "phk_batch_neighbors": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -1668,31 +1674,52 @@ def refine_boundaries(ctx, source, kmer_length, symbols, qtable, seq, lo, x, hi,
     """(position (B,) int64, evidence (B, 3) int64, support (B,) uint32) of phk_refine_boundaries_fasta (``source`` a
     ``Fasta``) or phk_refine_boundaries_ascii (a list of strings).  The arrays are converted, not checked: the library
     refuses what it does not take (ValueError for its PHK_ERR_ARG)."""
+    return _refine_call("refine_boundaries", ctx, source, kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row, None)
+
+
+def refine_confidence(ctx, source, kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row, drop_q):
+    """``refine_boundaries``' three arrays, then interval (B, 3) int64 = (lower, upper, n_within) and sums (B, 5) float64 =
+    (Z, M, S1_left, S1_right, S2) of phk_refine_confidence_fasta / _ascii; ``drop_q`` an integer in units of 2^-16 nat."""
+    drop_q = int(drop_q)
+    if not -2 ** 63 <= drop_q < 2 ** 63:
+        raise ValueError("refine_confidence: drop_q must fit an int64")
+    return _refine_call("refine_confidence", ctx, source, kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row, drop_q)
+
+
+def _refine_call(name, ctx, source, kmer_length, symbols, qtable, seq, lo, x, hi, left_row, right_row, drop_q):
+    """phk_refine_boundaries_* (``drop_q`` None) or phk_refine_confidence_*."""
     q = np.ascontiguousarray(qtable, dtype=np.int64)
     if q.ndim != 2:
-        raise ValueError("refine_boundaries: the table must be (n_rows, D)")
+        raise ValueError("%s: the table must be (n_rows, D)" % name)
     u64 = lambda v: np.ascontiguousarray(v, dtype=np.uint64).ravel()
     u32 = lambda v: np.ascontiguousarray(v, dtype=np.uint32).ravel()
     seq, lo, x, hi, left_row, right_row = u64(seq), u64(lo), u64(x), u64(hi), u32(left_row), u32(right_row)
     B = seq.shape[0]
     if not all(a.shape[0] == B for a in (lo, x, hi, left_row, right_row)):
-        raise ValueError("refine_boundaries: seq, lo, x, hi, left_row and right_row must have one entry per boundary")
+        raise ValueError("%s: seq, lo, x, hi, left_row and right_row must have one entry per boundary" % name)
     position, evidence = np.zeros(B, dtype=np.int64), np.zeros((B, 3), dtype=np.int64)
     support = np.zeros(B, dtype=np.uint32)
-    tail = (ptr(q), q.shape[0], q.shape[1], ptr(seq), ptr(lo), ptr(x), ptr(hi), ptr(left_row), ptr(right_row), B, ptr(position),
-            ptr(evidence), ptr(support))
+    out = (position, evidence, support)
+    tail = (ptr(q), q.shape[0], q.shape[1], ptr(seq), ptr(lo), ptr(x), ptr(hi), ptr(left_row), ptr(right_row), B)
+    if drop_q is None:
+        entry = "phk_refine_boundaries_"
+    else:
+        entry = "phk_refine_confidence_"
+        out += (np.zeros((B, 3), dtype=np.int64), np.zeros((B, 5), dtype=np.float64))
+        tail += (drop_q,)
+    tail += tuple(ptr(a) for a in out)
     if isinstance(source, Fasta):
-        rc = ctx.lib.phk_refine_boundaries_fasta(ctx.handle, source.handle, int(kmer_length), symbols, *tail)
+        rc = getattr(ctx.lib, entry + "fasta")(ctx.handle, source.handle, int(kmer_length), symbols, *tail)
     else:
         raw = [s.encode("latin-1", "replace") for s in source]
         offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
         if raw:
             offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
         bases = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
-        rc = ctx.lib.phk_refine_boundaries_ascii(ctx.handle, ptr(np.ascontiguousarray(bases)), ptr(offsets), len(raw),
-                                                 int(kmer_length), symbols, *tail)
+        rc = getattr(ctx.lib, entry + "ascii")(ctx.handle, ptr(np.ascontiguousarray(bases)), ptr(offsets), len(raw),
+                                               int(kmer_length), symbols, *tail)
     check_value(rc, nan=False)
-    return position, evidence, support
+    return out
 
 
 class Fasta(object):

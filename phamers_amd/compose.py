@@ -35,7 +35,7 @@ Two findings of the CPU study this module was built after:
     boundary_plan(state, owner, start, window, step, span)      the intervals around the region boundaries of a decode;
                                                                 ComposedSequences.refine / refined_regions: the boundaries
                                                                 to the base (section 4.29; refine.py)
-    python -m phamers_amd.compose -in FASTA -out DIR -S n [--scan [N]] [--per_record] [--refine [SPAN]]
+    python -m phamers_amd.compose -in FASTA -out DIR -S n [--scan [N]] [--per_record] [--refine [SPAN] [--confidence [NATS]]]
 """
 import collections
 import os
@@ -667,10 +667,25 @@ def _span(refine):
     raise ValueError("refine must be a bool or a span in bases >= 0, got %r" % (refine,))
 
 
+def _drop(confidence):
+    """``confidence`` of ``ComposedSequences.refine``: None / False = no, True = ``refine.DEFAULT_DROP`` nats, a number >= 0 =
+    that many nats.  None or the drop as a float."""
+    from . import refine as _refine
+    if confidence is None or (isinstance(confidence, (bool, np.bool_)) and not confidence):
+        return None
+    if isinstance(confidence, (bool, np.bool_)):
+        return _refine.DEFAULT_DROP
+    if isinstance(confidence, (int, float, np.integer, np.floating)):
+        _refine.drop_quantum(confidence)
+        return float(confidence)
+    raise ValueError("confidence must be a bool or a number of nats >= 0, got %r" % (confidence,))
+
+
 class ComposedSequences(object):
     """What ``segment_sequences`` returns: ``composition``; the windows' ``record_ids``, ``owner``, ``start``, ``window``,
     ``step``; ``state`` (n,), ``posterior`` (n, S); ``log_evidence`` and ``path_score`` per record; ``boundaries``: None until
-    ``refine`` has run, then a ``Boundaries``."""
+    ``refine`` has run, then a ``Boundaries``; ``boundary_confidence``: None until ``refine(confidence=...)`` has run, then a
+    ``refine.Confidence`` with one entry per entry of ``boundaries``."""
 
     def __init__(self, composition, record_ids, owner, start, window, step, decoded):
         self.composition, self.record_ids, self.owner, self.start = composition, list(record_ids), owner, start
@@ -678,19 +693,25 @@ class ComposedSequences(object):
         self.state, self.posterior = decoded.state, decoded.posterior
         self.log_evidence, self.path_score = decoded.log_evidence, decoded.path_score
         self.boundaries = None
+        self.boundary_confidence = None
 
     def __len__(self):
         return self.state.shape[0]
 
-    def refine(self, fasta_or_sequences, span=None):
+    def refine(self, fasta_or_sequences, span=None, confidence=None):
         """Refines every boundary between two runs of a record from the window grid to the base (``refine.boundaries`` on
         the intervals of ``boundary_plan``; ``span``: bases searched on either side of a window boundary at most, default
         ``window``) and fills ``self.boundaries``.  ``fasta_or_sequences`` is the input the windows were counted from.  The
         two states' profiles are row s of a ``Composition``'s ``log_profiles``, or row g S + s of a ``Compositions``' for
         record g (one group per record, as ``segment_sequences(per_record=True)`` fits them); a record whose group was not
         fitted is one run of state 0 and has no boundary.  A composition fitted with ``both_strands`` has folded
-        (strand-symmetric) profiles; they are used as they are, with the forward strand's k-mers.  Returns ``self``."""
+        (strand-symmetric) profiles; they are used as they are, with the forward strand's k-mers.  Returns ``self``.
+
+        ``confidence``: True, or a drop in nats, also fills ``self.boundary_confidence`` (``refine.confidence``: a support
+        interval and the position's posterior per boundary; True = 3 nats); None or False leaves it
+        None and is the call without it.  ``boundaries`` and ``refined_regions()`` are the same either way."""
         from . import refine as _refine
+        drop = _drop(confidence)
         comp = self.composition
         grouped = isinstance(comp, Compositions)
         D = comp.n_columns if grouped else comp.log_profiles.shape[1]
@@ -702,7 +723,12 @@ class ComposedSequences(object):
             left, right = plan.record * S + plan.left_state, plan.record * S + plan.right_state
         else:
             table, left, right = comp.log_profiles, plan.left_state, plan.right_state
-        r = _refine.boundaries(fasta_or_sequences, k, table, plan.record, plan.lo, plan.x, plan.hi, left, right)
+        if drop is None:
+            r = _refine.boundaries(fasta_or_sequences, k, table, plan.record, plan.lo, plan.x, plan.hi, left, right)
+            self.boundary_confidence = None
+        else:
+            r, self.boundary_confidence = _refine.confidence(fasta_or_sequences, k, table, plan.record, plan.lo, plan.x, plan.hi,
+                                                             left, right, drop)
         self.boundaries = Boundaries(plan.record, [self.record_ids[int(g)] for g in plan.record], plan.x, r.position,
                                      plan.left_state, plan.right_state, r.gain_nats, r.left_evidence_nats, r.right_evidence_nats,
                                      r.support, np.stack([r.gain, r.left_evidence, r.right_evidence], axis=1).reshape(-1, 3))
@@ -737,7 +763,7 @@ class ComposedSequences(object):
 
 
 def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_length=4, both_strands=False, scan=None,
-                      per_record=False, refine=False, **fit_options):
+                      per_record=False, refine=False, confidence=None, **fit_options):
     """Counts the windows of a FASTA file (or a list of strings) as one resident batch, fits ``n_states`` compositions to
     them and decodes: a ``ComposedSequences``.  ``temper`` defaults to ``segment.default_temper(window, step, k)``; the other
     ``fit_options`` are ``fit``'s (``step`` is passed on); ``scan`` goes to the fit and to the decode.  ValueError when no
@@ -750,10 +776,14 @@ def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_l
     too short for ``n_states`` is not fitted (state 0, NaN posteriors).  ``per_record`` does not go with ``scan``.
 
     ``refine``: True, or a span in bases, refines the region boundaries to the base before returning
-    (``ComposedSequences.refine`` with this call's input); False leaves ``boundaries`` None."""
+    (``ComposedSequences.refine`` with this call's input); False leaves ``boundaries`` None.
+    ``confidence`` (True, or a drop in nats) is passed to that call and fills ``boundary_confidence`` (section 4.30); it
+    requires ``refine``."""
     from . import kmer
     scan = _scan(scan)
     refine, span = _span(refine)
+    if _drop(confidence) is not None and not refine:
+        raise ValueError("confidence requires refine")
     if per_record and scan:
         raise ValueError("per_record does not go with the tile scan (scan=)")
     both_strands = kmer._check_strands(kmer.DNA, both_strands)
@@ -776,7 +806,7 @@ def segment_sequences(fasta_or_sequences, n_states, window=500, step=500, kmer_l
     finally:
         batch.close()
     result = ComposedSequences(comp, record_ids, owner, first, window, step, decoded)
-    return result.refine(fasta_or_sequences, span) if refine else result
+    return result.refine(fasta_or_sequences, span, confidence) if refine else result
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------
@@ -804,6 +834,9 @@ def _parser():
     ap.add_argument('--refine', type=int, nargs='?', const=True, default=None, metavar='SPAN',
                     help="Refine the region boundaries to the base, searching SPAN bases on either side of a window boundary "
                          "(without SPAN: the window); writes compose_boundaries.csv and compose_segments_refined.csv")
+    ap.add_argument('--confidence', type=float, nargs='?', const=True, default=None, metavar='NATS',
+                    help="With --refine: per boundary the support interval of the positions within NATS of the best log "
+                         "likelihood (without NATS: 3) and the position's posterior; writes compose_boundary_confidence.csv")
     ap.add_argument('-pf', '--positive_features', default=None, help="Count file of the positive reference (labels the states)")
     ap.add_argument('-nf', '--negative_features', default=None, help="Count file of the negative reference")
     return ap
@@ -859,6 +892,23 @@ def write_refined_files(directory, result):
             f.write("%s,%d,%d,%d,%d,%r\n" % (rid, a, e, s, nw, mp))
 
 
+def write_confidence_file(directory, result):
+    """compose_boundary_confidence.csv (one line per refined boundary: the support interval, whether the search interval cut
+    it short, and the posterior's figures) of a ``ComposedSequences`` whose ``refine(confidence=...)`` has run."""
+    os.makedirs(directory, exist_ok=True)
+    b, c = result.boundaries, result.boundary_confidence
+    if b is None or c is None:
+        raise ValueError("write_confidence_file needs the confidence: call refine(fasta_or_sequences, confidence=True) first")
+    with open(os.path.join(directory, "compose_boundary_confidence.csv"), 'w') as f:
+        f.write("record_id,window_boundary,position,lower,upper,n_within,at_lo,at_hi,mass_within,mass_at_position,mean_offset,"
+                "rms_distance\n")
+        for i in range(len(b.position)):
+            f.write("%s,%d,%d,%d,%d,%d,%d,%d,%r,%r,%r,%r\n" % (
+                b.record_id[i], int(b.window_boundary[i]), int(b.position[i]), int(c.lower[i]), int(c.upper[i]), int(c.n_within[i]),
+                int(c.at_lo[i]), int(c.at_hi[i]), float(c.mass_within[i]), float(c.mass_at_position[i]), float(c.mean_offset[i]),
+                float(c.rms_distance[i])))
+
+
 def write_files(directory, result, phage_score=None):
     """compose_windows.csv, compose_segments.csv, compose_profiles.csv and compose_trace.csv of a ``ComposedSequences``; for
     one fitted per record (``segment_sequences(per_record=True)``) the last two gain a leading record_id column and
@@ -905,6 +955,10 @@ def main(argv=None):
         raise SystemExit("--per_record does not go with --scan")
     if args.refine is not None and args.refine is not True and args.refine < 0:
         raise SystemExit("--refine takes a span in bases >= 0")
+    if args.confidence is not None and args.refine is None:
+        raise SystemExit("--confidence goes with --refine")
+    if args.confidence is not None and args.confidence is not True and not (np.isfinite(args.confidence) and args.confidence >= 0):
+        raise SystemExit("--confidence takes a number of nats >= 0")
     result = segment_sequences(args.input_file, args.states, args.window, args.step, args.kmer_length, args.both_strands,
                                args.scan, args.per_record, **options)
     score = None
@@ -915,8 +969,10 @@ def main(argv=None):
         score = result.composition.label(pos, neg)
     write_files(args.output_directory, result, score)
     if args.refine is not None:
-        result.refine(args.input_file, None if args.refine is True else args.refine)
+        result.refine(args.input_file, None if args.refine is True else args.refine, args.confidence)
         write_refined_files(args.output_directory, result)
+        if args.confidence is not None:
+            write_confidence_file(args.output_directory, result)
     return result
 
 

@@ -1032,6 +1032,18 @@ extern "C" int phk_refine_boundaries_fasta(phk_ctx *ctx, const phk_fasta *f, int
                                        seq, lo, x, hi, left_row, right_row, B, position, evidence, support);
 }
 
+// ... and with the boundary confidence (refine.hip)
+extern "C" int phk_refine_confidence_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const char *symbols4, const int64_t *qtable,
+                                           uint64_t n_rows, uint64_t D, const uint64_t *seq, const uint64_t *lo, const uint64_t *x,
+                                           const uint64_t *hi, const uint32_t *left_row, const uint32_t *right_row, uint64_t B,
+                                           int64_t drop_q, int64_t *position, int64_t *evidence, uint32_t *support, int64_t *interval,
+                                           double *sums) {
+    PHK_REQUIRE(ctx && f, "phk_refine_confidence_fasta: NULL");
+    PHK_REQUIRE(f->bases.data() || f->offsets.back() == 0, "phk_refine_confidence_fasta: the file was only indexed (phk_fasta_index)");
+    return phk_refine_confidence_ascii(ctx, f->bases.data(), f->offsets.data(), f->offsets.size() - 1, k, symbols4, qtable, n_rows, D,
+                                       seq, lo, x, hi, left_row, right_row, B, drop_q, position, evidence, support, interval, sums);
+}
+
 extern "C" int phk_count_fasta(phk_ctx *ctx, const phk_fasta *f, int k, const char *symbols4, int64_t *counts) {
     PHK_REQUIRE(ctx && f, "phk_count_fasta: NULL");
     PHK_REQUIRE(f->bases.data() || f->offsets.back() == 0, "phk_count_fasta: the file was only indexed (phk_fasta_index)");
