@@ -4,6 +4,7 @@ the bootstrap by the brute-force weighted pair sum (and, for large shapes, by th
 
     placements(scores, n_pos)               -> t_pos (C, P), t_neg (C, N) int64
     grams(t_pos, t_neg)                     -> area2 (list of int), G10, G01 (object arrays of Python ints)
+    placements_by_sort / grams_exact        -> the same two for shapes the P x N matrix cannot hold, entries up to 2^64
     covariance / delta / delta_variance / z / p_value
     weights(seed, b, P, N)                  -> (n,) int64: how often resample b draws each row
     bootstrap_brute / bootstrap_runs(scores, n_pos, seed, B, first=0) -> (B, C) uint64
@@ -94,16 +95,51 @@ def grams(t_pos, t_neg):
     return [int(v) for v in tp.sum(axis=1)], tp.dot(tp.T).astype(object), tn.dot(tn.T).astype(object)
 
 
-class Statement(object):
-    """area2, Grams and the rational covariance of one matrix."""
+def placements_by_sort(scores, n_pos):
+    """The same without the P x N matrix, for shapes it cannot hold: with the other class sorted, #{y < x} and #{y <= x} are
+    the two insertion points of x (np.searchsorted left / right), so t_pos = left + right; for a negative y among the sorted
+    positives #{x > y} = P - right and #{x == y} = right - left, so t_neg = 2 P - right - left."""
+    s, P = _matrix(scores, n_pos)
+    t_pos, t_neg = [], []
+    for row in s:
+        x, y = row[:P] + 0.0, row[P:] + 0.0               # + 0.0: -0.0 -> +0.0, one value whatever the sort makes of signs
+        xs, ys = np.sort(x), np.sort(y)
+        t_pos.append(np.searchsorted(ys, x, side='left') + np.searchsorted(ys, x, side='right'))
+        t_neg.append(2 * P - np.searchsorted(xs, y, side='right') - np.searchsorted(xs, y, side='left'))
+    return np.array(t_pos, dtype=np.int64), np.array(t_neg, dtype=np.int64)
 
-    def __init__(self, scores, n_pos):
+
+GRAM_CHUNK = 1 << 17   # rows per int64 dot product of grams_exact
+
+
+def grams_exact(t_pos, t_neg):
+    """``grams`` for any size the library accepts (entries below 2^64) without object arrays: int64 dot products over at
+    most 2^17 rows -- placements are below 2^23 (n < 2^22 under the library's limit), so a chunk's sum stays below
+    2^17 2^46 = 2^63 -- added up as Python integers."""
+    out = []
+    for t in (np.asarray(t_pos, dtype=np.int64), np.asarray(t_neg, dtype=np.int64)):
+        if t.size and int(t.max()) >= 1 << 23:
+            raise ValueError("a placement of 2^23 or more: a chunk's sum could pass int64")
+        g = np.zeros((len(t), len(t)), dtype=object)
+        for lo in range(0, t.shape[1], GRAM_CHUNK):
+            piece = t[:, lo:lo + GRAM_CHUNK]
+            g += piece.dot(piece.T).astype(object)
+        out.append(g)
+    area2 = [int(v) for v in np.asarray(t_pos, dtype=np.int64).sum(axis=1)]   # (<= 2 P N < 2^45)
+    return area2, out[0], out[1]
+
+
+class Statement(object):
+    """area2, Grams and the rational covariance of one matrix (``by_sort``: placements_by_sort and grams_exact, for shapes
+    the brute-force forms cannot hold)."""
+
+    def __init__(self, scores, n_pos, by_sort=False):
         s, P = _matrix(scores, n_pos)
         self.P, self.N = P, s.shape[1] - P
         if self.P < 2 or self.N < 2:
             raise ValueError("two rows of each class")
-        self.t_pos, self.t_neg = placements(s, P)
-        self.area2, self.G10, self.G01 = grams(self.t_pos, self.t_neg)
+        self.t_pos, self.t_neg = (placements_by_sort if by_sort else placements)(s, P)
+        self.area2, self.G10, self.G01 = (grams_exact if by_sort else grams)(self.t_pos, self.t_neg)
         self.C = len(self.area2)
 
     def cov_fraction(self, a, b):

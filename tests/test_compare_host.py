@@ -73,6 +73,55 @@ def test_run_formula_equals_brute_force(scores):
     assert [int(v) for v in st.t_pos.sum(axis=1)] == st.area2
 
 
+def _assert_sort_forms_equal_brute_force(m, n_pos):
+    t_pos, t_neg = ref.placements(m, n_pos)
+    s_pos, s_neg = ref.placements_by_sort(m, n_pos)
+    assert s_pos.dtype == np.int64 and np.array_equal(s_pos, t_pos) and np.array_equal(s_neg, t_neg)
+    area2, g10, g01 = ref.grams(t_pos, t_neg)
+    e_area2, e10, e01 = ref.grams_exact(s_pos, s_neg)
+    assert e_area2 == area2 and all(type(a) is int for a in e_area2)
+    assert e10.dtype == object and np.array_equal(e10, g10) and np.array_equal(e01, g01)
+    assert all(type(v) is int for v in e10.ravel()) and all(type(v) is int for v in e01.ravel())
+
+
+@pytest.mark.parametrize("name", sorted(evaluate_ref.cases()))
+def test_sort_based_placements_and_chunked_grams_equal_brute_force_on_the_cases(name):
+    pos, neg = evaluate_ref.cases()[name]
+    _assert_sort_forms_equal_brute_force(np.concatenate((pos, neg))[None, :], len(pos))
+
+
+@pytest.mark.parametrize("shape", [(37, 45), (301, 212)], ids=lambda s: "%dx%d" % s)
+def test_sort_based_placements_and_chunked_grams_equal_brute_force_on_noisy_cells(shape, monkeypatch):
+    p, n = shape
+    m = ref.noisy_cells(np.random.RandomState(p), p, n, 6)
+    a, b = evaluate_ref.cases()["rounded"]                 # holds +0.0 and -0.0 in both classes
+    signed = np.r_[a[:p], b[:n]]
+    assert np.signbit(signed[signed == 0]).any() and not np.signbit(signed[signed == 0]).all()
+    assert (signed[:p] == 0).any() and (signed[p:] == 0).any()
+    m = np.vstack((m, signed))
+    _assert_sort_forms_equal_brute_force(m, p)
+    st, by_sort = ref.Statement(m, p), ref.Statement(m, p, by_sort=True)
+    assert by_sort.area2 == st.area2 and np.array_equal(by_sort.covariance(), st.covariance())
+    monkeypatch.setattr(ref, "GRAM_CHUNK", 64)             # several chunks and a partial last one
+    _assert_sort_forms_equal_brute_force(m, p)
+
+
+def test_chunked_grams_are_exact_where_int64_is_not():
+    """Placements of the size the device meets at its limit (below 2^23), enough rows for a sum past 2^63: the chunked form
+    equals Python-integer arithmetic, and the uint64 dot product (mod 2^64) agrees with it below 2^64."""
+    rng = np.random.RandomState(1)
+    rows = ref.GRAM_CHUNK + ref.GRAM_CHUNK // 2 + 11        # two chunks; rows 2^46 lies between 2^63 and 2^64
+    t = rng.randint(2 ** 23 - 4096, 2 ** 23, (2, rows)).astype(np.int64)
+    area2, g, _ = ref.grams_exact(t, t[:, :5])
+    want = [[sum(int(a) * int(b) for a, b in zip(t[i].tolist(), t[j].tolist())) for j in range(2)] for i in range(2)]
+    assert g.tolist() == want and area2 == [sum(t[0].tolist()), sum(t[1].tolist())]
+    assert 2 ** 63 <= min(min(r) for r in want) and max(max(r) for r in want) < 2 ** 64
+    u = t.astype(np.uint64)
+    assert [[int(v) for v in r] for r in u.dot(u.T)] == want
+    with pytest.raises(ValueError, match="2\\^23"):
+        ref.grams_exact(np.array([[2 ** 23]]), np.array([[1]]))
+
+
 def test_the_module_refuses_before_any_device_work(scores, monkeypatch):
     from phamers_amd import _lib, compare
 
