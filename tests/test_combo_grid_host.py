@@ -1,5 +1,6 @@
 """CPU-only: the NumPy statement of a cell of the k_neighbors x k_clusters grid (tests/combo_grid_ref.py) against
-scikit-learn and the oracle, and the host side of phamers_amd.combo_grid: argument checks that come before any device call,
+scikit-learn, the oracle and -- for the parts that take fold ids of the caller's own -- a plain Python brute force, the inputs
+of tests/test_gpu_combo_grid_shapes.py, and the host side of phamers_amd.combo_grid: argument checks that come before any device call,
 the CSV, the three command lines' new options, and the new kernels' figures in the built library's code objects."""
 import os
 import re
@@ -66,6 +67,103 @@ def test_tie_fixture_has_duplicates_of_every_kind():
     assert (same & (cls[:, None] != cls[None, :])).any()
     assert (same & (fold_of[:, None] != fold_of[None, :])).any()
     assert (same & (fold_of[:, None] == fold_of[None, :])).any()
+
+
+# ---- the statement with fold ids of the caller's own (tests/test_gpu_combo_grid_shapes.py) ------------------------------
+def _small_case():
+    """13 integer-valued rows in 3 columns (every squared distance an exact small integer, many of them equal), four fold
+    ids of which one holds nothing and one a single row."""
+    rng = np.random.RandomState(5)
+    X = rng.randint(0, 3, (13, 3)).astype(np.float64)
+    X[7] = X[2]
+    fold_of = np.array([0, 1, 0, 0, 1, 3, 0, 1, 0, 1, 0, 0, 1])
+    is_pos = np.arange(13) % 3 != 1
+    return X, fold_of, is_pos
+
+
+def _d2(a, b):
+    s = 0.0
+    for x, y in zip(a, b):
+        s += (float(x) - float(y)) * (float(x) - float(y))      # exact on the small case's integers
+    return s
+
+
+def test_neighbour_bits_and_votes_equal_a_plain_python_brute_force():
+    X, fold_of, is_pos = _small_case()
+    assert np.bincount(fold_of, minlength=4).tolist() == [7, 5, 0, 1]
+    kmax = 6                                                    # the smallest train set: 13 - 7 rows
+    bits = ref.neighbour_bits(X, fold_of, is_pos, kmax)
+    assert bits.shape == (13, kmax) and bits.dtype == bool
+    tied = 0
+    for i in range(13):
+        others = sorted((_d2(X[i], X[j]), j) for j in range(13) if fold_of[j] != fold_of[i])
+        tied += len(set(d for d, _ in others[:kmax + 1])) <= kmax
+        want = [bool(is_pos[j]) for _, j in others[:kmax]]
+        assert bits[i].tolist() == want, i
+        for k in range(1, kmax + 1):
+            positive = sum(want[:k])
+            assert ref.votes(bits, k)[i] == (1.0 if positive > k - positive else -1.0), (i, k)
+    assert tied >= 10                                           # the order among equal distances is what is compared
+    splits = [k for k in (2, 4, 6) if (2 * bits[:, :k].sum(axis=1) == k).any()]
+    assert splits == [2, 4, 6]                                  # even splits occur, and go to -1.0 above
+
+
+def test_kmeans_scores_for_equals_a_plain_python_brute_force():
+    import math
+    X, fold_of, _ = _small_case()
+    rng = np.random.RandomState(6)
+    cents = {f: (rng.randint(0, 3, (2 + f, 3)).astype(np.float64), rng.randint(0, 3, (3, 3)).astype(np.float64)) for f in range(4)}
+    cents[0][0][1] = X[3]                                       # a held-out row of fold 0 as its own positive centroid
+    cents[1][1][2] = X[4]                                       # and one of fold 1 as a negative centroid
+    cents[1][0][:] = X[4] + 1.0
+    got = ref.kmeans_scores_for(X, fold_of, cents)
+    assert got.shape == (13,)
+    eps = np.finfo(np.float64).eps
+    for i in range(13):
+        cp, cn = cents[int(fold_of[i])]
+        ep = math.sqrt(min(_d2(X[i], c) for c in cp))
+        en = math.sqrt(min(_d2(X[i], c) for c in cn))
+        if ep + en == 0.0:
+            assert np.isnan(got[i])
+            continue
+        want = math.tanh((en - ep) / (ep + en))
+        assert abs(got[i] - want) <= 4 * eps * abs(want), i     # (two implementations of tanh)
+    assert got[3] == np.tanh(1.0) and got[4] == np.tanh(-1.0)
+    # the plan's own fold ids give kmeans_scores
+    P, N = ref.blob_fixture()
+    rng = np.random.RandomState(3)
+    c3 = {f: (P[rng.choice(len(P), 5, replace=False)] + 0.01, N[rng.choice(len(N), 4, replace=False)] - 0.01) for f in range(FOLDS)}
+    assert np.array_equal(ref.kmeans_scores_for(np.vstack((P, N)), ref.fold_ids(len(P), len(N), FOLDS, SEED), c3),
+                          ref.kmeans_scores(P, N, FOLDS, SEED, c3))
+    # a fold without a key, or without rows, is left out
+    part = ref.kmeans_scores_for(X, fold_of, {0: cents[0], 2: cents[2]})
+    assert np.array_equal(np.isnan(part), fold_of != 0) and np.array_equal(part[fold_of == 0], got[fold_of == 0])
+
+
+def test_the_word_fixture_cannot_pass_with_a_narrower_word():
+    """What tests/test_gpu_combo_grid_shapes.py asserts of its input, with the figures of this input."""
+    X, fold_of, is_pos = ref.word_fixture()
+    assert X.shape == (200, 17) and min(int((fold_of != f).sum()) for f in range(3)) == 130
+    bits = ref.neighbour_bits(X, fold_of, is_pos, 64)
+    for k in (1, 2, 31, 32, 33, 63, 64):
+        assert set(ref.votes(bits, k).tolist()) == {-1.0, 1.0}, k
+    assert int((bits.sum(axis=1) == 32).sum()) == 9
+    assert int((ref.votes(bits, 63) != ref.votes(bits, 64)).sum()) == 3
+    assert int(bits[:, 63].sum()) == 106
+
+
+def test_blob_rows_at_other_widths_and_the_edge_fixtures():
+    rng = np.random.RandomState(1)
+    c = rng.rand(6, 20)
+    assert np.array_equal(ref.blob_rows(1, 70), c[np.arange(70) % 6] + 0.02 * rng.randn(70, 20))     # D = 20: as before
+    assert np.array_equal(ref.blob_rows(1, 70), ref.blob_fixture()[0]) and ref.blob_rows(4, 31, 257).shape == (31, 257)
+    for M in (63, 64, 65, 127, 128, 129):
+        held = np.bincount(ref.edge_folds(M), minlength=4)
+        assert held[2] == 0 and held[3] == 1 and held[0] > held[1] > 1 and held.sum() == M and M - held.max() >= 5
+        X, is_pos = ref.tie_rows(M)
+        assert X.shape == (M, 8) and np.array_equal(X, np.round(X)) and 0 < is_pos.sum() < M
+        if M > 80:
+            assert np.array_equal(X[80:], X[:M - 80]) and np.array_equal(is_pos[80:], is_pos[:M - 80])
 
 
 # ---- arguments: refused before any device call -------------------------------------------------------------------------

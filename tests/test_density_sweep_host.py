@@ -174,3 +174,34 @@ def test_per_pass_constant_matches_the_header():
     text = open(os.path.join(helpers.REPO, "include", "phamers_hip.h")).read()
     value = int(re.search(r"#define\s+PHK_KDE_SWEEP_PER_PASS\s+(\d+)", text).group(1))
     assert learning.DENSITY_SWEEP_PER_PASS == _lib.KDE_SWEEP_PER_PASS == value
+
+
+# ---- the inputs of tests/test_gpu_density_sweep_shapes.py ---------------------------------------------------------------
+@pytest.mark.parametrize("D", [8, 32])
+def test_grid_rows_tie_at_the_minimum(D):
+    Q, X = density_sweep_ref.grid_rows(D, 40 + D)
+    assert Q.shape == (130, D) and X.shape == (300, D)
+    for a in (Q, X):
+        assert np.array_equal(a * 8.0, np.round(a * 8.0)) and a.min() == 0.0 and a.max() == 0.25
+    assert np.array_equal(X[255], X[256]) and np.array_equal(X[16], X[17])
+    assert not np.array_equal(X[254], X[255]) and not np.array_equal(X[15], X[16])
+    # every d^2 is the true one: an integer multiple of 1/64 below 2^53 / 64 however it is summed
+    d2 = ((Q[:, None, :] - X[None, :, :]) ** 2).sum(axis=2)
+    gram = np.einsum("ij,ij->i", Q, Q)[:, None] + np.einsum("ij,ij->i", X, X)[None, :] - 2.0 * (Q @ X.T)
+    assert np.array_equal(d2, gram) and np.array_equal(d2 * 64.0, np.round(d2 * 64.0))
+    assert (d2[:40].min(axis=1) == 0.0).all() and d2[0, 16] == d2[0, 17] == 0.0 and d2[1, 255] == d2[1, 256] == 0.0
+    at_min = density_sweep_ref.rows_at_the_minimum(Q, X)
+    assert np.array_equal(at_min, (d2 == d2.min(axis=1, keepdims=True)).sum(axis=1))
+    print("D = %d: %d of 130 queries attain their smallest d^2 twice or more (most: %d rows)" % (D, (at_min >= 2).sum(), at_min.max()))
+    assert 2 * (at_min >= 2).sum() >= 130
+    own = density_sweep_ref.rows_at_the_minimum(X, X, exclude_self=True)
+    assert own[255] >= 1 and own[16] >= 1 and (own >= 2).any()
+
+
+def test_near_tie_rows_differ_by_one_ulp_in_one_column():
+    Q, X = density_sweep_ref.near_tie_rows(32, 82)
+    assert np.array_equal(density_sweep_ref.smooth_rows(20, 7, 3), _rows(20, 7, 3))
+    differ = X[1::2] != X[0::2]
+    assert (differ.sum(axis=1) == 1).all() and len(set(np.argmax(differ, axis=1).tolist())) == 32
+    assert np.array_equal(X[1::2][differ], np.nextafter(X[0::2][differ], 1.0))
+    assert np.array_equal(Q[:40], X[0:80:2]) and not (Q[40:, None, :] == X[None, :, :]).all(axis=2).any()
