@@ -28,15 +28,18 @@
 //                              vectors alike
 // The records of at least scan_from windows (phk_chain_set_scan; 0: none) are passed over by the four per-record kernels and
 // take the tile scan, the phk_chain_scan_* kernels further down.
-// The recurrences of a record and the emission epilogue are the bodies of chain_body.h: the phk_chain_group_* kernels further
-// down call the same bodies with the parameters of the record's group (phk_chain_set_groups).
+// The recurrences and the emission epilogue are the bodies of chain_body.h, each stated once: the per-record kernels run a
+// span body over a whole record, the walk kernels of the tile scan run the same bodies over a tile from the vector that
+// enters it, and the phk_chain_group_* kernels further down run them with the parameters of the record's group
+// (phk_chain_set_groups).
 // The integer sums: |q| <= 2^31 and |qlog| <= 2^31 (checked), so a path over n <= 2^30 windows stays inside 2^62.
 // The float sums stay away from 0 / 0 as long as the ratio of two entries of a row or column of A stays inside the format
 // (entries of 1e-12 are tested): the largest entry of a rescaled vector is in [1/2, 1) and the state of the largest emission
 // has e = 1, so every normalising sum is at least min(A) / 2 times a positive normal number.
 #include <algorithm>
 #include <cmath>
-
+#include <cstdio>
+#include <new>
 #include <vector>
 
 #include "chain_body.h"
@@ -182,7 +185,8 @@ __global__ __launch_bounds__(256) void phk_chain_fold_kernel(const double *__res
 // [G][S^2 + S] (A then pi), gqpar likewise, glogp = [G][S][D].  rg[r] = the group of record r, or CH_NO_GROUP for a record
 // the kernels pass over (its group is inactive or holds no window).  The matrix-pipe kernels and the fold find their work
 // in descriptor tables built per phk_chain_set_grouped for the groups at work and read at blockIdx.x (uniform addresses);
-// the per-record kernels load a record's parameters from its group one record ahead of the record they work on.
+// the per-record kernels load a record's parameters from its group one record ahead of the record they work on
+// (chain_group_walk: the one loop of the three).
 //   phk_chain_group_emit_kernel      gram_tile + chain_emit_epilogue for the workgroup's (group, row tile of that group)
 //   phk_chain_group_backward_kernel  chain_backward_record with the record's group's A
 //   phk_chain_group_forward_kernel   chain_forward_record
@@ -222,25 +226,39 @@ __global__ __launch_bounds__(GT_WAVES * 64, 2) void phk_chain_group_emit_kernel(
     chain_emit_epilogue(acc, q0, g.n, S, temper, E + g.w0 * S, M + g.w0);
 }
 
-// A[j][:] of group g into arow (zeros past S and for CH_NO_GROUP)
-template <int SP>
-__device__ __forceinline__ void chain_group_row(const double *__restrict__ par, uint32_t g, uint32_t S, uint32_t j, bool live,
-                                                double (&arow)[SP]) {
-    const double *p = par + (uint64_t)(g == CH_NO_GROUP ? 0 : g) * (S * S + S);
-    const bool ok = live && g != CH_NO_GROUP;
+// What a record body takes of its group's parameters in lane j: a[i] = A[j][i] (COL false: backward), or a[i] = A[i][j] and
+// p = pi[j] (COL true: forward on doubles, Viterbi on the quantised logarithms); zeros past S and for CH_NO_GROUP.
+template <int SP, typename T, bool COL>
+struct ChainGroupPar {
+    T a[SP], p;
+    __device__ __forceinline__ void load(const T *__restrict__ par, uint32_t g, uint32_t S, uint32_t j, bool live) {
+        const T *q = par + (uint64_t)(g == CH_NO_GROUP ? 0 : g) * (S * S + S);
+        const bool ok = live && g != CH_NO_GROUP;
 #pragma unroll
-    for (int i = 0; i < SP; ++i) arow[i] = (ok && (uint32_t)i < S) ? p[j * S + i] : 0.0;
-}
+        for (int i = 0; i < SP; ++i) a[i] = (ok && (uint32_t)i < S) ? q[COL ? (uint32_t)i * S + j : j * S + (uint32_t)i] : (T)0;
+        if constexpr (COL) p = ok ? q[S * S + j] : (T)0;   // (a row goes without the pi entry)
+    }
+};
 
-// A[:][j] and pi[j] of group g
-template <int SP, typename T>
-__device__ __forceinline__ void chain_group_col(const T *__restrict__ par, uint32_t g, uint32_t S, uint32_t j, bool live,
-                                                T (&acol)[SP], T &pj) {
-    const T *p = par + (uint64_t)(g == CH_NO_GROUP ? 0 : g) * (S * S + S);
-    const bool ok = live && g != CH_NO_GROUP;
-#pragma unroll
-    for (int i = 0; i < SP; ++i) acol[i] = (ok && (uint32_t)i < S) ? p[(uint32_t)i * S + j] : (T)0;
-    pj = ok ? p[S * S + j] : (T)0;
+// The records of the lane group in turn: record(r, j, live, par) for every record r of a group at work, par = its group's
+// parameters, loaded one record ahead of the record at work.
+template <int SP, typename T, bool COL, typename F>
+__device__ __forceinline__ void chain_group_walk(const uint32_t *__restrict__ rg, uint64_t R, const T *__restrict__ gpar,
+                                                 uint32_t S, F &&record) {
+    const uint32_t j = threadIdx.x % SP;
+    const bool live = j < S;
+    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
+    uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP;
+    uint32_t g = r < R ? rg[r] : CH_NO_GROUP;
+    ChainGroupPar<SP, T, COL> par, next;
+    par.load(gpar, g, S, j, live);
+    for (; r < R; r += groups) {
+        const uint64_t rn = r + groups;
+        const uint32_t gn = rn < R ? rg[rn] : CH_NO_GROUP;   // the next record's parameters, issued ahead of this record's chain
+        next.load(gpar, gn, S, j, live);
+        if (g != CH_NO_GROUP) record(r, j, live, par);
+        g = gn, par = next;
+    }
 }
 
 template <int SP>
@@ -248,26 +266,10 @@ __global__ __launch_bounds__(64) void phk_chain_group_backward_kernel(const doub
                                                                       const uint64_t *__restrict__ off, uint64_t R, uint32_t S,
                                                                       const uint32_t *__restrict__ rg,
                                                                       const double *__restrict__ gpar, double *__restrict__ B) {
-    const uint32_t j = threadIdx.x % SP;
-    const bool live = j < S;
-    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
-    uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP;
-    uint32_t g = r < R ? rg[r] : CH_NO_GROUP;
-    double arow[SP];
-    chain_group_row<SP>(gpar, g, S, j, live, arow);
-    for (; r < R; r += groups) {
-        const uint64_t rn = r + groups;
-        const uint32_t gn = rn < R ? rg[rn] : CH_NO_GROUP;   // the next record's parameters, issued ahead of this record's chain
-        double an[SP];
-        chain_group_row<SP>(gpar, gn, S, j, live, an);
-        if (g != CH_NO_GROUP) {
-            const uint64_t w0 = off[r], w1 = off[r + 1];
-            if (w1 != w0) chain_backward_record<SP>(E, M, w0, w1, S, j, live, arow, B);
-        }
-        g = gn;
-#pragma unroll
-        for (int i = 0; i < SP; ++i) arow[i] = an[i];
-    }
+    chain_group_walk<SP, double, false>(rg, R, gpar, S, [&](uint64_t r, uint32_t j, bool live, const auto &par) {
+        const uint64_t w0 = off[r], w1 = off[r + 1];
+        if (w1 != w0) chain_backward_record<SP>(E, M, w0, w1, S, j, live, par.a, B);
+    });
 }
 
 template <int SP>
@@ -277,24 +279,10 @@ __global__ __launch_bounds__(64) void phk_chain_group_forward_kernel(const doubl
                                                                      const double *__restrict__ gpar,
                                                                      const double *__restrict__ B, double *__restrict__ G,
                                                                      double *__restrict__ V) {
-    const uint32_t j = threadIdx.x % SP;
-    const bool live = j < S;
-    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
     const uint64_t Ev = (uint64_t)S * S + S + 1;
-    uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP;
-    uint32_t g = r < R ? rg[r] : CH_NO_GROUP;
-    double acol[SP], pj;
-    chain_group_col<SP, double>(gpar, g, S, j, live, acol, pj);
-    for (; r < R; r += groups) {
-        const uint64_t rn = r + groups;
-        const uint32_t gn = rn < R ? rg[rn] : CH_NO_GROUP;
-        double an[SP], pn;
-        chain_group_col<SP, double>(gpar, gn, S, j, live, an, pn);
-        if (g != CH_NO_GROUP) chain_forward_record<SP>(E, M, off[r], off[r + 1], S, j, live, acol, pj, B, G, V + r * Ev);
-        g = gn, pj = pn;
-#pragma unroll
-        for (int i = 0; i < SP; ++i) acol[i] = an[i];
-    }
+    chain_group_walk<SP, double, true>(rg, R, gpar, S, [&](uint64_t r, uint32_t j, bool live, const auto &par) {
+        chain_forward_record<SP>(E, M, off[r], off[r + 1], S, j, live, par.a, par.p, B, G, V + r * Ev);
+    });
 }
 
 template <int SP>
@@ -303,30 +291,15 @@ __global__ __launch_bounds__(64) void phk_chain_group_viterbi_kernel(const doubl
                                                                      const uint32_t *__restrict__ rg,
                                                                      const int64_t *__restrict__ gqpar, uint8_t *__restrict__ BP,
                                                                      int64_t *__restrict__ score, uint8_t *__restrict__ last) {
-    const uint32_t j = threadIdx.x % SP;
-    const bool live = j < S;
-    const uint64_t groups = (uint64_t)gridDim.x * (64 / SP);
-    uint64_t r = (uint64_t)blockIdx.x * (64 / SP) + threadIdx.x / SP;
-    uint32_t g = r < R ? rg[r] : CH_NO_GROUP;
-    long long qcol[SP], qp;
-    chain_group_col<SP, long long>((const long long *)gqpar, g, S, j, live, qcol, qp);
-    for (; r < R; r += groups) {
-        const uint64_t rn = r + groups;
-        const uint32_t gn = rn < R ? rg[rn] : CH_NO_GROUP;
-        long long qn[SP], qpn;
-        chain_group_col<SP, long long>((const long long *)gqpar, gn, S, j, live, qn, qpn);
-        if (g != CH_NO_GROUP) {
-            const uint64_t w0 = off[r], w1 = off[r + 1];
-            if (w1 == w0) {
-                if (j == 0) score[r] = 0, last[r] = 0;
-            } else {
-                chain_viterbi_record<SP>(E, M, w0, w1, S, j, live, qcol, qp, BP, score, last, r);
-            }
+    chain_group_walk<SP, long long, true>(rg, R, (const long long *)gqpar, S,
+                                          [&](uint64_t r, uint32_t j, bool live, const auto &par) {
+        const uint64_t w0 = off[r], w1 = off[r + 1];
+        if (w1 == w0) {
+            if (j == 0) score[r] = 0, last[r] = 0;
+        } else {
+            chain_viterbi_record<SP>(E, M, w0, w1, S, j, live, par.a, par.p, BP, score, last, r);
         }
-        g = gn, qp = qpn;
-#pragma unroll
-        for (int i = 0; i < SP; ++i) qcol[i] = qn[i];
-    }
+    });
 }
 
 // Rx holds the spread gamma of the windows wa .. of the batch; a group's rows start at window w0 (before wa for a group cut
@@ -356,14 +329,16 @@ extern "C" uint64_t phk_chain_grid_pass(void) { return (uint64_t)CH_BLOCKS_MAX *
 // are s = 0 .. ns - 1 (record sr[s], tiles st[s] .. st[s + 1] - 1); tile t belongs to scanned record ti[t].
 //   phk_chain_scan_tile_kernel   a group of SP x SP lanes per tile, lane (i, j) = entry [i][j]: F = the ordered product of the
 //                                tile's A diag(e_t) with the exponent of its power-of-two rescaling, the max-plus product Vq on
-//                                int64, the tile's sum of M.  A record's first tile starts from pi: every row is that vector.
+//                                int64, the tile's sum of M.  A record's first tile starts from
+//                                pi: every row is that vector.
 //   phk_chain_scan_carry_kernel  a group of SP x SP lanes per scanned record, over its tiles in tile order; blockIdx.y is the
 //                                role: alpha entering every tile and the log evidence (left to right), beta leaving every tile
 //                                (right to left), delta entering every tile, path_score and the last state (left to right).
 //                                The tiles' matrices are loaded CH_PF tiles ahead of the chain.
-//   phk_chain_scan_walk_kernel   a group of SP lanes per tile: the backward and the forward recurrence of the per-record kernels
-//                                inside the tile from the vectors that enter it; gamma, the tile's xi, gamma_0 from the first
-//   phk_chain_scan_path_kernel   likewise the max-plus recurrence: the backpointer words (the tile's first step too) and the
+//   phk_chain_scan_walk_kernel   a group of SP lanes per tile: chain_backward_span and chain_forward_span, the bodies of the
+//                                per-record kernels, inside the tile from the vectors that enter it; gamma, the tile's xi,
+//                                gamma_0 from the first
+//   phk_chain_scan_path_kernel   likewise chain_maxplus_span: the backpointer words (the tile's first step too) and the
 //                                tile's map from end state to the state before the tile
 //   phk_chain_scan_fold_kernel   xi of a record = its tiles' xi added in tile order, into V[r]
 //   phk_chain_scan_ends_kernel   lane per scanned record: the state at every tile's end, right to left through the maps
@@ -447,6 +422,8 @@ __global__ __launch_bounds__(64) void phk_chain_scan_tile_kernel(const double *_
             for (int k = 0; k < SP; ++k) gs += __shfl(f, k, SP) * acol[k];
             f = gs * e;
             fe += chain_scale2x<1, G>(f);
+            // row i of the max-plus product: chain_maxplus_step without the predecessor's index, kept here in its own words
+            // because the call costs this kernel registers (96 -> 100 VGPRs at SP = 4)
             long long best = __shfl(v, 0, SP) + qcol[0];
 #pragma unroll
             for (int k = 1; k < SP; ++k) {
@@ -593,64 +570,27 @@ __global__ __launch_bounds__(64) void phk_chain_scan_walk_kernel(const double *_
         uint64_t r, a, b;
         bool first;
         chain_scan_tile(ti, sr, st, off, t, r, first, a, b);
-        // beta of the tile's steps, right to left from the vector of its last step
-        double bv = live ? BO[t * SP + j] : 0.0;
-        {
-            uint64_t w = b - 1;
-            double x = live ? E[w * S + j] - M[w] : 0.0;
-            for (;;) {
-                if (live) B[w * S + j] = bv;
-                if (w == a) break;
-                const double e = live ? exp(x) : 0.0;
-                --w;
-                x = live ? E[w * S + j] - M[w] : 0.0;
-                const double u = e * bv;
-                double nb = 0.0;
-#pragma unroll
-                for (int i = 0; i < SP; ++i) nb += arow[i] * __shfl(u, i, SP);
-                (void)chain_scale2<SP>(nb);
-                bv = nb;
-            }
-        }
-        // alpha, gamma and xi left to right; bv is now beta of the tile's first step
+        // beta of the tile's steps, right to left from the vector of its last step; bw = beta of its first step
+        double bw = chain_backward_span<SP>(E, M, a, b, S, j, live, arow, live ? BO[t * SP + j] : 0.0, B);
+        // alpha, gamma and xi left to right from the vector that enters the tile (the exponents and the sum of M are the
+        // carry's: what the span adds up here goes unused)
         double xi[SP];
 #pragma unroll
         for (int i = 0; i < SP; ++i) xi[i] = 0.0;
-        double x = live ? E[a * S + j] - M[a] : 0.0, bw = bv, al;
+        double mw = M[a], x = live ? E[a * S + j] - mw : 0.0, al, sm = 0.0;
+        int64_t ex = 0;
         uint64_t w = a;
         if (first) {
-            const double e = live ? exp(x) : 0.0;
-            const double p = pj * (e * bw);
-            const double g0 = p / chain_sum<SP>(p);
+            double g0;
+            chain_forward_first<SP>(pj, x, bw, live, g0, al);
             if (live) Gm[a * S + j] = g0, V[r * Ev + S * S + j] = g0;
-            al = pj * e;
             (void)chain_scale2<SP>(al);
             w = a + 1;
-            if (w < b) x = live ? E[w * S + j] - M[w] : 0.0, bw = live ? B[w * S + j] : 0.0;
+            if (w < b) chain_forward_load(E, M, B, w, S, j, live, mw, x, bw);
         } else {
             al = live ? AI[t * SP + j] : 0.0;
         }
-        while (w < b) {
-            const double e = live ? exp(x) : 0.0;
-            const double c = e * bw;
-            const uint64_t wn = w + 1;
-            if (wn < b) x = live ? E[wn * S + j] - M[wn] : 0.0, bw = live ? B[wn * S + j] : 0.0;
-            double wv[SP], gs = 0.0, col = 0.0;
-#pragma unroll
-            for (int i = 0; i < SP; ++i) {
-                const double pr = __shfl(al, i, SP) * acol[i];
-                gs += pr;
-                wv[i] = pr * c;
-                col += wv[i];
-            }
-            const double inv = 1.0 / chain_sum<SP>(col);
-#pragma unroll
-            for (int i = 0; i < SP; ++i) xi[i] += wv[i] * inv;
-            if (live) Gm[w * S + j] = col * inv;
-            al = gs * e;
-            (void)chain_scale2<SP>(al);
-            w = wn;
-        }
+        (void)chain_forward_span<SP>(E, M, B, w, b, S, j, live, acol, al, mw, x, bw, Gm, xi, ex, sm);
 #pragma unroll
         for (int i = 0; i < SP; ++i) XI[t * (SP * SP) + (uint32_t)i * SP + j] = xi[i];
     }
@@ -677,30 +617,14 @@ __global__ __launch_bounds__(64) void phk_chain_scan_path_kernel(const double *_
         chain_scan_tile(ti, sr, st, off, t, r, first, a, b);
         long long d;
         uint64_t w = a;
-        uint32_t org = j;
         if (first) {
-            d = qp + (live ? (long long)chain_quant(E[a * S + j] - M[a]) : 0ll);
+            d = chain_maxplus_first(E, M, a, S, j, live, qp);
             w = a + 1;
         } else {
             d = live ? (long long)DI[t * SP + j] : 0ll;
         }
-        double x = (live && w < b) ? E[w * S + j] - M[w] : 0.0;
-        while (w < b) {
-            const long long q = (long long)chain_quant(x);
-            const uint64_t wn = w + 1;
-            x = (live && wn < b) ? E[wn * S + j] - M[wn] : 0.0;
-            long long best = __shfl(d, 0, SP) + qcol[0];
-            uint32_t k = 0;
-#pragma unroll
-            for (int i = 1; i < SP; ++i) {
-                const long long c = __shfl(d, i, SP) + qcol[i];
-                if ((uint32_t)i < S && c > best) best = c, k = (uint32_t)i;   // a tie stays with the smaller predecessor
-            }
-            d = best + q;
-            BP[8 * w + j] = (uint8_t)k;
-            org = __shfl(org, k, SP);
-            w = wn;
-        }
+        uint32_t org = j;   // the state before the tile on the best path to state j of the step reached
+        (void)chain_maxplus_span<SP>(E, M, w, b, S, j, live, qcol, d, BP, [&](uint32_t k) { org = __shfl(org, k, SP); });
         MP[8 * t + j] = (uint8_t)org;
     }
 }
@@ -755,28 +679,44 @@ extern "C" uint64_t phk_chain_tile(void) { return PHK_CHAIN_TILE; }
 extern "C" uint64_t phk_chain_scan_grid_pass(void) { return CH_SCAN_PASS; }
 
 // ---- the resident chain ------------------------------------------------------------------------------------------------
+// the tile scan (phk_chain_set_scan) and its buffers
+struct ChainScan {
+    uint64_t from = 0, ns = 0, nt = 0;     // the threshold at work (0 = every record on the per-record route), scanned
+                                           // records, tiles
+    uint64_t asked = 0;                    // the threshold as the caller gave it (grouped mode refuses any but 0)
+    PhkDevMem ti, sr, st, F, FE, Vq, SM, AI, BO, DI, XI, MP, END;
+};
+
+// grouped mode (phk_chain_set_groups) and its buffers
+struct ChainGroups {
+    uint64_t G = 0;                        // groups of consecutive records; 0 = one set of parameters for every record
+    std::vector<uint64_t> off;             // [G + 1] over the records
+    std::vector<uint8_t> work;             // per group: at work in the calls after the last phk_chain_set_grouped
+    bool tables = false;                   // the descriptor tables below are those of work
+    struct Batch { uint64_t wa, nb, d0, d1; };                    // windows wa .. wa + nb - 1, expect descriptors d0 .. d1 - 1
+    std::vector<Batch> batches;
+    std::vector<std::pair<uint64_t, uint64_t>> levels_v, levels_t;   // fold descriptors [first, last) level by level
+    uint64_t ntiles = 0;
+    PhkDevMem rg, spans, par, qpar, logp, part, resT, resV, fold, tiles, etiles, folds;
+};
+
 struct phk_chain {
     uint64_t n = 0, R = 0, D = 0, B = 0;   // B: rows per batch of the emission and expectation passes
     uint32_t S = 0;
     bool from_counts = false, ready = false;
     const uint32_t *counts = nullptr;      // the batch's rows, or own_counts
     PhkDevMem own_counts, off, E, M, Bt, G, BP, state, par, qpar, logp, V, last, score, Rx, part, fold[2];
-    // the tile scan (phk_chain_set_scan): ns scanned records, nt tiles; 0 = every record on the per-record route
-    uint64_t scan_from = 0, ns = 0, nt = 0;
-    std::vector<uint64_t> h_off;           // the offsets on the host: the tile tables are built from them
-    PhkDevMem s_ti, s_sr, s_st, s_F, s_FE, s_Vq, s_SM, s_AI, s_BO, s_DI, s_XI, s_MP, s_END;
-    uint64_t scan_asked = 0;               // the threshold as the caller gave it (grouped mode refuses any but 0)
-    // grouped mode (phk_chain_set_groups): G groups of consecutive records; 0 = one set of parameters for every record
-    uint64_t NG = 0;
-    std::vector<uint64_t> g_off;           // [G + 1] over the records
-    std::vector<uint8_t> g_work;           // per group: at work in the calls after the last phk_chain_set_grouped
-    bool g_tables = false;                 // the descriptor tables below are those of g_work
-    struct Batch { uint64_t wa, nb, d0, d1; };                    // windows wa .. wa + nb - 1, expect descriptors d0 .. d1 - 1
-    std::vector<Batch> g_batches;
-    std::vector<std::pair<uint64_t, uint64_t>> g_levels_v, g_levels_t;   // fold descriptors [first, last) level by level
-    uint64_t g_ntiles = 0;
-    PhkDevMem g_rg, g_grp, g_par, g_qpar, g_logp, g_part, g_resT, g_resV, g_fold, g_tiles, g_etiles, g_folds;
+    std::vector<uint64_t> h_off;           // the offsets on the host: the tile and group tables are built from them
+    ChainScan scan;
+    ChainGroups grp;
 };
+
+// a member that owns its buffers, as new: what it held is freed (the caller drains the stream if it may be in use)
+template <typename T>
+static void chain_renew(T &x) {
+    x.~T();
+    new (&x) T();
+}
 
 static unsigned chain_grid(uint64_t items, uint64_t per_block, uint64_t cap) {
     const uint64_t b = phk_div_up(items, per_block);
@@ -910,26 +850,26 @@ extern "C" int phk_chain_destroy(phk_ctx *ctx, phk_chain *c) {
     return PHK_OK;
 }
 
-static int chain_scan_alloc(phk_ctx *ctx, phk_chain *c, const std::vector<uint32_t> &ti, const std::vector<uint64_t> &sr,
-                            const std::vector<uint64_t> &st) {
+static int chain_scan_alloc(phk_ctx *ctx, ChainScan &s, uint32_t S, const std::vector<uint32_t> &ti,
+                            const std::vector<uint64_t> &sr, const std::vector<uint64_t> &st) {
     const char *who = "phk_chain_set_scan";
-    const uint64_t nt = ti.size(), ns = sr.size(), SP = c->S <= 2 ? 2 : (c->S <= 4 ? 4 : 8), G = SP * SP;
-    PHK_TRY(c->s_ti.alloc(who, "tile table", nt * 4));
-    PHK_TRY(c->s_sr.alloc(who, "tile table", ns * 8));
-    PHK_TRY(c->s_st.alloc(who, "tile table", (ns + 1) * 8));
-    PHK_TRY(c->s_F.alloc(who, "tile matrices", nt * G * 8));
-    PHK_TRY(c->s_FE.alloc(who, "tile exponents", nt * 4));
-    PHK_TRY(c->s_Vq.alloc(who, "tile matrices", nt * G * 8));
-    PHK_TRY(c->s_SM.alloc(who, "tile sums", nt * 8));
-    PHK_TRY(c->s_AI.alloc(who, "entering vectors", nt * SP * 8));
-    PHK_TRY(c->s_BO.alloc(who, "entering vectors", nt * SP * 8));
-    PHK_TRY(c->s_DI.alloc(who, "entering vectors", nt * SP * 8));
-    PHK_TRY(c->s_XI.alloc(who, "tile vectors", nt * G * 8));
-    PHK_TRY(c->s_MP.alloc(who, "tile maps", nt * 8));
-    PHK_TRY(c->s_END.alloc(who, "tile end states", nt));
-    PHK_TRY(phk_copy_to_device(ctx, c->s_ti.ptr, ti.data(), nt * 4));
-    PHK_TRY(phk_copy_to_device(ctx, c->s_sr.ptr, sr.data(), ns * 8));
-    PHK_TRY(phk_copy_to_device(ctx, c->s_st.ptr, st.data(), (ns + 1) * 8));
+    const uint64_t nt = ti.size(), ns = sr.size(), SP = S <= 2 ? 2 : (S <= 4 ? 4 : 8), G = SP * SP;
+    PHK_TRY(s.ti.alloc(who, "tile table", nt * 4));
+    PHK_TRY(s.sr.alloc(who, "tile table", ns * 8));
+    PHK_TRY(s.st.alloc(who, "tile table", (ns + 1) * 8));
+    PHK_TRY(s.F.alloc(who, "tile matrices", nt * G * 8));
+    PHK_TRY(s.FE.alloc(who, "tile exponents", nt * 4));
+    PHK_TRY(s.Vq.alloc(who, "tile matrices", nt * G * 8));
+    PHK_TRY(s.SM.alloc(who, "tile sums", nt * 8));
+    PHK_TRY(s.AI.alloc(who, "entering vectors", nt * SP * 8));
+    PHK_TRY(s.BO.alloc(who, "entering vectors", nt * SP * 8));
+    PHK_TRY(s.DI.alloc(who, "entering vectors", nt * SP * 8));
+    PHK_TRY(s.XI.alloc(who, "tile vectors", nt * G * 8));
+    PHK_TRY(s.MP.alloc(who, "tile maps", nt * 8));
+    PHK_TRY(s.END.alloc(who, "tile end states", nt));
+    PHK_TRY(phk_copy_to_device(ctx, s.ti.ptr, ti.data(), nt * 4));
+    PHK_TRY(phk_copy_to_device(ctx, s.sr.ptr, sr.data(), ns * 8));
+    PHK_TRY(phk_copy_to_device(ctx, s.st.ptr, st.data(), (ns + 1) * 8));
     PHK_HIP(hipStreamSynchronize(ctx->stream));   // the tables leave scope
     return PHK_OK;
 }
@@ -937,12 +877,10 @@ static int chain_scan_alloc(phk_ctx *ctx, phk_chain *c, const std::vector<uint32
 extern "C" int phk_chain_set_scan(phk_ctx *ctx, phk_chain *c, uint64_t scan_from) {
     PHK_ENTER(ctx, "phk_chain_set_scan");
     PHK_REQUIRE(c, "phk_chain_set_scan: NULL chain");
-    PHK_REQUIRE(!(c->NG && scan_from), "phk_chain_set_scan: a grouped chain does not take the tile scan");
+    PHK_REQUIRE(!(c->grp.G && scan_from), "phk_chain_set_scan: a grouped chain does not take the tile scan");
     PHK_HIP(hipStreamSynchronize(ctx->stream));   // the buffers of an earlier threshold may be in use
-    PhkDevMem *mem[] = {&c->s_ti, &c->s_sr, &c->s_st, &c->s_F, &c->s_FE, &c->s_Vq, &c->s_SM,
-                        &c->s_AI, &c->s_BO, &c->s_DI, &c->s_XI, &c->s_MP, &c->s_END};
-    for (PhkDevMem *m : mem) m->release();
-    c->scan_from = 0, c->ns = 0, c->nt = 0, c->scan_asked = scan_from;
+    chain_renew(c->scan);
+    c->scan.asked = scan_from;
     if (scan_from == 0 || c->n == 0) return PHK_OK;
     std::vector<uint32_t> ti;
     std::vector<uint64_t> sr, st;
@@ -955,30 +893,76 @@ extern "C" int phk_chain_set_scan(phk_ctx *ctx, phk_chain *c, uint64_t scan_from
     }
     if (sr.empty()) return PHK_OK;
     st.push_back(ti.size());
-    const int rc = chain_scan_alloc(ctx, c, ti, sr, st);
+    const int rc = chain_scan_alloc(ctx, c->scan, c->S, ti, sr, st);
     if (rc != PHK_OK) {
-        for (PhkDevMem *m : mem) m->release();
-        c->scan_asked = 0;
+        chain_renew(c->scan);
         return rc;
     }
-    c->scan_from = scan_from, c->ns = sr.size(), c->nt = ti.size();
+    c->scan.from = scan_from, c->scan.ns = sr.size(), c->scan.nt = ti.size();
     return PHK_OK;
 }
 
+#define CHAIN_BY_SP(S, CALL)  \
+    do {                      \
+        if ((S) <= 2) {       \
+            CALL(2);          \
+        } else if ((S) <= 4) {\
+            CALL(4);          \
+        } else {              \
+            CALL(8);          \
+        }                     \
+    } while (0)
+
+// the two variants of a loader: FULL (gram_tile: the columns fill whole chunks) or VEC (mix_expect_body: rows of whole float4)
+#define CHAIN_BY_FLAG(FLAG, CALL) \
+    do {                          \
+        if (FLAG) {               \
+            CALL(true);           \
+        } else {                  \
+            CALL(false);          \
+        }                         \
+    } while (0)
+
 static int chain_emit(phk_ctx *ctx, phk_chain *c, double temper) {
     const uint64_t n = c->n, D = c->D;
-    const bool full = D % GT_KC == 0;
     for (uint64_t s = 0; s < n; s += c->B) {
         const uint64_t nb = n - s < c->B ? n - s : c->B;
         const dim3 grid((unsigned)phk_div_up(nb, GT_QB)), blk(GT_WAVES * 64);
         double *E = c->E.as<double>() + s * c->S, *M = c->M.as<double>() + s;
-        if (full) {
-            PHK_LAUNCH(ctx, "phk_chain_emit_kernel", phk_chain_emit_kernel<true><<<grid, blk, 0, ctx->stream>>>(
-                                                         c->counts + s * D, nb, c->logp.as<double>(), c->S, D, temper, E, M));
-        } else {
-            PHK_LAUNCH(ctx, "phk_chain_emit_kernel", phk_chain_emit_kernel<false><<<grid, blk, 0, ctx->stream>>>(
-                                                         c->counts + s * D, nb, c->logp.as<double>(), c->S, D, temper, E, M));
-        }
+#define CH_EMIT(FULL)                                                                                                         \
+        PHK_LAUNCH(ctx, "phk_chain_emit_kernel", phk_chain_emit_kernel<FULL><<<grid, blk, 0, ctx->stream>>>(                  \
+                                                     c->counts + s * D, nb, c->logp.as<double>(), c->S, D, temper, E, M))
+        CHAIN_BY_FLAG(D % GT_KC == 0, CH_EMIT);
+#undef CH_EMIT
+    }
+    return PHK_OK;
+}
+
+// A in (0, 1), pi in (0, 1), every row of A and pi summing to 1 within 4 ulp of 1, the quantised logarithms in [-2^31, 0];
+// a message names the group (between the entry point's name and its text) unless group < 0
+static int chain_check_params(const char *who, long long group, uint32_t S, const double *trans, const double *init,
+                              const int64_t *qlog_trans, const int64_t *qlog_init) {
+    char prefix[40] = "";
+    auto where = [&]() -> const char * {   // written only for a message: the check runs per group and call
+        if (group >= 0) snprintf(prefix, sizeof prefix, "group %lld: ", group);
+        return prefix;
+    };
+    for (uint32_t i = 0; i < S * S; ++i)
+        PHK_REQUIRE(trans[i] > 0.0 && trans[i] < 1.0, "%s: %stransition probability %u = %g is not in (0, 1)", who, where(), i,
+                    trans[i]);
+    for (uint32_t i = 0; i < S; ++i)
+        PHK_REQUIRE(init[i] > 0.0 && init[i] < 1.0, "%s: %sinitial probability %u = %g is not in (0, 1)", who, where(), i, init[i]);
+    for (uint32_t i = 0; i <= S; ++i) {
+        const double *row = i < S ? trans + i * S : init;
+        double sum = 0.0;
+        for (uint32_t j = 0; j < S; ++j) sum += row[j];
+        PHK_REQUIRE(fabs(sum - 1.0) <= 4.0 * 0x1p-52, "%s: %srow %u of the transition matrix (row %u: the initial distribution) "
+                                                      "does not sum to 1", who, where(), i, S);
+    }
+    for (uint32_t i = 0; i < S * S + S; ++i) {
+        const int64_t q = i < S * S ? qlog_trans[i] : qlog_init[i - S * S];
+        PHK_REQUIRE(q <= 0 && q >= -CH_QMAX, "%s: %squantised logarithm %u = %lld is not in [-2^31, 0]", who, where(), i,
+                    (long long)q);
     }
     return PHK_OK;
 }
@@ -987,24 +971,10 @@ extern "C" int phk_chain_set(phk_ctx *ctx, phk_chain *c, const double *log_profi
                              const double *init, const int64_t *qlog_trans, const int64_t *qlog_init, double temper) {
     PHK_ENTER(ctx, "phk_chain_set");
     PHK_REQUIRE(c, "phk_chain_set: NULL chain");
-    PHK_REQUIRE(!c->NG, "phk_chain_set: a grouped chain takes its parameters from phk_chain_set_grouped");
+    PHK_REQUIRE(!c->grp.G, "phk_chain_set: a grouped chain takes its parameters from phk_chain_set_grouped");
     PHK_REQUIRE(trans && init && qlog_trans && qlog_init, "phk_chain_set: NULL parameters");
     const uint32_t S = c->S;
-    for (uint32_t i = 0; i < S * S; ++i)
-        PHK_REQUIRE(trans[i] > 0.0 && trans[i] < 1.0, "phk_chain_set: transition probability %u = %g is not in (0, 1)", i, trans[i]);
-    for (uint32_t i = 0; i < S; ++i)
-        PHK_REQUIRE(init[i] > 0.0 && init[i] < 1.0, "phk_chain_set: initial probability %u = %g is not in (0, 1)", i, init[i]);
-    for (uint32_t i = 0; i <= S; ++i) {
-        const double *row = i < S ? trans + i * S : init;
-        double sum = 0.0;
-        for (uint32_t j = 0; j < S; ++j) sum += row[j];
-        PHK_REQUIRE(fabs(sum - 1.0) <= 4.0 * 0x1p-52, "phk_chain_set: row %u of the transition matrix (row %u: the initial "
-                                                      "distribution) does not sum to 1", i, S);
-    }
-    for (uint32_t i = 0; i < S * S + S; ++i) {
-        const int64_t q = i < S * S ? qlog_trans[i] : qlog_init[i - S * S];
-        PHK_REQUIRE(q <= 0 && q >= -CH_QMAX, "phk_chain_set: quantised logarithm %u = %lld is not in [-2^31, 0]", i, (long long)q);
-    }
+    PHK_TRY(chain_check_params("phk_chain_set", -1, S, trans, init, qlog_trans, qlog_init));
     PHK_REQUIRE(temper > 0.0 && temper - temper == 0.0, "phk_chain_set: temper = %g is not finite and > 0", temper);
     if (c->from_counts) {
         PHK_REQUIRE(log_profiles, "phk_chain_set: NULL log profiles");
@@ -1045,30 +1015,20 @@ extern "C" int phk_chain_emissions(phk_ctx *ctx, const phk_chain *c, double *E) 
     if (c->n == 0) return PHK_OK;
     PHK_REQUIRE(E, "phk_chain_emissions: NULL pointer");
     PHK_TRY(phk_copy_to_host(ctx, E, c->E.ptr, c->n * c->S * 8));
-    if (c->NG) chain_group_zero<double>(c, E, c->S, nullptr);   // a group that is not at work has no emissions
+    if (c->grp.G) chain_group_zero<double>(c, E, c->S, nullptr);   // a group that is not at work has no emissions
     return PHK_OK;
 }
 
-#define CHAIN_BY_SP(S, CALL)  \
-    do {                      \
-        if ((S) <= 2) {       \
-            CALL(2);          \
-        } else if ((S) <= 4) {\
-            CALL(4);          \
-        } else {              \
-            CALL(8);          \
-        }                     \
-    } while (0)
-
 // the scanned records' tiles: F, Vq and the sums of M
 static int chain_scan_tiles(phk_ctx *ctx, const phk_chain *c) {
+    const ChainScan &s = c->scan;
 #define CH_TILES(SP)                                                                                                          \
     PHK_LAUNCH(ctx, "phk_chain_scan_tile_kernel",                                                                             \
                phk_chain_scan_tile_kernel<SP>                                                                                 \
-               <<<dim3(chain_grid(c->nt, 64 / (SP * SP), CH_SCAN_PASS / (64 / (SP * SP)))), dim3(64), 0, ctx->stream>>>(      \
-                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), \
-                   c->s_st.as<uint64_t>(), c->nt, c->S, c->par.as<double>(), c->qpar.as<int64_t>(), c->s_F.as<double>(),      \
-                   c->s_FE.as<int32_t>(), c->s_Vq.as<int64_t>(), c->s_SM.as<double>()))
+               <<<dim3(chain_grid(s.nt, 64 / (SP * SP), CH_SCAN_PASS / (64 / (SP * SP)))), dim3(64), 0, ctx->stream>>>(       \
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), s.ti.as<uint32_t>(), s.sr.as<uint64_t>(),     \
+                   s.st.as<uint64_t>(), s.nt, c->S, c->par.as<double>(), c->qpar.as<int64_t>(), s.F.as<double>(),             \
+                   s.FE.as<int32_t>(), s.Vq.as<int64_t>(), s.SM.as<double>()))
     CHAIN_BY_SP(c->S, CH_TILES);
 #undef CH_TILES
     return PHK_OK;
@@ -1076,14 +1036,14 @@ static int chain_scan_tiles(phk_ctx *ctx, const phk_chain *c) {
 
 // the carry over the scanned records' tiles: `roles` roles from `role0` on (0 alpha, 1 beta, 2 delta)
 static int chain_scan_carry(phk_ctx *ctx, const phk_chain *c, uint32_t role0, uint32_t roles) {
+    const ChainScan &s = c->scan;
 #define CH_CARRY(SP)                                                                                                          \
     PHK_LAUNCH(ctx, "phk_chain_scan_carry_kernel",                                                                            \
                phk_chain_scan_carry_kernel<SP>                                                                                \
-               <<<dim3(chain_grid(c->ns, 64 / (SP * SP), CH_BLOCKS_MAX), roles), dim3(64), 0, ctx->stream>>>(                 \
-                   c->s_F.as<double>(), c->s_FE.as<int32_t>(), c->s_Vq.as<int64_t>(), c->s_SM.as<double>(),                   \
-                   c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->ns, c->S, role0, c->s_AI.as<double>(),                  \
-                   c->s_BO.as<double>(), c->s_DI.as<int64_t>(), c->V.as<double>(), c->score.as<int64_t>(),                    \
-                   c->last.as<uint8_t>()))
+               <<<dim3(chain_grid(s.ns, 64 / (SP * SP), CH_BLOCKS_MAX), roles), dim3(64), 0, ctx->stream>>>(                  \
+                   s.F.as<double>(), s.FE.as<int32_t>(), s.Vq.as<int64_t>(), s.SM.as<double>(), s.sr.as<uint64_t>(),          \
+                   s.st.as<uint64_t>(), s.ns, c->S, role0, s.AI.as<double>(), s.BO.as<double>(), s.DI.as<int64_t>(),          \
+                   c->V.as<double>(), c->score.as<int64_t>(), c->last.as<uint8_t>()))
     CHAIN_BY_SP(c->S, CH_CARRY);
 #undef CH_CARRY
     return PHK_OK;
@@ -1091,17 +1051,18 @@ static int chain_scan_carry(phk_ctx *ctx, const phk_chain *c, uint32_t role0, ui
 
 // forward-backward of the scanned records (after chain_scan_tiles): B, G and V as the per-record kernels leave them
 static int chain_scan_forward_backward(phk_ctx *ctx, const phk_chain *c) {
+    const ChainScan &s = c->scan;
     PHK_TRY(chain_scan_carry(ctx, c, 0, 2));
 #define CH_WALK(SP)                                                                                                           \
     PHK_LAUNCH(ctx, "phk_chain_scan_walk_kernel",                                                                             \
                phk_chain_scan_walk_kernel<SP>                                                                                 \
-               <<<dim3(chain_grid(c->nt, 64 / SP, CH_SCAN_PASS / (64 / SP))), dim3(64), 0, ctx->stream>>>(                    \
-                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), \
-                   c->s_st.as<uint64_t>(), c->nt, c->S, c->par.as<double>(), c->s_AI.as<double>(), c->s_BO.as<double>(),      \
-                   c->Bt.as<double>(), c->G.as<double>(), c->s_XI.as<double>(), c->V.as<double>()));                          \
+               <<<dim3(chain_grid(s.nt, 64 / SP, CH_SCAN_PASS / (64 / SP))), dim3(64), 0, ctx->stream>>>(                     \
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), s.ti.as<uint32_t>(), s.sr.as<uint64_t>(),     \
+                   s.st.as<uint64_t>(), s.nt, c->S, c->par.as<double>(), s.AI.as<double>(), s.BO.as<double>(),                \
+                   c->Bt.as<double>(), c->G.as<double>(), s.XI.as<double>(), c->V.as<double>()));                             \
     PHK_LAUNCH(ctx, "phk_chain_scan_fold_kernel",                                                                             \
-               phk_chain_scan_fold_kernel<<<dim3(chain_grid(c->ns * c->S * c->S, 256, 4096)), dim3(256), 0, ctx->stream>>>(   \
-                   c->s_XI.as<double>(), c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->ns, c->S, SP, c->V.as<double>()))
+               phk_chain_scan_fold_kernel<<<dim3(chain_grid(s.ns * c->S * c->S, 256, 4096)), dim3(256), 0, ctx->stream>>>(    \
+                   s.XI.as<double>(), s.sr.as<uint64_t>(), s.st.as<uint64_t>(), s.ns, c->S, SP, c->V.as<double>()))
     CHAIN_BY_SP(c->S, CH_WALK);
 #undef CH_WALK
     return PHK_OK;
@@ -1110,31 +1071,32 @@ static int chain_scan_forward_backward(phk_ctx *ctx, const phk_chain *c) {
 // the max-plus half of the scanned records (after chain_scan_tiles): BP, state, score and last as the per-record kernels
 // leave them
 static int chain_scan_path(phk_ctx *ctx, const phk_chain *c) {
+    const ChainScan &s = c->scan;
     PHK_TRY(chain_scan_carry(ctx, c, 2, 1));
 #define CH_PATH(SP)                                                                                                           \
     PHK_LAUNCH(ctx, "phk_chain_scan_path_kernel",                                                                             \
                phk_chain_scan_path_kernel<SP>                                                                                 \
-               <<<dim3(chain_grid(c->nt, 64 / SP, CH_SCAN_PASS / (64 / SP))), dim3(64), 0, ctx->stream>>>(                    \
-                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), \
-                   c->s_st.as<uint64_t>(), c->nt, c->S, c->qpar.as<int64_t>(), c->s_DI.as<int64_t>(), c->BP.as<uint8_t>(),    \
-                   c->s_MP.as<uint8_t>()))
+               <<<dim3(chain_grid(s.nt, 64 / SP, CH_SCAN_PASS / (64 / SP))), dim3(64), 0, ctx->stream>>>(                     \
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), s.ti.as<uint32_t>(), s.sr.as<uint64_t>(),     \
+                   s.st.as<uint64_t>(), s.nt, c->S, c->qpar.as<int64_t>(), s.DI.as<int64_t>(), c->BP.as<uint8_t>(),           \
+                   s.MP.as<uint8_t>()))
     CHAIN_BY_SP(c->S, CH_PATH);
 #undef CH_PATH
     PHK_LAUNCH(ctx, "phk_chain_scan_ends_kernel",
-               phk_chain_scan_ends_kernel<<<dim3(chain_grid(c->ns, 64, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(
-                   c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->ns, c->last.as<uint8_t>(), c->s_MP.as<uint64_t>(),
-                   c->s_END.as<uint8_t>()));
+               phk_chain_scan_ends_kernel<<<dim3(chain_grid(s.ns, 64, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>(
+                   s.sr.as<uint64_t>(), s.st.as<uint64_t>(), s.ns, c->last.as<uint8_t>(), s.MP.as<uint64_t>(),
+                   s.END.as<uint8_t>()));
     PHK_LAUNCH(ctx, "phk_chain_scan_fill_kernel",
-               phk_chain_scan_fill_kernel<<<dim3(chain_grid(c->nt, 64, CH_SCAN_PASS / 64)), dim3(64), 0, ctx->stream>>>(
-                   c->off.as<uint64_t>(), c->s_ti.as<uint32_t>(), c->s_sr.as<uint64_t>(), c->s_st.as<uint64_t>(), c->nt,
-                   c->s_END.as<uint8_t>(), c->BP.as<uint64_t>(), c->state.as<uint8_t>()));
+               phk_chain_scan_fill_kernel<<<dim3(chain_grid(s.nt, 64, CH_SCAN_PASS / 64)), dim3(64), 0, ctx->stream>>>(
+                   c->off.as<uint64_t>(), s.ti.as<uint32_t>(), s.sr.as<uint64_t>(), s.st.as<uint64_t>(), s.nt,
+                   s.END.as<uint8_t>(), c->BP.as<uint64_t>(), c->state.as<uint8_t>()));
     return PHK_OK;
 }
 
 // backward then forward over every record: B, G and the records' vectors V
 static int chain_forward_backward(phk_ctx *ctx, const phk_chain *c) {
     const double *E = c->E.as<double>(), *M = c->M.as<double>(), *par = c->par.as<double>();
-    const uint64_t *off = c->off.as<uint64_t>(), sf = c->scan_from;
+    const uint64_t *off = c->off.as<uint64_t>(), sf = c->scan.from;
     if (sf) PHK_TRY(chain_scan_forward_backward(ctx, c));
 #define CH_FB(SP)                                                                                                             \
     {                                                                                                                         \
@@ -1166,10 +1128,19 @@ static int chain_fold(phk_ctx *ctx, const phk_chain *c, const double *in, uint64
     return PHK_OK;
 }
 
+// out[r] = the log evidence of record r: the last entry of its vector V[r]
+static int chain_record_evidence(phk_ctx *ctx, const phk_chain *c, double *out) {
+    const uint64_t R = c->R, Ev = (uint64_t)c->S * c->S + c->S + 1;
+    std::vector<double> rec(R * Ev);
+    PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
+    for (uint64_t r = 0; r < R; ++r) out[r] = rec[r * Ev + Ev - 1];
+    return PHK_OK;
+}
+
 static int chain_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, double *Ns, double *xi, double *gamma0,
                             double *log_evidence, double *log_evidence_rec) {
     const uint64_t S = c->S, D = c->D, R = c->R, n = c->n, Ev = S * S + S + 1, Em = S * D + S + 1;
-    if (c->scan_from) PHK_TRY(chain_scan_tiles(ctx, c));
+    if (c->scan.from) PHK_TRY(chain_scan_tiles(ctx, c));
     PHK_TRY(chain_forward_backward(ctx, c));
     const double *tot;
     PHK_TRY(chain_fold(ctx, c, c->V.as<double>(), R, Ev, &tot));
@@ -1178,13 +1149,8 @@ static int chain_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, double 
     std::copy(v.begin(), v.begin() + S * S, xi);
     std::copy(v.begin() + S * S, v.begin() + S * S + S, gamma0);
     *log_evidence = v[S * S + S];
-    if (log_evidence_rec) {
-        std::vector<double> rec(R * Ev);
-        PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
-        for (uint64_t r = 0; r < R; ++r) log_evidence_rec[r] = rec[r * Ev + S * S + S];
-    }
+    if (log_evidence_rec) PHK_TRY(chain_record_evidence(ctx, c, log_evidence_rec));
     if (!T) return PHK_OK;
-    const bool vec = D % 4 == 0;
     for (uint64_t s = 0; s < n; s += c->B) {
         const uint64_t nb = n - s < c->B ? n - s : c->B;
         PHK_LAUNCH(ctx, "phk_chain_spread_kernel",
@@ -1192,15 +1158,12 @@ static int chain_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, double 
                        c->G.as<double>() + s * S, nb, (uint32_t)S, c->Rx.as<double>()));
         const dim3 grid((unsigned)phk_div_up(nb, MIX_RB), (unsigned)phk_div_up(D, GT_WAVES * MIX_CT)), blk(GT_WAVES * 64);
         double *part = c->part.as<double>() + (s / MIX_RB) * Em;
-        if (vec) {
-            PHK_LAUNCH(ctx, "phk_chain_expect_kernel", phk_chain_expect_kernel<true><<<grid, blk, 0, ctx->stream>>>(
-                                                           c->Rx.as<double>(), c->counts + s * D, D, nb, c->M.as<double>() + s,
-                                                           (uint32_t)S, Em, part));
-        } else {
-            PHK_LAUNCH(ctx, "phk_chain_expect_kernel", phk_chain_expect_kernel<false><<<grid, blk, 0, ctx->stream>>>(
-                                                           c->Rx.as<double>(), c->counts + s * D, D, nb, c->M.as<double>() + s,
-                                                           (uint32_t)S, Em, part));
-        }
+#define CH_EXPECT(VEC)                                                                                                        \
+        PHK_LAUNCH(ctx, "phk_chain_expect_kernel", phk_chain_expect_kernel<VEC><<<grid, blk, 0, ctx->stream>>>(               \
+                                                       c->Rx.as<double>(), c->counts + s * D, D, nb, c->M.as<double>() + s,   \
+                                                       (uint32_t)S, Em, part))
+        CHAIN_BY_FLAG(D % 4 == 0, CH_EXPECT);
+#undef CH_EXPECT
     }
     PHK_TRY(chain_fold(ctx, c, c->part.as<double>(), phk_div_up(n, MIX_RB), Em, &tot));
     std::vector<double> t(Em);
@@ -1214,7 +1177,7 @@ extern "C" int phk_chain_expect(phk_ctx *ctx, const phk_chain *c, double *T, dou
                                 double *log_evidence, double *log_evidence_rec) {
     PHK_ENTER(ctx, "phk_chain_expect");
     PHK_REQUIRE(c && c->ready, "phk_chain_expect: no chain, or phk_chain_set has not succeeded on it");
-    PHK_REQUIRE(!c->NG, "phk_chain_expect: a grouped chain gives its expectations through phk_chain_expect_grouped");
+    PHK_REQUIRE(!c->grp.G, "phk_chain_expect: a grouped chain gives its expectations through phk_chain_expect_grouped");
     PHK_REQUIRE(xi && gamma0 && log_evidence, "phk_chain_expect: NULL pointer");
     PHK_REQUIRE(!T == !Ns, "phk_chain_expect: T and Ns go together");
     PHK_REQUIRE(!T || c->from_counts, "phk_chain_expect: a chain made from emissions has no T");
@@ -1233,9 +1196,9 @@ extern "C" int phk_chain_expect(phk_ctx *ctx, const phk_chain *c, double *T, dou
 
 static int chain_decode_run(phk_ctx *ctx, const phk_chain *c, uint8_t *state, double *posterior, double *log_evidence_rec,
                             int64_t *path_score) {
-    const uint64_t S = c->S, R = c->R, n = c->n, Ev = S * S + S + 1;
-    const uint64_t *off = c->off.as<uint64_t>(), sf = c->scan_from;
-    if (c->NG) {   // every record with its group's parameters; the trace needs none
+    const uint64_t S = c->S, R = c->R, n = c->n;
+    const uint64_t *off = c->off.as<uint64_t>(), sf = c->scan.from;
+    if (c->grp.G) {   // every record with its group's parameters; the trace needs none
         if (posterior || log_evidence_rec) PHK_TRY(chain_group_forward_backward(ctx, c));
         PHK_TRY(chain_group_viterbi(ctx, c));
     } else {
@@ -1256,12 +1219,8 @@ static int chain_decode_run(phk_ctx *ctx, const phk_chain *c, uint8_t *state, do
     PHK_TRY(phk_copy_to_host(ctx, state, c->state.ptr, n));
     if (path_score) PHK_TRY(phk_copy_to_host(ctx, path_score, c->score.ptr, R * 8));
     if (posterior) PHK_TRY(phk_copy_to_host(ctx, posterior, c->G.ptr, n * S * 8));
-    if (log_evidence_rec) {
-        std::vector<double> rec(R * Ev);
-        PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
-        for (uint64_t r = 0; r < R; ++r) log_evidence_rec[r] = rec[r * Ev + S * S + S];
-    }
-    if (c->NG) {   // zeros for the groups that are not at work
+    if (log_evidence_rec) PHK_TRY(chain_record_evidence(ctx, c, log_evidence_rec));
+    if (c->grp.G) {   // zeros for the groups that are not at work
         chain_group_zero<uint8_t>(c, state, 1, nullptr);
         if (posterior) chain_group_zero<double>(c, posterior, S, nullptr);
         if (log_evidence_rec) chain_group_zero<double>(c, nullptr, 0, log_evidence_rec);
@@ -1288,17 +1247,9 @@ extern "C" int phk_chain_decode(phk_ctx *ctx, const phk_chain *c, uint8_t *state
 }
 
 // ---- grouped chains: the host half ----------------------------------------------------------------------
-static void chain_group_release(phk_chain *c) {
-    PhkDevMem *mem[] = {&c->g_rg, &c->g_grp, &c->g_par, &c->g_qpar, &c->g_logp, &c->g_part, &c->g_resT, &c->g_resV,
-                        &c->g_fold, &c->g_tiles, &c->g_etiles, &c->g_folds};
-    for (PhkDevMem *m : mem) m->release();
-    c->NG = 0, c->g_tables = false, c->g_ntiles = 0;
-    c->g_off.clear(), c->g_work.clear(), c->g_batches.clear(), c->g_levels_v.clear(), c->g_levels_t.clear();
-}
-
 // the windows [w0, w1) of group g
 static inline void chain_group_span(const phk_chain *c, uint64_t g, uint64_t &w0, uint64_t &w1) {
-    const uint64_t r0 = c->g_off[g], r1 = c->g_off[g + 1];
+    const uint64_t r0 = c->grp.off[g], r1 = c->grp.off[g + 1];
     w0 = c->R ? c->h_off[r0] : 0, w1 = c->R ? c->h_off[r1] : 0;
 }
 
@@ -1308,14 +1259,14 @@ extern "C" int phk_chain_set_groups(phk_ctx *ctx, phk_chain *c, const uint64_t *
     PHK_REQUIRE(c, "%s: NULL chain", who);
     if (G == 0) {
         PHK_REQUIRE(!group_offsets, "%s: offsets and no group", who);
-        if (!c->NG) return PHK_OK;
+        if (!c->grp.G) return PHK_OK;
         PHK_HIP(hipStreamSynchronize(ctx->stream));
-        chain_group_release(c);
+        chain_renew(c->grp);
         c->ready = false;   // (the parameters of the calls that follow come from phk_chain_set)
         return PHK_OK;
     }
     PHK_REQUIRE(c->from_counts, "%s: a chain made from emissions has no groups", who);
-    PHK_REQUIRE(c->scan_asked == 0, "%s: the tile scan is on (phk_chain_set_scan): grouped chains do not take it", who);
+    PHK_REQUIRE(c->scan.asked == 0, "%s: the tile scan is on (phk_chain_set_scan): grouped chains do not take it", who);
     PHK_REQUIRE(group_offsets, "%s: NULL offsets", who);
     PHK_REQUIRE(G < CH_NO_GROUP, "%s: 2^32 - 1 groups or more", who);
     PHK_REQUIRE(group_offsets[0] == 0 && group_offsets[G] == c->R, "%s: the group offsets do not run from 0 to the %llu records",
@@ -1324,10 +1275,10 @@ extern "C" int phk_chain_set_groups(phk_ctx *ctx, phk_chain *c, const uint64_t *
         PHK_REQUIRE(group_offsets[g] <= group_offsets[g + 1], "%s: the group offsets decrease at group %llu", who,
                     (unsigned long long)g);
     PHK_HIP(hipStreamSynchronize(ctx->stream));   // the buffers of earlier groups may be in use
-    chain_group_release(c);
+    chain_renew(c->grp);
     c->ready = false;
-    c->g_off.assign(group_offsets, group_offsets + G + 1);
-    c->NG = G;
+    c->grp.off.assign(group_offsets, group_offsets + G + 1);
+    c->grp.G = G;
     const uint64_t S = c->S, D = c->D, PS = S * S + S, Ev = PS + 1, Em = S * D + S + 1;
     // every group at work at once: its blocks' partial vectors, and two fold buffers per tree that has a second level
     std::vector<ChainGroup> grp(G);
@@ -1336,22 +1287,22 @@ extern "C" int phk_chain_set_groups(phk_ctx *ctx, phk_chain *c, const uint64_t *
         uint64_t w0, w1;
         chain_group_span(c, g, w0, w1);
         grp[g] = ChainGroup{w0, w1 - w0};
-        const uint64_t nb = phk_div_up(w1 - w0, MIX_RB), nr = c->g_off[g + 1] - c->g_off[g];
+        const uint64_t nb = phk_div_up(w1 - w0, MIX_RB), nr = c->grp.off[g + 1] - c->grp.off[g];
         blocks += nb;
         if (nb > 256) fold += 2 * phk_div_up(nb, 256) * Em;
         if (nr > 256) fold += 2 * phk_div_up(nr, 256) * Ev;
     }
     auto body = [&]() -> int {
-        PHK_TRY(c->g_rg.alloc(who, "record groups", c->R * 4));
-        PHK_TRY(c->g_grp.alloc(who, "groups", G * sizeof(ChainGroup)));
-        PHK_TRY(c->g_par.alloc(who, "parameters", G * PS * 8));
-        PHK_TRY(c->g_qpar.alloc(who, "parameters", G * PS * 8));
-        PHK_TRY(c->g_logp.alloc(who, "log profiles", G * S * D * 8));
-        PHK_TRY(c->g_part.alloc(who, "partial vectors", blocks * Em * 8));
-        PHK_TRY(c->g_resT.alloc(who, "group vectors", G * Em * 8));
-        PHK_TRY(c->g_resV.alloc(who, "group vectors", G * Ev * 8));
-        PHK_TRY(c->g_fold.alloc(who, "fold vectors", fold * 8));
-        PHK_TRY(phk_copy_to_device(ctx, c->g_grp.ptr, grp.data(), G * sizeof(ChainGroup)));
+        PHK_TRY(c->grp.rg.alloc(who, "record groups", c->R * 4));
+        PHK_TRY(c->grp.spans.alloc(who, "groups", G * sizeof(ChainGroup)));
+        PHK_TRY(c->grp.par.alloc(who, "parameters", G * PS * 8));
+        PHK_TRY(c->grp.qpar.alloc(who, "parameters", G * PS * 8));
+        PHK_TRY(c->grp.logp.alloc(who, "log profiles", G * S * D * 8));
+        PHK_TRY(c->grp.part.alloc(who, "partial vectors", blocks * Em * 8));
+        PHK_TRY(c->grp.resT.alloc(who, "group vectors", G * Em * 8));
+        PHK_TRY(c->grp.resV.alloc(who, "group vectors", G * Ev * 8));
+        PHK_TRY(c->grp.fold.alloc(who, "fold vectors", fold * 8));
+        PHK_TRY(phk_copy_to_device(ctx, c->grp.spans.ptr, grp.data(), G * sizeof(ChainGroup)));
         if (c->R) PHK_HIP(hipMemsetAsync(c->last.ptr, 0, c->R, ctx->stream));   // the trace reads it for every record
         PHK_HIP(hipStreamSynchronize(ctx->stream));   // grp leaves scope
         return PHK_OK;
@@ -1359,44 +1310,44 @@ extern "C" int phk_chain_set_groups(phk_ctx *ctx, phk_chain *c, const uint64_t *
     const int rc = body();
     if (rc != PHK_OK) {
         (void)hipStreamSynchronize(ctx->stream);
-        chain_group_release(c);
+        chain_renew(c->grp);
     }
     return rc;
 }
 
-// The tables of the groups at work (c->g_work): the records' groups, the emission tiles, the expectation blocks in batches
+// The tables of the groups at work (c->grp.work): the records' groups, the emission tiles, the expectation blocks in batches
 // of at most c->B consecutive windows, the fold levels of the records' vectors and of the blocks' partial vectors.
 static int chain_group_tables(phk_ctx *ctx, phk_chain *c) {
     const char *who = "phk_chain_set_grouped";
-    const uint64_t G = c->NG, S = c->S, D = c->D, Ev = S * S + S + 1, Em = S * D + S + 1;
+    const uint64_t G = c->grp.G, S = c->S, D = c->D, Ev = S * S + S + 1, Em = S * D + S + 1;
     const uint64_t ygroups = phk_div_up(D, GT_WAVES * MIX_CT), cap = c->B > c->n ? c->n : c->B;
     std::vector<uint32_t> rg(c->R, CH_NO_GROUP);
     std::vector<ChainGroupTile> tiles, etiles;
     std::vector<ChainGroupFold> folds;
-    c->g_batches.clear(), c->g_levels_v.clear(), c->g_levels_t.clear();
+    c->grp.batches.clear(), c->grp.levels_v.clear(), c->grp.levels_t.clear();
     struct Live { const double *in; double *res, *f[2]; uint64_t m; };
     std::vector<Live> live_v, live_t;
     uint64_t part_at = 0, fold_at = 0;
-    double *part = c->g_part.as<double>(), *fold = c->g_fold.as<double>();
+    double *part = c->grp.part.as<double>(), *fold = c->grp.fold.as<double>();
     for (uint64_t g = 0; g < G; ++g) {
-        if (!c->g_work[g]) continue;
+        if (!c->grp.work[g]) continue;
         uint64_t w0, w1;
         chain_group_span(c, g, w0, w1);
-        const uint64_t r0 = c->g_off[g], r1 = c->g_off[g + 1], n = w1 - w0, nb = phk_div_up(n, MIX_RB);
+        const uint64_t r0 = c->grp.off[g], r1 = c->grp.off[g + 1], n = w1 - w0, nb = phk_div_up(n, MIX_RB);
         std::fill(rg.begin() + r0, rg.begin() + r1, (uint32_t)g);
         for (uint64_t t = 0; t < phk_div_up(n, GT_QB); ++t) tiles.push_back(ChainGroupTile{(uint32_t)g, (uint32_t)t, 0, 0, 0});
         for (uint64_t b = 0; b < nb; ++b) {
             const uint64_t a = w0 + b * MIX_RB, e = a + MIX_RB < w1 ? a + MIX_RB : w1;
-            if (c->g_batches.empty() || e - c->g_batches.back().wa > cap)
-                c->g_batches.push_back(phk_chain::Batch{a, 0, etiles.size(), etiles.size()});
+            if (c->grp.batches.empty() || e - c->grp.batches.back().wa > cap)
+                c->grp.batches.push_back(ChainGroups::Batch{a, 0, etiles.size(), etiles.size()});
             for (uint64_t y = 0; y < ygroups; ++y)
                 etiles.push_back(ChainGroupTile{(uint32_t)g, (uint32_t)b, (uint32_t)y, 0, part_at + b});
-            c->g_batches.back().nb = e - c->g_batches.back().wa, c->g_batches.back().d1 = etiles.size();
+            c->grp.batches.back().nb = e - c->grp.batches.back().wa, c->grp.batches.back().d1 = etiles.size();
         }
-        Live t{part + part_at * Em, c->g_resT.as<double>() + g * Em, {nullptr, nullptr}, nb};
+        Live t{part + part_at * Em, c->grp.resT.as<double>() + g * Em, {nullptr, nullptr}, nb};
         if (nb > 256) t.f[0] = fold + fold_at, t.f[1] = t.f[0] + phk_div_up(nb, 256) * Em, fold_at += 2 * phk_div_up(nb, 256) * Em;
         live_t.push_back(t);
-        Live v{c->V.as<double>() + r0 * Ev, c->g_resV.as<double>() + g * Ev, {nullptr, nullptr}, r1 - r0};
+        Live v{c->V.as<double>() + r0 * Ev, c->grp.resV.as<double>() + g * Ev, {nullptr, nullptr}, r1 - r0};
         if (v.m > 256) v.f[0] = fold + fold_at, v.f[1] = v.f[0] + phk_div_up(v.m, 256) * Ev, fold_at += 2 * phk_div_up(v.m, 256) * Ev;
         live_v.push_back(v);
         part_at += nb;
@@ -1418,21 +1369,21 @@ static int chain_group_tables(phk_ctx *ctx, phk_chain *c) {
             live.swap(next);
         }
     };
-    levels(live_v, Ev, c->g_levels_v);
-    levels(live_t, Em, c->g_levels_t);
+    levels(live_v, Ev, c->grp.levels_v);
+    levels(live_t, Em, c->grp.levels_t);
     PHK_REQUIRE(tiles.size() < (1ull << 31) && etiles.size() < (1ull << 31) && folds.size() < (1ull << 31),
                 "%s: more than 2^31 workgroups in one launch", who);
-    c->g_ntiles = tiles.size();
-    if (c->g_tiles.bytes < tiles.size() * sizeof(ChainGroupTile))
-        PHK_TRY(c->g_tiles.alloc(who, "descriptors", tiles.size() * sizeof(ChainGroupTile)));
-    if (c->g_etiles.bytes < etiles.size() * sizeof(ChainGroupTile))
-        PHK_TRY(c->g_etiles.alloc(who, "descriptors", etiles.size() * sizeof(ChainGroupTile)));
-    if (c->g_folds.bytes < folds.size() * sizeof(ChainGroupFold))
-        PHK_TRY(c->g_folds.alloc(who, "descriptors", folds.size() * sizeof(ChainGroupFold)));
-    if (c->R) PHK_TRY(phk_copy_to_device(ctx, c->g_rg.ptr, rg.data(), c->R * 4));
-    if (!tiles.empty()) PHK_TRY(phk_copy_to_device(ctx, c->g_tiles.ptr, tiles.data(), tiles.size() * sizeof(ChainGroupTile)));
-    if (!etiles.empty()) PHK_TRY(phk_copy_to_device(ctx, c->g_etiles.ptr, etiles.data(), etiles.size() * sizeof(ChainGroupTile)));
-    if (!folds.empty()) PHK_TRY(phk_copy_to_device(ctx, c->g_folds.ptr, folds.data(), folds.size() * sizeof(ChainGroupFold)));
+    c->grp.ntiles = tiles.size();
+    if (c->grp.tiles.bytes < tiles.size() * sizeof(ChainGroupTile))
+        PHK_TRY(c->grp.tiles.alloc(who, "descriptors", tiles.size() * sizeof(ChainGroupTile)));
+    if (c->grp.etiles.bytes < etiles.size() * sizeof(ChainGroupTile))
+        PHK_TRY(c->grp.etiles.alloc(who, "descriptors", etiles.size() * sizeof(ChainGroupTile)));
+    if (c->grp.folds.bytes < folds.size() * sizeof(ChainGroupFold))
+        PHK_TRY(c->grp.folds.alloc(who, "descriptors", folds.size() * sizeof(ChainGroupFold)));
+    if (c->R) PHK_TRY(phk_copy_to_device(ctx, c->grp.rg.ptr, rg.data(), c->R * 4));
+    if (!tiles.empty()) PHK_TRY(phk_copy_to_device(ctx, c->grp.tiles.ptr, tiles.data(), tiles.size() * sizeof(ChainGroupTile)));
+    if (!etiles.empty()) PHK_TRY(phk_copy_to_device(ctx, c->grp.etiles.ptr, etiles.data(), etiles.size() * sizeof(ChainGroupTile)));
+    if (!folds.empty()) PHK_TRY(phk_copy_to_device(ctx, c->grp.folds.ptr, folds.data(), folds.size() * sizeof(ChainGroupFold)));
     PHK_HIP(hipStreamSynchronize(ctx->stream));   // the tables leave scope
     return PHK_OK;
 }
@@ -1443,32 +1394,16 @@ extern "C" int phk_chain_set_grouped(phk_ctx *ctx, phk_chain *c, const double *l
     const char *who = "phk_chain_set_grouped";
     PHK_ENTER(ctx, "phk_chain_set_grouped");
     PHK_REQUIRE(c, "%s: NULL chain", who);
-    PHK_REQUIRE(c->NG, "%s: the chain has no groups (phk_chain_set_groups)", who);
+    PHK_REQUIRE(c->grp.G, "%s: the chain has no groups (phk_chain_set_groups)", who);
     PHK_REQUIRE(log_profiles && trans && init && qlog_trans && qlog_init, "%s: NULL parameters", who);
     PHK_REQUIRE(D == c->D, "%s: the profiles have %llu columns, the count rows %llu", who, (unsigned long long)D,
                 (unsigned long long)c->D);
     PHK_REQUIRE(temper > 0.0 && temper - temper == 0.0, "%s: temper = %g is not finite and > 0", who, temper);
-    const uint64_t G = c->NG, S = c->S, SS = S * S, PS = SS + S;
+    const uint64_t G = c->grp.G, S = c->S, SS = S * S, PS = SS + S;
     for (uint64_t g = 0; g < G; ++g) {
         if (active && !active[g]) continue;
-        const double *A = trans + g * SS, *pi = init + g * S;
-        const unsigned long long gl = (unsigned long long)g;
-        for (uint32_t i = 0; i < SS; ++i)
-            PHK_REQUIRE(A[i] > 0.0 && A[i] < 1.0, "%s: group %llu: transition probability %u = %g is not in (0, 1)", who, gl, i, A[i]);
-        for (uint32_t i = 0; i < S; ++i)
-            PHK_REQUIRE(pi[i] > 0.0 && pi[i] < 1.0, "%s: group %llu: initial probability %u = %g is not in (0, 1)", who, gl, i, pi[i]);
-        for (uint32_t i = 0; i <= S; ++i) {
-            const double *row = i < S ? A + i * S : pi;
-            double sum = 0.0;
-            for (uint32_t j = 0; j < S; ++j) sum += row[j];
-            PHK_REQUIRE(fabs(sum - 1.0) <= 4.0 * 0x1p-52, "%s: group %llu: row %u of the transition matrix (row %u: the initial "
-                                                          "distribution) does not sum to 1", who, gl, i, (uint32_t)S);
-        }
-        for (uint32_t i = 0; i < PS; ++i) {
-            const int64_t q = i < SS ? qlog_trans[g * SS + i] : qlog_init[g * S + i - SS];
-            PHK_REQUIRE(q <= 0 && q >= -CH_QMAX, "%s: group %llu: quantised logarithm %u = %lld is not in [-2^31, 0]", who, gl, i,
-                        (long long)q);
-        }
+        PHK_TRY(chain_check_params(who, (long long)g, c->S, trans + g * SS, init + g * S, qlog_trans + g * SS,
+                                   qlog_init + g * S));
     }
     for (uint64_t g = 0; g < G; ++g) {
         if (active && !active[g]) continue;
@@ -1505,28 +1440,24 @@ extern "C" int phk_chain_set_grouped(phk_ctx *ctx, phk_chain *c, const double *l
         lp = logp.data();
     }
     auto body = [&]() -> int {
-        if (!c->g_tables || work != c->g_work) {
-            c->g_tables = false;
-            c->g_work = work;
+        if (!c->grp.tables || work != c->grp.work) {
+            c->grp.tables = false;
+            c->grp.work = work;
             PHK_TRY(chain_group_tables(ctx, c));
-            c->g_tables = true;
+            c->grp.tables = true;
         }
-        PHK_TRY(phk_copy_to_device(ctx, c->g_par.ptr, par.data(), G * PS * 8));
-        PHK_TRY(phk_copy_to_device(ctx, c->g_qpar.ptr, qpar.data(), G * PS * 8));
-        PHK_TRY(phk_copy_to_device(ctx, c->g_logp.ptr, lp, G * S * D * 8));
-        if (c->g_ntiles) {
-            const dim3 grid((unsigned)c->g_ntiles), blk(GT_WAVES * 64);
-            if (D % GT_KC == 0) {
-                PHK_LAUNCH(ctx, "phk_chain_group_emit_kernel",
-                           phk_chain_group_emit_kernel<true><<<grid, blk, 0, ctx->stream>>>(
-                               c->counts, c->g_grp.as<ChainGroup>(), c->g_tiles.as<ChainGroupTile>(), c->g_logp.as<double>(),
-                               c->S, D, temper, c->E.as<double>(), c->M.as<double>()));
-            } else {
-                PHK_LAUNCH(ctx, "phk_chain_group_emit_kernel",
-                           phk_chain_group_emit_kernel<false><<<grid, blk, 0, ctx->stream>>>(
-                               c->counts, c->g_grp.as<ChainGroup>(), c->g_tiles.as<ChainGroupTile>(), c->g_logp.as<double>(),
-                               c->S, D, temper, c->E.as<double>(), c->M.as<double>()));
-            }
+        PHK_TRY(phk_copy_to_device(ctx, c->grp.par.ptr, par.data(), G * PS * 8));
+        PHK_TRY(phk_copy_to_device(ctx, c->grp.qpar.ptr, qpar.data(), G * PS * 8));
+        PHK_TRY(phk_copy_to_device(ctx, c->grp.logp.ptr, lp, G * S * D * 8));
+        if (c->grp.ntiles) {
+            const dim3 grid((unsigned)c->grp.ntiles), blk(GT_WAVES * 64);
+#define CH_GEMIT(FULL)                                                                                                        \
+            PHK_LAUNCH(ctx, "phk_chain_group_emit_kernel",                                                                    \
+                       phk_chain_group_emit_kernel<FULL><<<grid, blk, 0, ctx->stream>>>(                                      \
+                           c->counts, c->grp.spans.as<ChainGroup>(), c->grp.tiles.as<ChainGroupTile>(),                       \
+                           c->grp.logp.as<double>(), c->S, D, temper, c->E.as<double>(), c->M.as<double>()))
+            CHAIN_BY_FLAG(D % GT_KC == 0, CH_GEMIT);
+#undef CH_GEMIT
         }
         return PHK_OK;
     };
@@ -1541,9 +1472,9 @@ extern "C" int phk_chain_set_grouped(phk_ctx *ctx, phk_chain *c, const double *l
 
 // backward then forward over the records of the groups at work
 static int chain_group_forward_backward(phk_ctx *ctx, const phk_chain *c) {
-    const double *E = c->E.as<double>(), *M = c->M.as<double>(), *par = c->g_par.as<double>();
+    const double *E = c->E.as<double>(), *M = c->M.as<double>(), *par = c->grp.par.as<double>();
     const uint64_t *off = c->off.as<uint64_t>();
-    const uint32_t *rg = c->g_rg.as<uint32_t>();
+    const uint32_t *rg = c->grp.rg.as<uint32_t>();
 #define CH_GFB(SP)                                                                                                            \
     {                                                                                                                         \
         const dim3 grid(chain_grid(c->R, 64 / SP, CH_BLOCKS_MAX));                                                            \
@@ -1562,8 +1493,8 @@ static int chain_group_viterbi(phk_ctx *ctx, const phk_chain *c) {
 #define CH_GVIT(SP)                                                                                                           \
     PHK_LAUNCH(ctx, "phk_chain_group_viterbi_kernel",                                                                         \
                phk_chain_group_viterbi_kernel<SP><<<dim3(chain_grid(c->R, 64 / SP, CH_BLOCKS_MAX)), dim3(64), 0, ctx->stream>>>( \
-                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->R, c->S, c->g_rg.as<uint32_t>(),           \
-                   c->g_qpar.as<int64_t>(), c->BP.as<uint8_t>(), c->score.as<int64_t>(), c->last.as<uint8_t>()))
+                   c->E.as<double>(), c->M.as<double>(), c->off.as<uint64_t>(), c->R, c->S, c->grp.rg.as<uint32_t>(),         \
+                   c->grp.qpar.as<int64_t>(), c->BP.as<uint8_t>(), c->score.as<int64_t>(), c->last.as<uint8_t>()))
     CHAIN_BY_SP(c->S, CH_GVIT);
 #undef CH_GVIT
     return PHK_OK;
@@ -1574,7 +1505,7 @@ static int chain_group_fold(phk_ctx *ctx, const phk_chain *c, const std::vector<
         if (lv.second == lv.first) continue;
         PHK_LAUNCH(ctx, "phk_chain_group_fold_kernel",
                    phk_chain_group_fold_kernel<<<dim3((unsigned)(lv.second - lv.first)), dim3(256), 0, ctx->stream>>>(
-                       c->g_folds.as<ChainGroupFold>() + lv.first));
+                       c->grp.folds.as<ChainGroupFold>() + lv.first));
     }
     return PHK_OK;
 }
@@ -1583,45 +1514,40 @@ static int chain_group_fold(phk_ctx *ctx, const phk_chain *c, const std::vector<
 // that are not at work
 template <typename T>
 static void chain_group_zero(const phk_chain *c, T *x, uint64_t per, T *y) {
-    for (uint64_t g = 0; g < c->NG; ++g) {
-        if (c->g_work[g]) continue;
+    for (uint64_t g = 0; g < c->grp.G; ++g) {
+        if (c->grp.work[g]) continue;
         uint64_t w0, w1;
         chain_group_span(c, g, w0, w1);
         if (x) std::fill(x + w0 * per, x + w1 * per, (T)0);
-        if (y) std::fill(y + c->g_off[g], y + c->g_off[g + 1], (T)0);
+        if (y) std::fill(y + c->grp.off[g], y + c->grp.off[g + 1], (T)0);
     }
 }
 
 static int chain_group_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, double *Ns, double *xi, double *gamma0,
                                   double *log_evidence, double *log_evidence_rec) {
-    const uint64_t S = c->S, D = c->D, R = c->R, G = c->NG, SS = S * S, Ev = SS + S + 1, Em = S * D + S + 1;
+    const uint64_t S = c->S, D = c->D, G = c->grp.G, SS = S * S, Ev = SS + S + 1, Em = S * D + S + 1;
     PHK_TRY(chain_group_forward_backward(ctx, c));
-    PHK_TRY(chain_group_fold(ctx, c, c->g_levels_v));
-    const bool vec = D % 4 == 0;
-    for (const phk_chain::Batch &b : c->g_batches) {
+    PHK_TRY(chain_group_fold(ctx, c, c->grp.levels_v));
+    for (const ChainGroups::Batch &b : c->grp.batches) {
         PHK_LAUNCH(ctx, "phk_chain_spread_kernel",
                    phk_chain_spread_kernel<<<dim3(chain_grid(b.nb * CH_KP, 256, 4096)), dim3(256), 0, ctx->stream>>>(
                        c->G.as<double>() + b.wa * S, b.nb, (uint32_t)S, c->Rx.as<double>()));
         const dim3 grid((unsigned)(b.d1 - b.d0)), blk(GT_WAVES * 64);
-        const ChainGroupTile *tiles = c->g_etiles.as<ChainGroupTile>() + b.d0;
-        if (vec) {
-            PHK_LAUNCH(ctx, "phk_chain_group_expect_kernel",
-                       phk_chain_group_expect_kernel<true><<<grid, blk, 0, ctx->stream>>>(
-                           c->Rx.as<double>(), b.wa, c->counts, D, c->g_grp.as<ChainGroup>(), tiles, c->M.as<double>(),
-                           (uint32_t)S, Em, c->g_part.as<double>()));
-        } else {
-            PHK_LAUNCH(ctx, "phk_chain_group_expect_kernel",
-                       phk_chain_group_expect_kernel<false><<<grid, blk, 0, ctx->stream>>>(
-                           c->Rx.as<double>(), b.wa, c->counts, D, c->g_grp.as<ChainGroup>(), tiles, c->M.as<double>(),
-                           (uint32_t)S, Em, c->g_part.as<double>()));
-        }
+        const ChainGroupTile *tiles = c->grp.etiles.as<ChainGroupTile>() + b.d0;
+#define CH_GEXPECT(VEC)                                                                                                       \
+        PHK_LAUNCH(ctx, "phk_chain_group_expect_kernel",                                                                      \
+                   phk_chain_group_expect_kernel<VEC><<<grid, blk, 0, ctx->stream>>>(                                         \
+                       c->Rx.as<double>(), b.wa, c->counts, D, c->grp.spans.as<ChainGroup>(), tiles, c->M.as<double>(),       \
+                       (uint32_t)S, Em, c->grp.part.as<double>()))
+        CHAIN_BY_FLAG(D % 4 == 0, CH_GEXPECT);
+#undef CH_GEXPECT
     }
-    PHK_TRY(chain_group_fold(ctx, c, c->g_levels_t));
+    PHK_TRY(chain_group_fold(ctx, c, c->grp.levels_t));
     std::vector<double> v(G * Ev), t(G * Em);
-    PHK_TRY(phk_copy_to_host(ctx, v.data(), c->g_resV.ptr, G * Ev * 8));
-    PHK_TRY(phk_copy_to_host(ctx, t.data(), c->g_resT.ptr, G * Em * 8));
+    PHK_TRY(phk_copy_to_host(ctx, v.data(), c->grp.resV.ptr, G * Ev * 8));
+    PHK_TRY(phk_copy_to_host(ctx, t.data(), c->grp.resT.ptr, G * Em * 8));
     for (uint64_t g = 0; g < G; ++g) {
-        if (!c->g_work[g]) {
+        if (!c->grp.work[g]) {
             std::fill(xi + g * SS, xi + (g + 1) * SS, 0.0), std::fill(gamma0 + g * S, gamma0 + (g + 1) * S, 0.0);
             std::fill(T + g * S * D, T + (g + 1) * S * D, 0.0), std::fill(Ns + g * S, Ns + (g + 1) * S, 0.0);
             log_evidence[g] = 0.0;
@@ -1633,9 +1559,7 @@ static int chain_group_expect_run(phk_ctx *ctx, const phk_chain *c, double *T, d
         std::copy(pt, pt + S * D, T + g * S * D), std::copy(pt + S * D, pt + S * D + S, Ns + g * S);
     }
     if (log_evidence_rec) {
-        std::vector<double> rec(R * Ev);
-        PHK_TRY(phk_copy_to_host(ctx, rec.data(), c->V.ptr, R * Ev * 8));
-        for (uint64_t r = 0; r < R; ++r) log_evidence_rec[r] = rec[r * Ev + SS + S];
+        PHK_TRY(chain_record_evidence(ctx, c, log_evidence_rec));
         chain_group_zero<double>(c, nullptr, 0, log_evidence_rec);
     }
     return PHK_OK;
@@ -1646,7 +1570,7 @@ extern "C" int phk_chain_expect_grouped(phk_ctx *ctx, const phk_chain *c, double
     const char *who = "phk_chain_expect_grouped";
     PHK_ENTER(ctx, "phk_chain_expect_grouped");
     PHK_REQUIRE(c, "%s: NULL chain", who);
-    PHK_REQUIRE(c->NG, "%s: the chain has no groups (phk_chain_set_groups)", who);
+    PHK_REQUIRE(c->grp.G, "%s: the chain has no groups (phk_chain_set_groups)", who);
     PHK_REQUIRE(c->ready, "%s: phk_chain_set_grouped has not succeeded on the chain", who);
     PHK_REQUIRE(T && Ns && xi && gamma0 && log_evidence, "%s: NULL pointer", who);
     const int rc = chain_group_expect_run(ctx, c, T, Ns, xi, gamma0, log_evidence, log_evidence_rec);
